@@ -2,7 +2,9 @@
 """Headline benchmark: gate-applications/sec and achieved HBM GB/s of the gate-application hot
 path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5          # the headline line only
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   # ... and every other measurement and check of an N = 1 run
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # ... and the state the last step left, DIR/state.npy
     python bench.py --gpus N --steps K --warmup W          # N > 1 without a launcher: this process starts its N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -22,6 +24,11 @@ execution of the whole circuit on the HBM-resident state; nothing crosses PCIe i
 `value` = gate-applications per second of the WHOLE 2^n state at every N (one gate of the
 circuit applied to the full state = 1).  Rank 0 prints ONE JSON line and exits non-zero when the run
 is invalid (parity or norm check failed, probe knobs in the environment).
+
+N = 1 without --full: set-up (layout search, planning), W warm-up steps, the K timed steps, the norm of the state they
+leave, the roofline of the dominant kernel from the timed steps' own HIP events, the line.  --full adds what takes runs
+of its own: the sustained region, the timed plan's fingerprint check, copy / stream ceilings, the fused run at
+--fused-qubits, the API-path timings, the per-target sweep, the CPU baselines with their parity.
 """
 from __future__ import annotations
 
@@ -42,6 +49,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level
 PARITY_TOL = 1e-10
 NORM_TOL = 1e-9
 ALLOWED_ENV: set = set()                 # no QSIM_* variable is read by anything this script times
+DUMP_MAX_AMPLITUDES = 1 << 21            # --dump-outputs: 2^21 amplitudes x 16 B = 32 MiB
+DUMP_SEED = 20261015
 
 
 class SectionBudget:
@@ -129,7 +138,22 @@ def parse_args():
     ap.add_argument("--other-api-timeout", type=float, default=150.0,
                     help="N > 1: seconds the second exchange API's section may take before the line is printed without it and the ranks exit")
     ap.add_argument("--ab-steps", type=int, default=3, help="N > 1: steps of the short A/B regions (fused re-layout off, other exchange API)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also measure and check everything beyond the headline figure (the longer sustained region, the "
+                         "timed plan's fingerprint check, copy / stream ceilings, the fused run at --fused-qubits, the API-path "
+                         "timings, the per-target sweep, the CPU baselines and their parity); the --no-* options above then "
+                         "leave sections out.  Without it a run sets up, warms up, times the steps and prints the line.  "
+                         "(N > 1 runs are unchanged by it: their optional sections follow --budget-seconds and --no-*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps write the state they left, in logical qubit order, to DIR/state.npy "
+                         "(float64, [re, im] per amplitude): the whole state up to %d amplitudes, above that a fixed, seeded "
+                         "sample of about as many logical indices (sorted), the same in every run" % DUMP_MAX_AMPLITUDES)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def refuse_probe_environment():
@@ -334,6 +358,39 @@ def api_path_record(circuit: dict, device: int, engine, invalid: list) -> dict:
     return rec
 
 
+def dump_outputs(engine, out_dir: Path) -> dict:
+    """--dump-outputs: the state the timed steps left, as a caller of the path sees it (logical qubit order, the engine's
+    layout undone), to out_dir/state.npy as float64 [re, im] rows.  Above DUMP_MAX_AMPLITUDES amplitudes: the sorted,
+    de-duplicated draw of DUMP_MAX_AMPLITUDES logical indices from a generator seeded with DUMP_SEED -- the same indices in
+    every run of the same size.  The state is read in physical slices of 2^24 amplitudes; nothing on the device changes."""
+    n = engine.n
+    size = 1 << n
+    if size <= DUMP_MAX_AMPLITUDES:
+        logical = np.arange(size, dtype=np.int64)
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        logical = np.unique(rng.integers(0, size, size=DUMP_MAX_AMPLITUDES, dtype=np.int64))
+    phys = logical
+    if engine.l2p is not None:
+        phys = np.zeros_like(logical)
+        for q, p in enumerate(engine.l2p):
+            phys |= ((logical >> q) & 1) << p
+    order = np.argsort(phys, kind="stable")
+    phys_sorted = phys[order]
+    amps = np.empty(logical.size, dtype=np.complex128)
+    step = 1 << 24
+    for off in range(0, size, step):
+        lo, hi = np.searchsorted(phys_sorted, [off, off + step])
+        if lo == hi:
+            continue
+        chunk = engine.state.download(off, min(step, size - off))
+        amps[order[lo:hi]] = chunk[phys_sorted[lo:hi] - off]
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "state.npy", np.stack([amps.real, amps.imag], axis=1))
+    return {"files": ["state.npy"], "amplitudes": int(logical.size),
+            "sample": None if logical.size == size else {"seed": DUMP_SEED, "draws": DUMP_MAX_AMPLITUDES}}
+
+
 # ---------------------------------------------------------------------------------- N = 1
 def run_single(args, k: int) -> tuple[dict, list[str]]:
     from quantum_simulations_amd.circuits import random_1q_cx_circuit
@@ -375,10 +432,12 @@ def run_single(args, k: int) -> tuple[dict, list[str]]:
     passes = engine.passes_per_step(plan)
     if abs(norm2 - 1.0) > NORM_TOL:
         invalid.append(f"|norm2 - 1| = {abs(norm2 - 1.0):.3e} > {NORM_TOL}")
+    # what the last timed step left, before anything below executes on the state again
+    outputs = dump_outputs(engine, Path(args.dump_outputs)) if args.dump_outputs else None
 
     # a second, longer timed region (no per-launch events): the same step repeated for ~sustain_seconds
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         reps = max(args.steps, int(args.sustain_seconds / max(dt / args.steps, 1e-6)))
         engine.barrier()
         t1 = time.perf_counter()
@@ -394,7 +453,7 @@ def run_single(args, k: int) -> tuple[dict, list[str]]:
     # norm check): one execution of `plan` from |0..0>, its layout-aware fingerprint, and the same of a plan made with
     # layout = "identity" (index bit = qubit, the library's own tiles)
     timed_plan_check = None
-    if args.mode == "fused" and not args.no_plan_check:
+    if args.full and args.mode == "fused" and not args.no_plan_check:
         seed = 20260504
         engine.init_zero_state()
         engine.execute(plan)
@@ -411,8 +470,10 @@ def run_single(args, k: int) -> tuple[dict, list[str]]:
             invalid.append(f"the timed plan's state differs from an identity-layout execution of the same circuit: "
                            f"fingerprints {abs(fp_timed - fp_plain):.3e} apart > {PARITY_TOL}")
 
-    copy = engine.copy_ceiling()                     # same-run device-to-device copy of a same-size buffer
-    stream = engine.stream_ceiling()                 # ... and the best of everything that streams (copies, in-place RMW)
+    # (--full: timing runs of their own) same-run device-to-device copy of a same-size buffer, and the best of everything
+    # that streams (copies, in-place RMW)
+    copy = engine.copy_ceiling() if args.full else None
+    stream = engine.stream_ceiling() if args.full else None
     dom = max(prof, key=lambda e: e["total_ms"]) if prof else None
     roofline = None
     if dom:
@@ -425,9 +486,6 @@ def run_single(args, k: int) -> tuple[dict, list[str]]:
                     "kernel": dom["kernel"], "launches": dom["launches"],
                     "avg_launch_ms": round(dom["total_ms"] / dom["launches"], 4),
                     "bytes_per_launch": dom["hbm_bytes"] / dom["launches"],
-                    "copy_ceiling_GBps": copy["GBps"], "frac_of_copy_ceiling": round(moved / copy["GBps"], 4),
-                    # against what this box was SEEN to stream in this run (max of copy kernels, hipMemcpy, in-place RMW)
-                    "stream_ceiling_GBps": stream["GBps"], "frac_of_achievable": round(moved / stream["GBps"], 4),
                     "frac_x_passes": round(moved / HBM_PEAK_GBS * passes, 3),
                     "gates_per_launch": round(n_gates * args.steps / dom["launches"], 2),
                     "algorithmic_GBps": round(dom["algorithmic_bytes"] / secs / 1e9, 1),
@@ -435,6 +493,10 @@ def run_single(args, k: int) -> tuple[dict, list[str]]:
                             "HIP-event time of the launches in the timed region; algorithmic_GBps sums SURVEY 8d's "
                             "per-gate bytes over the gates a fused launch applies (it may exceed the physical peak "
                             "and is not a roofline fraction)"}
+        if copy is not None:
+            roofline.update({"copy_ceiling_GBps": copy["GBps"], "frac_of_copy_ceiling": round(moved / copy["GBps"], 4),
+                             # against what this box was SEEN to stream in this run (max of copy kernels, hipMemcpy, in-place RMW)
+                             "stream_ceiling_GBps": stream["GBps"], "frac_of_achievable": round(moved / stream["GBps"], 4)})
     layout_rec = ("identity" if getattr(plan, "l2p", None) is None else
                   {"logical_to_index_bit": plan.l2p, **getattr(plan, "layout_info", {})})
     out = {
@@ -453,7 +515,7 @@ def run_single(args, k: int) -> tuple[dict, list[str]]:
                    "qubit_layout": layout_rec,
                    "value_is": "the steady state of a plan that is executed repeatedly (layout search, planning and the first, "
                                "cold execution are outside the timed region: `plan_seconds`, `first_execution_ms`); what ONE call "
-                               "of the drop-in entry points costs end to end is `api_path`"},
+                               "of the drop-in entry points costs end to end is `api_path` (--full)"},
         "timed_seconds": round(dt, 4),
         # which index bit a qubit lives on, and what choosing it cost (host search + timing runs on the device), at the top
         # level too: `value` is the steady state AFTER that search
@@ -468,17 +530,20 @@ def run_single(args, k: int) -> tuple[dict, list[str]]:
         "copy_ceiling": copy,
         "stream_ceiling": stream,
         "kernel_breakdown": [{**e, "total_ms": round(e["total_ms"], 3)} for e in prof],
+        "full": args.full,
     }
-    if args.fused_qubits and args.fused_qubits != n and args.mode == "fused":
+    if outputs is not None:
+        out["outputs"] = outputs
+    if args.full and args.fused_qubits and args.fused_qubits != n and args.mode == "fused":
         # the same workload family at the largest single-GPU size of BASELINE.json's list (16 GiB state): ~2 s of GPU
         # time, so the 30-qubit figure of the fused pass is timed by the driver's run and not only by profiles/
         out["fused%d" % args.fused_qubits] = fused_run(args.fused_qubits, args.depth, steps=5, warmup=2,
                                                         device=int(os.environ.get("LOCAL_RANK", "0")), layout=args.layout)
         if abs(out["fused%d" % args.fused_qubits]["norm2_after"] - 1.0) > NORM_TOL:
             invalid.append(f"fused{args.fused_qubits}: norm check failed")
-    if not args.no_api_path:
+    if args.full and not args.no_api_path:
         out["api_path"] = api_path_record(circuit, int(os.environ.get("LOCAL_RANK", "0")), engine, invalid)
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         # BASELINE config 3 / north-star target: one gate per launch on a 30-qubit random state (no fusion
         # across the timed gates), every target index, fractions of the 8 TB/s peak of SURVEY 8d's
         # algorithmic bytes (H 32 N, T and CNOT 16 N)
@@ -490,7 +555,7 @@ def run_single(args, k: int) -> tuple[dict, list[str]]:
             "achieved": round(h["median_frac"] * HBM_PEAK_GBS, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": h["median_frac"], "min_frac_over_targets": h["min_frac"],
             "workload": f"H on every target of a {sw['n_qubits']}-qubit state (32 B x 2^n per launch)"}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         base, psi_cpu, done = cpu_baseline(circuit, args.cpu_seconds)
         out["cpu_baseline"] = base
         out["vs_cpu_baseline"] = round(out["value"] / base["value"], 1)
@@ -856,6 +921,8 @@ def main():
     refuse_probe_environment()
     if args.gpus < 1 or args.gpus & (args.gpus - 1):
         raise SystemExit("number of GPUs must be a power of two (shards are indexed by high qubits)")
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs writes the state of a one-GPU run (--gpus 1)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))

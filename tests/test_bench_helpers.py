@@ -5,6 +5,9 @@ import json
 import sys
 from pathlib import Path
 
+import numpy as np
+import pytest
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -61,3 +64,50 @@ def test_probe_environment_is_refused(monkeypatch):
         bench.refuse_probe_environment()
     monkeypatch.delenv("QSIM_DIST_BACKEND")
     bench.refuse_probe_environment()
+
+
+class _HostEngine:
+    """The two things dump_outputs reads of an engine: `l2p` and `state.download(offset, count)`, over a host array that
+    holds a logical state in the layout l2p (logical qubit q on index bit l2p[q])."""
+
+    def __init__(self, psi_logical, l2p):
+        self.n = int(psi_logical.size).bit_length() - 1
+        self.l2p = l2p
+        phys = np.arange(psi_logical.size)
+        if l2p is not None:
+            logical = np.zeros_like(phys)
+            for q, p in enumerate(l2p):
+                logical |= ((phys >> p) & 1) << q
+            phys = logical
+        held = psi_logical[phys]
+        self.state = type("S", (), {"download": staticmethod(lambda off, cnt: held[off:off + cnt].copy())})()
+
+
+def test_dump_outputs_undoes_the_layout_and_samples_the_same_indices(tmp_path, monkeypatch):
+    bench = _bench()
+    rng = np.random.default_rng(5)
+    n = 12
+    psi = rng.standard_normal(1 << n) + 1j * rng.standard_normal(1 << n)
+    l2p = list(rng.permutation(n))
+    rec = bench.dump_outputs(_HostEngine(psi, l2p), tmp_path / "a")          # whole state
+    got = np.load(tmp_path / "a" / "state.npy")
+    assert got.dtype == np.float64 and got.shape == (1 << n, 2) and rec["sample"] is None
+    np.testing.assert_array_equal(got[:, 0] + 1j * got[:, 1], psi)
+    monkeypatch.setattr(bench, "DUMP_MAX_AMPLITUDES", 1 << 9)                 # sampled: fixed indices, same in every run
+    bench.dump_outputs(_HostEngine(psi, l2p), tmp_path / "b")
+    bench.dump_outputs(_HostEngine(psi, None), tmp_path / "c")
+    b, c = np.load(tmp_path / "b" / "state.npy"), np.load(tmp_path / "c" / "state.npy")
+    idx = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, 1 << n, size=1 << 9, dtype=np.int64))
+    np.testing.assert_array_equal(b, c)
+    np.testing.assert_array_equal(b[:, 0] + 1j * b[:, 1], psi[idx])
+
+
+def test_steps_and_warmup_are_checked(monkeypatch):
+    bench = _bench()
+    for argv in (["--steps", "0"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            bench.parse_args()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    args = bench.parse_args()
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None

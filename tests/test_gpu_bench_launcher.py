@@ -65,13 +65,13 @@ def test_four_ranks_sharing_one_gpu_through_the_launcher():
 
 
 def test_single_gpu_line_carries_the_contract_fields():
-    """`python3 bench.py` at N = 1 (a small state, short CPU column): ONE JSON line with the fields the driver reads --
+    """`python3 bench.py --full` at N = 1 (a small state, short CPU column): ONE JSON line with the fields the driver reads --
     metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype /
     data / config.workload, `roofline` {bound, achieved, peak, unit, frac, traffic}, `cpu_baseline` {value, unit, cores,
     kind, sample} -- exit code 0, no `invalid`; and exit code 2 with a QSIM_* knob in the environment."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE") and not k.startswith("QSIM_")}
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--local-qubits", "22", "--steps", "3", "--warmup", "1", "--sweep-qubits", "20",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--local-qubits", "22", "--steps", "3", "--warmup", "1", "--sweep-qubits", "20",
            "--fused-qubits", "0", "--sustain-seconds", "0", "--cpu-seconds", "2"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
@@ -107,3 +107,56 @@ def test_single_gpu_line_carries_the_contract_fields():
     assert d["timed_plan_check"]["fingerprint_abs_diff_vs_identity_layout_plan"] < 1e-10
     bad = subprocess.run(cmd, cwd=ROOT, env=dict(env, QSIM_PLAN_LOOKAHEAD="0"), capture_output=True, text=True, timeout=120)
     assert bad.returncode == 2 and "refusing" in bad.stdout
+
+
+def _plain_line(args, env, timeout=300):
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py")] + args, cwd=ROOT, env=env, capture_output=True, text=True,
+                         timeout=timeout)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_plain_single_gpu_line_and_its_dumped_state(tmp_path):
+    """`python3 bench.py` without --full: the headline fields, none of the --full sections, `steps` timed steps; and
+    --dump-outputs writes the state the last step left in logical qubit order -- at 16 qubits the whole state, equal to
+    the CPU oracle's after warmup + steps executions of the circuit; at 26 qubits (layout search on) the same seeded
+    sample as an identity-layout run of the same circuit."""
+    import numpy as np
+
+    from oracle import dense_oracle
+    from quantum_simulations_amd.circuit.io import validate_circuit_dict
+    from quantum_simulations_amd.circuits import random_1q_cx_circuit
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE") and not k.startswith("QSIM_")}
+    d = _plain_line(["--gpus", "1", "--local-qubits", "16", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "s16")], env)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False and "invalid" not in d
+    assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["ms_per_step"] > 0 and d["value"] > 0
+    for key in ("cpu_baseline", "sweep30", "api_path", "fused30"):
+        assert key not in d, key
+    assert d["sustained"] is None and d["timed_plan_check"] is None and d["copy_ceiling"] is None
+    got = np.load(tmp_path / "s16" / "state.npy")
+    assert got.dtype == np.float64 and got.shape == (1 << 16, 2) and d["outputs"]["amplitudes"] == 1 << 16
+    cd = validate_circuit_dict(random_1q_cx_circuit(16, depth=40))
+    psi = np.zeros(1 << 16, dtype=np.complex128)
+    psi[0] = 1.0
+    for _ in range(3):
+        for g in cd["gates"]:
+            U = dense_oracle.gate_matrix(g["gate"], g["params"])
+            (dense_oracle.apply_1q if len(g["qubits"]) == 1 else dense_oracle.apply_2q)(psi, *g["qubits"], U)
+    np.testing.assert_allclose(got[:, 0] + 1j * got[:, 1], psi, rtol=0, atol=1e-10)
+
+    searched = _plain_line(["--local-qubits", "26", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")], env)
+    plain = _plain_line(["--local-qubits", "26", "--steps", "2", "--warmup", "1", "--layout", "identity",
+                         "--dump-outputs", str(tmp_path / "b")], env)
+    assert searched["layout"] == "searched" and plain["layout"] == "identity"
+    a, b = np.load(tmp_path / "a" / "state.npy"), np.load(tmp_path / "b" / "state.npy")
+    sys.path.insert(0, str(ROOT))
+    import bench
+    idx = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, 1 << 26, size=bench.DUMP_MAX_AMPLITUDES, dtype=np.int64))
+    assert a.shape == b.shape == (idx.size, 2) and searched["outputs"]["amplitudes"] == idx.size
+    np.testing.assert_allclose(a, b, rtol=0, atol=1e-12)
+    assert np.abs(a).max() > 0

@@ -5,7 +5,7 @@ out=${1:-gpurun_out/clock_probe.txt}
 cd "$(dirname "$0")/.."
 mkdir -p "$(dirname "$out")"
 { echo "== idle"; rocm-smi --showclocks --showpower 2>&1 | grep -E "sclk|mclk|fclk|Power" ; } > "$out"
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-sweep --sustain-seconds 12 > gpurun_out/clock_probe_bench.json 2>/dev/null &
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-sweep --sustain-seconds 12 > "${out%.*}_bench.json" 2>/dev/null &
 bpid=$!
 sleep 1
 for i in $(seq 1 60); do
