@@ -336,6 +336,13 @@ int qsim_export_nonzero(qsim_chunk* c, double eps, uint64_t capacity, uint64_t* 
                         uint64_t* n_rows);
 int qsim_sync(qsim_chunk* c);
 int qsim_norm2(qsim_chunk* c, double* out);               /* sum |amp|^2               */
+/* Joint outcome probabilities of r measured qubits (1 <= r <= 8), unnormalised:
+ *   out[m] = sum of |amp_i|^2 over every i whose bit qubits[j] equals bit j of m, for m < 2^r.
+ * The summation order is fixed, so the result is bitwise reproducible. Blocks until out is written.
+ * One read-only pass over the chunk (any qubit set, in any order: one partial histogram per workgroup, summed in
+ * workgroup order on the device, no atomics); only the 2^r doubles cross to the host.  Qubits >= log2(chunk) fail with
+ * QSIM_ERR_NONLOCAL.  Dynamic circuits (mid-circuit measurement, reset) sample their outcomes from it. */
+int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out);
 /* max_i |amp_i - expected_i| for closed-form states, evaluated on the device:
  * kind 0: GHZ (1/sqrt2 at local index 0 of the first chunk and at the last index of the
  *         last), kind 1: GHZ+QFT  2^-(n+1)/2 (1 + exp(-2 pi i y / 2^n)), y = base + i.  */

@@ -106,6 +106,7 @@ SIGNATURES = {
     "qsim_export_nonzero": (C.c_int, [_P, C.c_double, C.c_uint64, _P, _P, C.POINTER(C.c_uint64)]),
     "qsim_sync": (C.c_int, [_P]),
     "qsim_norm2": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "qsim_probabilities": (C.c_int, [_P, C.c_int, _P, _P]),
     "qsim_max_abs_err_closed_form": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint64,
                                                C.POINTER(C.c_double)]),
     "qsim_max_abs_err_closed_form_perm": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint64, _P,

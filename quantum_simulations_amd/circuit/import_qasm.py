@@ -26,7 +26,8 @@ into one 2x2 before they reach the device, so the extra Cliffords cost nothing t
 
 A statevector differs from qiskit's by that one unit-modulus factor; probabilities, expectation values and every
 controlled use are unaffected.  Everything else (reset, if(...), opaque, mid-circuit measurement ...) raises
-ValueError("unsupported gate ...") like validate_circuit_dict does for unknown names.  Parity: the importer has no counterpart in the
+ValueError("unsupported gate ...") like validate_circuit_dict does for unknown names.  `qasm_to_dynamic(text)` reads
+reset, measurements anywhere and if(creg==int) as well, into a dynamic program (circuit/dynamic.py).  Parity: the importer has no counterpart in the
 reference, so there is no reference fixture for it -- "parity unpinned"; the tests check it against
 explicit matrices on small registers.  Qubit q[i] of the first register is qubit i (bit i of the
 amplitude index: qiskit's and this engine's little-endian convention); further registers follow.
@@ -285,6 +286,41 @@ def _split_args(text: str) -> list[str]:
 
 
 def qasm_to_dict(text: str) -> dict:
+    return _parse(text, dynamic=False)
+
+
+def qasm_to_dynamic(text: str, keep_terminal_measure: bool = False) -> dict:
+    """OpenQASM 2.0 -> dynamic program (circuit/dynamic.py): everything `qasm_to_dict` reads, plus `reset`,
+    `measure a -> b` anywhere (one qubit or a whole register) and `if(creg==int) <gate>` (a user gate or a ccx under an
+    `if` expands to contract gates that all carry the condition).  A measurement that no later gate or reset acts on
+    and whose register no later `if` reads is terminal: dropped, as `qasm_to_dict` drops it, unless
+    keep_terminal_measure.  `if` around a measure or a reset is not read (ValueError)."""
+    return _parse(text, dynamic=True, keep_terminal_measure=keep_terminal_measure)
+
+
+_IF = re.compile(r"^if\s*\(\s*([A-Za-z_][A-Za-z_0-9]*)\s*==\s*(\d+)\s*\)\s*(.*)$", re.S)
+
+
+def _drop_terminal_measures(ops: list) -> list:
+    """Keep a measurement only when a later gate or reset acts on its qubit or a later `if` reads its register."""
+    keep = [True] * len(ops)
+    touched: set[int] = set()       # qubits a later gate / reset acts on
+    read: set[str] = set()           # registers a later `if` reads
+    for i in range(len(ops) - 1, -1, -1):
+        op = ops[i]
+        if op.get("op") == "measure":
+            keep[i] = op["qubit"] in touched or op["clbit"][0] in read
+            continue
+        if op.get("op") == "reset":
+            touched.add(op["qubit"])
+            continue
+        touched.update(op["qubits"])
+        if "condition" in op:
+            read.add(op["condition"]["creg"])
+    return [op for op, k in zip(ops, keep) if k]
+
+
+def _parse(text: str, dynamic: bool, keep_terminal_measure: bool = False) -> dict:
     text = re.sub(r"//[^\n]*", "", text)
     # user gate definitions: gate name(params) qargs { body }
     macros: dict[str, tuple[list[str], list[str], list[str]]] = {}
@@ -302,6 +338,7 @@ def qasm_to_dict(text: str) -> dict:
     if re.search(r"\bopaque\b", text):
         raise _unsupported("opaque")
     regs: dict[str, tuple[int, int]] = {}
+    cregs: dict[str, int] = {}
     n_qubits = 0
     gates: list = []
     measured: set[int] = set()
@@ -350,6 +387,60 @@ def qasm_to_dict(text: str) -> dict:
             raise ValueError(f"gate {name!r}: wrong number of parameters or qubits")
         _emit_builtin(name, params, qubits, gates)
 
+    def resolve_clbits(arg: str) -> list[tuple[str, int]]:
+        m = re.match(r"^([A-Za-z_][A-Za-z_0-9]*)\s*(?:\[\s*(\d+)\s*\])?$", arg)
+        if not m or m.group(1) not in cregs:
+            raise ValueError(f"unknown classical bit argument {arg!r}")
+        size = cregs[m.group(1)]
+        if m.group(2) is None:
+            return [(m.group(1), i) for i in range(size)]
+        if int(m.group(2)) >= size:
+            raise ValueError(f"classical bit index out of range in {arg!r}")
+        return [(m.group(1), int(m.group(2)))]
+
+    def gate_statement(stmt: str) -> None:
+        sm = _STMT_GATE.match(stmt)
+        if not sm:
+            raise ValueError(f"cannot parse {stmt!r}")
+        name = sm.group(1)
+        params = [_eval_expr(e, {}) for e in _split_args(sm.group(2) or "")]
+        args = [resolve(a) for a in _split_args(sm.group(3))]
+        if not args:
+            raise ValueError(f"gate {name!r} without qubits")
+        width = max(len(a) for a in args)
+        if any(len(a) not in (1, width) for a in args):
+            raise ValueError(f"register sizes differ in {stmt!r}")
+        for i in range(width):                      # register broadcast
+            apply(name, params, [a[i] if len(a) > 1 else a[0] for a in args])
+
+    def dynamic_statement(stmt: str) -> None:       # reset / measure / if (dynamic programs only)
+        if stmt.startswith("measure"):
+            mm = re.match(r"^measure\s+(.+?)\s*->\s*(.+)$", stmt, re.S)
+            if not mm:
+                raise ValueError(f"bad measure statement {stmt!r}")
+            qs, cs = resolve(mm.group(1).strip()), resolve_clbits(mm.group(2).strip())
+            if len(qs) != len(cs):
+                raise ValueError(f"register sizes differ in {stmt!r}")
+            gates.extend({"op": "measure", "qubit": q, "clbit": [c, i]} for q, (c, i) in zip(qs, cs))
+            return
+        if re.match(r"^reset\b", stmt):
+            gates.extend({"op": "reset", "qubit": q} for q in resolve(stmt[len("reset"):].strip()))
+            return
+        im = _IF.match(stmt)
+        if not im:
+            raise ValueError(f"cannot parse {stmt!r}")
+        creg, value, body = im.group(1), int(im.group(2)), im.group(3).strip()
+        if creg not in cregs:
+            raise ValueError(f"unknown classical register {creg!r} in {stmt!r}")
+        if value >= 1 << cregs[creg]:
+            raise ValueError(f"value {value} does not fit register {creg!r} in {stmt!r}")
+        if re.match(r"^(measure|reset|if)\b", body):
+            raise _unsupported(body.split()[0].split("(")[0], "a measure, reset or if under an if is not read")
+        start = len(gates)
+        gate_statement(body)
+        for g in gates[start:]:
+            g["condition"] = {"creg": creg, "value": value}
+
     for raw in text.split(";"):
         stmt = raw.strip()
         if not stmt:
@@ -365,8 +456,13 @@ def qasm_to_dict(text: str) -> dict:
             if m.group(1) == "qreg":
                 regs[m.group(2)] = (n_qubits, int(m.group(3)))
                 n_qubits += int(m.group(3))
+            else:
+                cregs[m.group(2)] = int(m.group(3))
             continue
         if stmt.startswith("barrier"):
+            continue
+        if dynamic and (stmt.startswith("measure") or stmt.startswith("reset") or stmt.startswith("if")):
+            dynamic_statement(stmt)
             continue
         if stmt.startswith("measure"):
             mm = re.match(r"^measure\s+(.+?)\s*->\s*(.+)$", stmt, re.S)
@@ -391,9 +487,17 @@ def qasm_to_dict(text: str) -> dict:
             apply(name, params, [a[i] if len(a) > 1 else a[0] for a in args])
     if n_qubits == 0:
         raise ValueError("no qreg declared")
+    if dynamic:
+        return {"number_of_qubits": n_qubits, "cregs": dict(cregs),
+                "ops": gates if keep_terminal_measure else _drop_terminal_measures(gates)}
     return {"number_of_qubits": n_qubits, "gates": gates}
 
 
 def load_qasm(path) -> dict:
     with open(path) as f:
         return qasm_to_dict(f.read())
+
+
+def load_qasm_dynamic(path, keep_terminal_measure: bool = False) -> dict:
+    with open(path) as f:
+        return qasm_to_dynamic(f.read(), keep_terminal_measure=keep_terminal_measure)

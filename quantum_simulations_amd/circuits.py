@@ -124,3 +124,61 @@ def random_clifford_t_circuit(n_qubits: int, depth: int = 60, seed: int = 202604
             else:
                 gates.append({"qubits": [int(rng.integers(n_qubits))], "gate": name})
     return _circuit(n_qubits, gates)
+
+
+# ---- dynamic programs (circuit/dynamic.py) in the shape of QASMBench's reset / if inputs, as OpenQASM 2 text
+# (read with circuit/import_qasm.qasm_to_dynamic).  Used by tools/dynamic_probe.py and the dynamic-circuit tests.
+_QASM_HDR = 'OPENQASM 2.0;\ninclude "qelib1.inc";\n'
+
+
+def dynamic_bwt_style_qasm(n: int, n_gates: int = 240, every: int = 12, n_anc: int | None = None, seed: int = 0) -> str:
+    """bwt-like: x / cx / ccx on random qubits after a layer of h on the data qubits; the ancillas (the top n_anc
+    qubits) are reset every `every` gates; terminal measurement of everything."""
+    import random
+    rng = random.Random(seed)
+    n_anc = max(2, min(8, n // 4)) if n_anc is None else n_anc
+    lines = [_QASM_HDR, f"qreg q[{n}];", f"creg c[{n}];"]
+    lines += [f"h q[{i}];" for i in range(n - n_anc) if rng.random() < 0.5]
+    for g in range(n_gates):
+        kind = rng.choice(("x", "cx", "ccx", "ccx"))
+        qs = rng.sample(range(n), {"x": 1, "cx": 2, "ccx": 3}[kind])
+        lines.append(f"{kind} " + ",".join(f"q[{q}]" for q in qs) + ";")
+        if (g + 1) % every == 0:
+            lines += [f"reset q[{a}];" for a in range(n - n_anc, n)]
+    lines.append("measure q -> c;")
+    return "\n".join(lines) + "\n"
+
+
+def dynamic_square_root_style_qasm(n: int, n_blocks: int = 6, seed: int = 0) -> str:
+    """square_root-like: blocks of h / ry / cx / ccx followed by a run of 8 resets (random qubits, any order)."""
+    import random
+    rng = random.Random(seed)
+    lines = [_QASM_HDR, f"qreg q[{n}];", f"creg c[{n}];"]
+    for _ in range(n_blocks):
+        for _ in range(3 * n):
+            kind = rng.choice(("h", "ry", "cx", "ccx"))
+            qs = rng.sample(range(n), {"h": 1, "ry": 1, "cx": 2, "ccx": 3}[kind])
+            par = f"({rng.uniform(0.2, 2.9):.6f})" if kind == "ry" else ""
+            lines.append(f"{kind}{par} " + ",".join(f"q[{q}]" for q in qs) + ";")
+        lines += [f"reset q[{q}];" for q in rng.sample(range(n), min(8, n))]
+    lines.append("measure q -> c;")
+    return "\n".join(lines) + "\n"
+
+
+def dynamic_cc_style_qasm(n: int, seed: int = 0) -> str:
+    """cc-like: h on all but the last qubit, a parity onto it, ONE mid-circuit measurement round of two qubits into a
+    register, then gates under if(c==v) for every v: single gates, a ccx and a user gate."""
+    import random
+    rng = random.Random(seed)
+    lines = [_QASM_HDR, "gate tw a,b { h a; cx a,b; t b; }", f"qreg q[{n}];", "creg c[2];", f"creg d[{n}];"]
+    lines += [f"h q[{i}];" for i in range(n - 1)]
+    lines += [f"ry({rng.uniform(0.3, 2.8):.6f}) q[{i}];" for i in range(n - 1)]
+    lines += [f"cx q[{i}],q[{n - 1}];" for i in range(n - 1)]
+    lines += ["measure q[0] -> c[0];", f"measure q[{n - 1}] -> c[1];"]
+    for v in range(4):
+        a, b, t = rng.sample(range(1, n - 1), 3)
+        lines += [f"if(c=={v}) x q[{a}];", f"if(c=={v}) ccx q[{a}],q[{b}],q[{t}];", f"if(c=={v}) tw q[{b}],q[{t}];",
+                  f"if(c=={v}) h q[{t}];"]
+    lines += [f"cx q[{i}],q[{i + 1}];" for i in range(1, n - 2)]
+    lines.append("measure q -> d;")
+    return "\n".join(lines) + "\n"

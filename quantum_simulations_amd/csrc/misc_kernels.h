@@ -188,6 +188,91 @@ __global__ __launch_bounds__(kBlock) void k_norm2_partial(const double2* p, u64 
   block_reduce_store<false>(acc, partial);
 }
 
+// ---- joint outcome probabilities of r <= 8 qubits (qsim_probabilities): one read-only pass, a fixed summation order.
+// Index bits 0..7 are the 256 threads of a workgroup (a wave reads 1 KiB contiguous, 16 B per lane).  The host deals the
+// bits above out as ITEM bits (<= 3: the 2^ITEM amplitudes a thread loads per step), WORKGROUP bits (<= 11) and LOOP bits
+// (walked in ascending order by every workgroup).  Selected qubits above bit 7 go to item and workgroup bits first -- at
+// most 8 of them against up to 14 places -- so the bin of an amplitude depends on its lane, item and workgroup, never on
+// the loop step, and a thread keeps one running sum per item.  At the end each wave folds its lanes over the lane bits
+// that are NOT selected (butterfly; lanes a and a ^ off add the same two values), one lane per bin adds the result into
+// the wave's row of an LDS histogram, and the four rows go in wave order into the workgroup's partial histogram.
+// k_hist_sum adds the partials in workgroup order.  No atomics anywhere: every run gives the same bits.
+struct HistArgs {
+  const double2* amp;
+  u64 n;                  // amplitudes (threads >= n load nothing: chunks of fewer than 256)
+  u64 loop_mask;          // index bits walked by the loop (none of them selected)
+  int item_bit[3];        // index bit of item bit j
+  int wg_bit[11];         // index bit of workgroup-id bit j
+  int n_wg_bits;
+  int q[8];               // bin bit j <-> index bit q[j]
+  int r;
+  int lane_sel;           // the selected index bits among bits 0..5 (inside a wave), as a mask
+  double* partial;        // [workgroup][2^r]
+};
+template <int ITEM_BITS, bool NT>
+__global__ __launch_bounds__(kBlock) void k_hist(const HistArgs a) {
+  constexpr int ITEMS = 1 << ITEM_BITS;
+  __shared__ double hist[(kBlock / 64) * 256];
+  const int nbins = 1 << a.r;
+  // XCD-contiguous workgroup order (logical_block<true>) when the grid is whole octets
+  const u64 wg = (gridDim.x & 7) ? (u64)blockIdx.x : logical_block<true>();
+  for (int i = threadIdx.x; i < (kBlock / 64) * nbins; i += kBlock) hist[i] = 0.0;
+  u64 base = threadIdx.x;
+  for (int j = 0; j < a.n_wg_bits; ++j) base |= ((wg >> j) & 1ull) << a.wg_bit[j];
+  u64 item_off[ITEMS];
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) {
+    u64 o = 0;
+#pragma unroll
+    for (int j = 0; j < ITEM_BITS; ++j) o |= (u64)((it >> j) & 1) << a.item_bit[j];
+    item_off[it] = o;
+  }
+  double acc[ITEMS];
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) acc[it] = 0.0;
+  if (base < a.n) {
+    u64 t = 0;                                      // the loop bits' values in ascending order (subset enumeration)
+    do {
+      double2 x[ITEMS];
+#pragma unroll
+      for (int it = 0; it < ITEMS; ++it) x[it] = ld_amp<NT>(a.amp + (base | item_off[it] | t));
+      __builtin_amdgcn_sched_barrier(0);            // every load of the step in flight before the first use (hipcc interleaves
+                                                    // them with the sums otherwise: two 16-B loads in flight per lane)
+#pragma unroll
+      for (int it = 0; it < ITEMS; ++it) acc[it] = fma(x[it].x, x[it].x, fma(x[it].y, x[it].y, acc[it]));
+      t = ((t | ~a.loop_mask) + 1) & a.loop_mask;
+    } while (t);
+  }
+  __syncthreads();                                  // (the histogram rows are zeroed)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) {
+    double v = acc[it];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+      if (!(a.lane_sel & off)) v += __shfl_xor(v, off, 64);
+    if ((lane & ~a.lane_sel) == 0) {
+      const u64 i0 = base | item_off[it];
+      int m = 0;
+      for (int j = 0; j < a.r; ++j) m |= (int)((i0 >> a.q[j]) & 1) << j;
+      hist[wave * nbins + m] += v;
+    }
+  }
+  __syncthreads();
+  for (int m = threadIdx.x; m < nbins; m += kBlock) {
+    double s = hist[m];
+    for (int w = 1; w < kBlock / 64; ++w) s += hist[w * nbins + m];
+    a.partial[wg * (u64)nbins + m] = s;
+  }
+}
+
+// bin blockIdx.x of the partial histograms of n_wg workgroups: strided per thread, then the block reduction (fixed order)
+__global__ __launch_bounds__(kBlock) void k_hist_sum(const double* partial, int n_wg, int nbins, double* out) {
+  double v = 0.0;
+  for (int w = threadIdx.x; w < n_wg; w += kBlock) v += partial[(u64)w * nbins + blockIdx.x];
+  block_reduce_store<false>(v, out);
+}
+
 // ---- complex64 <-> complex128 on the device: the reference's chunk files are complex64 (storage/block_store.py:11),
 // so an export rounds on the GPU and moves 8 B per amplitude over PCIe instead of 16 (round to nearest even, what
 // numpy's astype(complex64) does)
@@ -639,6 +724,16 @@ static int ensure_scratch(qsim_chunk* c) {
   if (!c->scratch) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMalloc((void**)&c->scratch, sizeof(double) * kScratchDoubles));
+  }
+  return QSIM_OK;
+}
+
+constexpr int kHistWgBits = 11;            // qsim_probabilities: at most 2^11 workgroups (8 per CU)
+constexpr u64 kHistDoubles = (256ull << kHistWgBits) + 256;   // partial histograms + the summed one
+static int ensure_hist(qsim_chunk* c) {
+  if (!c->hist) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMalloc((void**)&c->hist, sizeof(double) * kHistDoubles));
   }
   return QSIM_OK;
 }

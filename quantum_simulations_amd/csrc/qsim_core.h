@@ -32,6 +32,7 @@ struct qsim_chunk {
   hipEvent_t ev0, ev1;   // timing
   bool have_events;
   double* scratch;       // reduction workspace (lazily allocated, owned)
+  double* hist;          // qsim_probabilities: partial histograms (lazily allocated, owned)
   int last_passes;       // HBM passes of the last qsim_apply_ops
   u64 span_bytes;        // size of the allocation the chunk lives in (cache-policy choice)
   struct PendingLast* pending;   // split form of qsim_apply_ops_io: the slab-storing pass, planned but not yet launched (owned)

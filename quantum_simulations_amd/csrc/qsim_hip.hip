@@ -157,6 +157,7 @@ int qsim_destroy(qsim_chunk* c) {
   (void)hipSetDevice(c->device);
   if (c->have_events) { (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1); }
   if (c->scratch) (void)hipFree(c->scratch);
+  if (c->hist) (void)hipFree(c->hist);
   delete c->pending;
   delete c->deferred;
   if (c->owns_memory && c->amp) {
@@ -195,6 +196,76 @@ int qsim_norm2(qsim_chunk* c, double* out) {
   long double total = 0;
   for (double v : host) total += v;
   *out = (double)total;
+  return QSIM_OK;
+}
+
+// Joint outcome probabilities of r measured qubits: k_hist (one read-only pass, partial histograms per workgroup) and
+// k_hist_sum (the partials in workgroup order); 2^r doubles cross to the host.  Bits of the chunk index are dealt out as
+// described at k_hist: 0..7 threads, then item bits, workgroup bits and loop bits, selected qubits first.
+int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out) {
+  int rc = check_chunk(c, "qsim_probabilities");
+  if (rc) return rc;
+  if (!qubits || !out) return fail(QSIM_ERR_INVALID, "qsim_probabilities: null argument");
+  if (r < 1 || r > 8) return fail(QSIM_ERR_INVALID, "qsim_probabilities: 1 <= r <= 8 qubits expected, got %d", r);
+  if (parts_pending(c)) return fail(QSIM_ERR_INVALID, "qsim_probabilities: slab pieces of a split qsim_apply_ops_io call are pending on this chunk");
+  u64 sel = 0;
+  for (int i = 0; i < r; ++i) {
+    if ((rc = check_local_qubit(c, qubits[i]))) return rc;
+    for (int j = 0; j < i; ++j) if (qubits[j] == qubits[i]) return fail(QSIM_ERR_INVALID, "qsim_probabilities: repeated qubit %d", qubits[i]);
+    sel |= 1ull << qubits[i];
+  }
+  if ((rc = ensure_hist(c))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const int k = c->k;
+  const int above = std::max(0, k - 8);
+  const int n_item = std::min(3, above);
+  const int n_wg = std::min(kHistWgBits, above - n_item);
+  HistArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.amp = c->amp;
+  a.n = amps(c);
+  a.r = r;
+  for (int i = 0; i < r; ++i) a.q[i] = qubits[i];
+  a.lane_sel = (int)(sel & 63);
+  // selected bits above the thread bits first (item bits, then workgroup bits), then the free bits: the lowest ones as
+  // item bits (a thread's loads stay close), the highest as workgroup bits (each XCD's workgroups cover one region)
+  std::vector<int> hi_sel, free_bits;
+  for (int b = 8; b < k; ++b) ((sel >> b) & 1 ? hi_sel : free_bits).push_back(b);
+  size_t si = 0, lo = 0, hi = free_bits.size();
+  u64 used = 0;
+  for (int j = 0; j < n_item; ++j) { const int b = si < hi_sel.size() ? hi_sel[si++] : free_bits[lo++]; a.item_bit[j] = b; used |= 1ull << b; }
+  std::vector<int> wg;
+  for (int j = 0; j < n_wg; ++j) { const int b = si < hi_sel.size() ? hi_sel[si++] : free_bits[--hi]; wg.push_back(b); used |= 1ull << b; }
+  if (si != hi_sel.size() || lo > hi) return fail(QSIM_ERR_INVALID, "internal: qsim_probabilities could not place the selected bits");
+  std::sort(wg.begin(), wg.end());
+  for (int j = 0; j < n_wg; ++j) a.wg_bit[j] = wg[(size_t)j];
+  a.n_wg_bits = n_wg;
+  const u64 all_hi = k > 8 ? (((1ull << k) - 1) & ~255ull) : 0;
+  a.loop_mask = all_hi & ~used;
+  a.partial = c->hist;
+  const int nbins = 1 << r;
+  const unsigned grid = 1u << n_wg;
+  double* dev_out = c->hist + ((u64)grid << 8);
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  {
+    ProfileScope prof(8, 16.0 * (double)amps(c), c->stream, nt);
+#define QSIM_HIST_LAUNCH(IB)                                                                                     \
+    if (nt) hipLaunchKernelGGL((k_hist<IB, true>), dim3(grid), dim3(kBlock), 0, c->stream, a);                    \
+    else hipLaunchKernelGGL((k_hist<IB, false>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+    switch (n_item) {
+      case 0: QSIM_HIST_LAUNCH(0) break;
+      case 1: QSIM_HIST_LAUNCH(1) break;
+      case 2: QSIM_HIST_LAUNCH(2) break;
+      default: QSIM_HIST_LAUNCH(3) break;
+    }
+#undef QSIM_HIST_LAUNCH
+    HIP_TRY(hipGetLastError());
+    prof.done(c->stream);
+  }
+  hipLaunchKernelGGL(k_hist_sum, dim3(nbins), dim3(kBlock), 0, c->stream, (const double*)c->hist, (int)grid, nbins, dev_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, dev_out, sizeof(double) * nbins, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return QSIM_OK;
 }
 

@@ -277,6 +277,18 @@ class DeviceChunk:
         _lib.check(_lib.load().qsim_norm2(self._h, C.byref(out)))
         return out.value
 
+    def probabilities(self, qubits) -> np.ndarray:
+        """Joint outcome probabilities of `qubits` (1 to 8 of them, any order), unnormalised: entry m = sum of |amp|^2
+        over the amplitudes whose bit qubits[j] equals bit j of m (qsim_probabilities: one read-only pass on the device,
+        a fixed summation order -- two calls give the same bits)."""
+        q = np.ascontiguousarray(qubits, dtype=np.int32).reshape(-1)
+        if not 1 <= len(q) <= 8:
+            raise ValueError(f"probabilities: 1 to 8 qubits expected, got {len(q)}")
+        out = np.empty(1 << len(q), dtype=np.float64)
+        _lib.check(_lib.load().qsim_probabilities(self._h, len(q), q.ctypes.data_as(C.c_void_p),
+                                                  out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def max_abs_err_closed_form(self, kind: str, n_total: int, base_index: int = 0,
                                 log_to_phys=None) -> float:
         """max |amp - closed form| over this chunk; `log_to_phys` maps a staged layout back."""
