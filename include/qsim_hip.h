@@ -343,6 +343,25 @@ int qsim_norm2(qsim_chunk* c, double* out);               /* sum |amp|^2        
  * workgroup order on the device, no atomics); only the 2^r doubles cross to the host.  Qubits >= log2(chunk) fail with
  * QSIM_ERR_NONLOCAL.  Dynamic circuits (mid-circuit measurement, reset) sample their outcomes from it. */
 int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out);
+/* Expectation values of Pauli strings, unnormalised: out[t] = <psi|P_t|psi> for t < n_terms.  P_t is two masks of
+ * physical local index bits: x_masks[t] = the bits that carry X or Y, z_masks[t] = the bits that carry Z or Y; with
+ * ny = popcount(x & z) (Y = i X Z), P|i> = i^ny (-1)^popcount(i & z) |i ^ x> and
+ *   <psi|P|psi> = sum_i (-1)^popcount(i & z) Re(i^ny conj(psi_{i ^ x}) psi_i)   (real for every string).
+ * Coefficients and the division by the norm are the caller's.  Read-only passes over the chunk: the terms are grouped
+ * by qsim_plan_expectation; a tile pass evaluates up to 1024 terms whose x lies in its <= 11 tile bits from LDS, a
+ * wide-X pass one term whose x does not fit a tile.  Per-workgroup partials are summed in workgroup order on the device
+ * (no atomics): two calls give the same bits.  Only the n_terms doubles cross to the host; blocks until out is written.
+ * *n_passes = the passes that ran (= qsim_plan_expectation's).  A bit >= log2(chunk) fails with QSIM_ERR_NONLOCAL. */
+int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, const uint64_t* z_masks, double* out,
+                           int* n_passes);
+/* The pass plan of qsim_expectation_pauli (pure function, no GPU).  pass_of_term[t] = the pass that evaluates term t;
+ * tile_masks[p] = the tile bits of pass p (they contain the line bits 0..2 and the x of each of its terms), 0 for a
+ * wide-X pass (one per term whose x and the line bits exceed 11 bits; they come after the tile passes).  tile_masks
+ * needs room for n_terms entries (every pass holds a term).  Deterministic: terms with x != 0 go, in order, into the
+ * first pass with room (< 1024 terms) whose tile stays within 11 bits, terms with x = 0 fill the tile passes in order.
+ * A bit >= n_local_qubits in x fails with QSIM_ERR_NONLOCAL. */
+int qsim_plan_expectation(int n_local_qubits, int n_terms, const uint64_t* x_masks, int32_t* pass_of_term,
+                          uint64_t* tile_masks, int* n_passes);
 /* max_i |amp_i - expected_i| for closed-form states, evaluated on the device:
  * kind 0: GHZ (1/sqrt2 at local index 0 of the first chunk and at the last index of the
  *         last), kind 1: GHZ+QFT  2^-(n+1)/2 (1 + exp(-2 pi i y / 2^n)), y = base + i.  */

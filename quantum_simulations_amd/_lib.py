@@ -107,6 +107,8 @@ SIGNATURES = {
     "qsim_sync": (C.c_int, [_P]),
     "qsim_norm2": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "qsim_probabilities": (C.c_int, [_P, C.c_int, _P, _P]),
+    "qsim_expectation_pauli": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
+    "qsim_plan_expectation": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_max_abs_err_closed_form": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint64,
                                                C.POINTER(C.c_double)]),
     "qsim_max_abs_err_closed_form_perm": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint64, _P,

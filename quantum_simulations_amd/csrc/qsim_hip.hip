@@ -48,6 +48,7 @@ typedef unsigned long long u64;
 #include "tile_kernel.h"
 #include "tile_planner.h"
 #include "misc_kernels.h"
+#include "expect_kernels.h"
 #include "comm_rccl.h"
 
 // An op list whose SOURCE arrives in pieces (qsim_ops_io::src_parts: the receive side of a fused re-layout): planned and
@@ -158,6 +159,7 @@ int qsim_destroy(qsim_chunk* c) {
   if (c->have_events) { (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1); }
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->hist) (void)hipFree(c->hist);
+  if (c->expect) (void)hipFree(c->expect);
   delete c->pending;
   delete c->deferred;
   if (c->owns_memory && c->amp) {
@@ -266,6 +268,144 @@ int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out)
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, dev_out, sizeof(double) * nbins, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return QSIM_OK;
+}
+
+// Pauli-sum expectation values (expect_kernels.h): the pass plan on the host, then per pass k_expect_tile (or
+// k_expect_wide) and k_hist_sum (the workgroup rows in workgroup order) into a device array of per-term results, in
+// pass order; one copy of n_terms doubles to the host at the end.
+int qsim_plan_expectation(int n_local_qubits, int n_terms, const uint64_t* x_masks, int32_t* pass_of_term,
+                          uint64_t* tile_masks, int* n_passes) {
+  if (!n_passes || (n_terms > 0 && (!pass_of_term || !tile_masks)))
+    return fail(QSIM_ERR_INVALID, "qsim_plan_expectation: null argument");
+  ExpPlan p;
+  const int rc = plan_expectation(n_local_qubits, n_terms, x_masks, &p);
+  if (rc) return rc;
+  for (int t = 0; t < n_terms; ++t) pass_of_term[t] = p.pass_of[(size_t)t];
+  for (size_t q = 0; q < p.tile.size(); ++q) tile_masks[q] = p.tile[q];
+  *n_passes = (int)p.tile.size();
+  return QSIM_OK;
+}
+
+static int ensure_expect(qsim_chunk* c, u64 bytes) {
+  if (c->expect_bytes >= bytes) return QSIM_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->expect) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipFree(c->expect));
+    c->expect = nullptr;
+    c->expect_bytes = 0;
+  }
+  HIP_TRY(hipMalloc(&c->expect, bytes));
+  c->expect_bytes = bytes;
+  return QSIM_OK;
+}
+
+int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, const uint64_t* z_masks, double* out,
+                           int* n_passes) {
+  int rc = check_chunk(c, "qsim_expectation_pauli");
+  if (rc) return rc;
+  if (n_terms < 0) return fail(QSIM_ERR_INVALID, "qsim_expectation_pauli: n_terms = %d", n_terms);
+  if (!n_passes || (n_terms > 0 && (!x_masks || !z_masks || !out)))
+    return fail(QSIM_ERR_INVALID, "qsim_expectation_pauli: null argument");
+  if (parts_pending(c)) return fail(QSIM_ERR_INVALID, "qsim_expectation_pauli: slab pieces of a split qsim_apply_ops_io call are pending on this chunk");
+  const int k = c->k;
+  const u64 all = (1ull << k) - 1;
+  for (int t = 0; t < n_terms; ++t)
+    if ((x_masks[t] | z_masks[t]) & ~all)
+      return fail(QSIM_ERR_NONLOCAL, "qsim_expectation_pauli: term %d acts on index bit %d >= log2(chunk_size)=%d", t,
+                  63 - __builtin_clzll((x_masks[t] | z_masks[t]) & ~all), k);
+  ExpPlan p;
+  if ((rc = plan_expectation(k, n_terms, x_masks, &p))) return rc;
+  *n_passes = 0;
+  if (n_terms == 0) return QSIM_OK;
+  const int np = (int)p.tile.size();
+  // term tables of the tile passes (in pass order) and the result slot of every term
+  std::vector<int> first(np + 1, 0);
+  for (int q = 0; q < np; ++q) first[q + 1] = first[q] + p.count[q];
+  std::vector<int> fill(first.begin(), first.end() - 1), order((size_t)n_terms);
+  for (int t = 0; t < n_terms; ++t) order[(size_t)t] = fill[(size_t)p.pass_of[(size_t)t]]++;   // result slot of term t
+  std::vector<ExpTerm> table((size_t)n_terms);
+  std::memset(table.data(), 0, sizeof(ExpTerm) * table.size());
+  std::vector<int> wide_term((size_t)np, -1);       // the term of a wide-X pass
+  for (int t = 0; t < n_terms; ++t) {
+    const u64 T = p.tile[(size_t)p.pass_of[(size_t)t]];
+    const u64 x = x_masks[t], z = z_masks[t];
+    ExpTerm& e = table[(size_t)order[(size_t)t]];
+    exp_phase(x, z, &e.cr, &e.ci);
+    if (!T && x) {                                  // wide-X: the masks go as launch arguments
+      wide_term[(size_t)p.pass_of[(size_t)t]] = t;
+      continue;
+    }
+    e.xi = (unsigned)exp_pext(x, T);
+    e.zi = (unsigned)exp_pext(z & T, T);
+    e.zo = z & ~T;
+    e.h = e.xi ? 31 - __builtin_clz(e.xi) : -1;
+  }
+  const u64 n_tiles_max = 1ull << (k - std::min(k, kExpTileBits));
+  const unsigned grid_tile = (unsigned)std::min<u64>(n_tiles_max, kExpMaxWg);
+  int max_count = 1;
+  for (int q = 0; q < np; ++q) max_count = std::max(max_count, p.count[q]);
+  const u64 partial_bytes = sizeof(double) * (u64)kExpMaxWg * (u64)max_count;
+  const u64 table_off = partial_bytes, out_off = table_off + sizeof(ExpTerm) * (u64)n_terms;
+  if ((rc = ensure_expect(c, out_off + sizeof(double) * (u64)n_terms))) return rc;
+  char* base = static_cast<char*>(c->expect);
+  double* partial = reinterpret_cast<double*>(base);
+  ExpTerm* dev_table = reinterpret_cast<ExpTerm*>(base + table_off);
+  double* dev_out = reinterpret_cast<double*>(base + out_off);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(dev_table, table.data(), sizeof(ExpTerm) * table.size(), hipMemcpyHostToDevice, c->stream));
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  for (int q = 0; q < np; ++q) {
+    const u64 T = p.tile[(size_t)q];
+    if (wide_term[(size_t)q] >= 0) {
+      const int t = wide_term[(size_t)q];
+      ExpWideArgs w;
+      std::memset(&w, 0, sizeof w);
+      w.amp = c->amp;
+      w.partial = partial;
+      w.half = amps(c) >> 1;
+      w.x = x_masks[t];
+      w.z = z_masks[t];
+      w.h = 63 - __builtin_clzll(w.x);
+      w.cr = table[(size_t)first[q]].cr;
+      w.ci = table[(size_t)first[q]].ci;
+      const unsigned grid = (unsigned)std::min<u64>(std::max<u64>(w.half / kBlock, 1), kExpMaxWg);
+      if (nt) hipLaunchKernelGGL((k_expect_wide<true>), dim3(grid), dim3(kBlock), 0, c->stream, w);
+      else hipLaunchKernelGGL((k_expect_wide<false>), dim3(grid), dim3(kBlock), 0, c->stream, w);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_hist_sum, dim3(1), dim3(kBlock), 0, c->stream, (const double*)partial, (int)grid, 1,
+                         dev_out + first[q]);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
+    ExpArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.amp = c->amp;
+    a.terms = dev_table + first[q];
+    a.partial = partial;
+    a.tb = __builtin_popcountll(T);
+    for (int b = 0, j = 0; b < k; ++b)
+      if ((T >> b) & 1) a.tile_bit[j++] = b;
+    a.outer_mask = all & ~T;
+    a.n_tiles = 1ull << (k - a.tb);
+    a.n_terms = p.count[q];
+    int slices = 1;
+    while (slices * 2 * a.n_terms <= kBlock) slices *= 2;
+    a.slices = slices;
+    const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, grid_tile);
+    if (nt) hipLaunchKernelGGL((k_expect_tile<true>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_expect_tile<false>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_hist_sum, dim3(a.n_terms), dim3(kBlock), 0, c->stream, (const double*)partial, (int)grid,
+                       a.n_terms, dev_out + first[q]);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<double> res((size_t)n_terms);
+  HIP_TRY(hipMemcpyAsync(res.data(), dev_out, sizeof(double) * (u64)n_terms, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int t = 0; t < n_terms; ++t) out[t] = res[(size_t)order[(size_t)t]];
+  *n_passes = np;
   return QSIM_OK;
 }
 

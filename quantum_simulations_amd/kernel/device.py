@@ -289,6 +289,30 @@ class DeviceChunk:
                                                   out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def expectation_pauli(self, x_masks, z_masks) -> np.ndarray:
+        """<psi|P_t|psi> of Pauli strings given as masks of PHYSICAL index bits of this chunk (x: X or Y, z: Z or Y),
+        unnormalised (qsim_expectation_pauli: read-only passes on the device, a fixed summation order -- two calls give
+        the same bits).  `self.last_expectation_passes` = the passes that ran."""
+        x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
+        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
+        if x.shape != z.shape:
+            raise ValueError(f"expectation_pauli: {x.size} x masks, {z.size} z masks")
+        out = np.empty(x.size, dtype=np.float64)
+        passes = C.c_int(0)
+        _lib.check(_lib.load().qsim_expectation_pauli(self._h, int(x.size), x.ctypes.data_as(C.c_void_p),
+                                                      z.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                                                      C.byref(passes)))
+        self.last_expectation_passes = passes.value
+        return out
+
+    def expectation(self, obs, l2p=None) -> float:
+        """sum_t c_t <psi|P_t|psi> (unnormalised) of a PauliSum (or what PauliSum accepts) whose logical qubit q lives
+        on index bit l2p[q] of this chunk (None: identity)."""
+        from quantum_simulations_amd.observable import as_pauli_sum
+        obs = as_pauli_sum(obs, self.k if l2p is None else len(l2p))
+        x, z = obs.masks(l2p)
+        return obs.value(self.expectation_pauli(x, z))
+
     def max_abs_err_closed_form(self, kind: str, n_total: int, base_index: int = 0,
                                 log_to_phys=None) -> float:
         """max |amp - closed form| over this chunk; `log_to_phys` maps a staged layout back."""
@@ -367,6 +391,18 @@ def split_piece_count(k: int, m: int, parts: int) -> int:
     """Pieces the split form of `apply_ops_io` cuts every slab into (qsim_split_piece_count: a pure function of the chunk
     size, the slab bits' count and the pieces asked for -- no device needed)."""
     return int(_lib.load().qsim_split_piece_count(int(k), int(m), int(parts)))
+
+
+def plan_expectation(k: int, x_masks) -> tuple[np.ndarray, np.ndarray]:
+    """qsim_plan_expectation (host only): (pass of every term, tile-bit mask of every pass; 0 = wide-X pass)."""
+    x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
+    pass_of = np.empty(x.size, dtype=np.int32)
+    tiles = np.empty(max(x.size, 1), dtype=np.uint64)
+    n = C.c_int(0)
+    _lib.check(_lib.load().qsim_plan_expectation(int(k), int(x.size), x.ctypes.data_as(C.c_void_p),
+                                                 pass_of.ctypes.data_as(C.c_void_p), tiles.ctypes.data_as(C.c_void_p),
+                                                 C.byref(n)))
+    return pass_of, tiles[: n.value].copy()
 
 
 def device_count() -> int:

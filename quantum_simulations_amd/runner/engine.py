@@ -86,6 +86,11 @@ class SingleGpuEngine:
         from quantum_simulations_amd.circuit.staging import permute_state
         return permute_state(psi, self.l2p)
 
+    def expectation(self, obs) -> float:
+        """<psi|H|psi> (unnormalised) of a Pauli sum over LOGICAL qubits (observable.PauliSum or what it accepts),
+        evaluated on the device through the current layout; the state does not move."""
+        return self.state.expectation(obs, l2p=self.l2p if self.l2p is not None else list(range(self.n)))
+
     def logical_index(self, offset: int, count: int) -> np.ndarray:
         """Logical amplitude indices of the physical range [offset, offset + count) of the state in its current layout."""
         x = offset + np.arange(count, dtype=np.int64)

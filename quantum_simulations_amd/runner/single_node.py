@@ -303,6 +303,13 @@ def _apply_nonlocal(data: dict, qs: list[int], U: np.ndarray, k: int) -> None:
                                        data[cb | (1 << pa) | (1 << pb)], U)
 
 
+def expectation(buf: HbmStateBuffer, obs) -> float:
+    """<psi|H|psi> (unnormalised) of a Pauli sum over LOGICAL qubits on the final state of `run`, evaluated on the
+    device through the staging layout `buf.log_to_phys` (nothing is downloaded or permuted)."""
+    l2p = getattr(buf, "log_to_phys", None) or list(range(buf.n_qubits))
+    return buf.state.expectation(obs, l2p=l2p)
+
+
 def collect_state(buf: HbmStateBuffer, apply_permutation: bool = False,
                   work_dir: str | Path | None = None) -> np.ndarray:
     """All chunks back as one complex128 vector; with `apply_permutation` and a
