@@ -18,7 +18,8 @@ from __future__ import annotations
 import json
 
 from quantum_simulations_amd import circuits as gen
-from quantum_simulations_amd.runner.distributed import DistributedEngine, PlanningBackend
+from quantum_simulations_amd.runner.distributed import DistributedEngine
+from quantum_simulations_amd.runner.shard_backends import PlanningBackend
 
 
 def workloads(n: int) -> list:

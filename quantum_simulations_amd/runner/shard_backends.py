@@ -1,0 +1,320 @@
+"""Shard backends of the multi-GPU engine (runner/distributed.py): what touches amplitudes (`HipShardBackend`) or stands in
+for it (`DryBackend`: the schedule alone; `PlanningBackend`: and the HBM passes the library would make).  The engine
+addresses buffers by role ("state", "buf0", "buf1"); the CPU test double (tests/cpu_shard_backend.py) has the same methods.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+class HipShardBackend:
+    """Shard + exchange buffers as torch CUDA tensors, arithmetic through libqsim_hip.so."""
+
+    def __init__(self, k: int, device: int):
+        import torch
+
+        from quantum_simulations_amd.kernel.device import DeviceChunk
+        self.torch, self.k, self.device = torch, k, device
+        torch.cuda.set_device(device)
+        self._DeviceChunk = DeviceChunk
+        self._tensors: dict[str, object] = {}
+        self._chunks: dict[str, object] = {}
+        self.tensor("state")
+
+    def tensor(self, name: str):
+        if name not in self._tensors:
+            t = self.torch.empty(2 << self.k, dtype=self.torch.float64, device=f"cuda:{self.device}")
+            stream = self.torch.cuda.current_stream(self.device).cuda_stream
+            self._tensors[name] = t
+            self._chunks[name] = self._DeviceChunk.wrap_pointer(t.data_ptr(), self.k, self.device,
+                                                                stream=stream, keep=t)
+        return self._tensors[name]
+
+    def chunk(self, name: str):
+        self.tensor(name)
+        return self._chunks[name]
+
+    # ---- state ---------------------------------------------------------------------
+    def init_zero(self, set_amp0: bool) -> None:
+        self.chunk("state").init_zero(set_amp0)
+
+    def norm2(self) -> float:
+        return self.chunk("state").norm2()
+
+    def download(self, offset: int = 0, count: int | None = None) -> np.ndarray:
+        return self.chunk("state").download(offset, count)
+
+    def sync(self) -> None:
+        self.torch.cuda.synchronize(self.device)
+
+    # ---- arithmetic -----------------------------------------------------------------
+    def apply_ops(self, ops, src=None, dst=None, parts: int = 0, src_parts: int = 0, tiles=None) -> int:
+        """HBM passes made.  src = (buffer, bits): the shard is read from that buffer in slab layout; dst = (buffer,
+        bits, own_buffer, own_pattern): it is left there in slab layout (qsim_apply_ops_io: the re-layout's pack /
+        unpack ride in the last / first fused pass).  parts (with dst): split form -- the slabs are stored piece by piece
+        by `store_part(j)` for every piece of `pending_parts()`.  src_parts (with src): the source is still arriving in
+        pieces: nothing runs until `load_part(j)` announces them, the first pass piece by piece.  tiles: the high tile bits
+        of the first passes as the partition planner chose them (uint64 masks)."""
+        st = self.chunk("state")
+        if src is None and dst is None:
+            if tiles is not None and len(tiles) and len(ops) >= 2:
+                return st.apply_ops_tiled(ops, tiles)
+            return st.apply_ops(ops)
+        return st.apply_ops_io(ops, src=(self.chunk(src[0]), src[1]) if src else None,
+                               dst=(self.chunk(dst[0]), dst[1], self.chunk(dst[2]), dst[3]) if dst else None, parts=parts,
+                               src_parts=src_parts, tiles=tiles)
+
+    def own_slab_in_state(self) -> bool:
+        """The last `apply_ops` with a `dst` whose own-slab buffer was the source buffer left that slab in "state" (one
+        pass read the source and stored the slabs: qsim_apply_ops_io_own_slab)."""
+        return self.chunk("state").own_slab_in_chunk()
+
+    def swap_names(self, a: str, b: str) -> None:
+        """Buffers `a` and `b` trade names (the shard's home moves: the engine addresses buffers by role)."""
+        self.tensor(a), self.tensor(b)
+        self._tensors[a], self._tensors[b] = self._tensors[b], self._tensors[a]
+        self._chunks[a], self._chunks[b] = self._chunks[b], self._chunks[a]
+
+    def load_part(self, j: int) -> None:
+        self.chunk("state").load_part(j)
+
+    def pending_parts(self) -> list:
+        return self.chunk("state").pending_parts()
+
+    def store_part(self, j: int) -> None:
+        self.chunk("state").store_part(j)
+
+    # ---- exchange through the library's own communicator (DistributedEngine(exchange="cabi")) -----------------
+    def comm_init(self, dist, rank: int, world: int) -> None:
+        """qsim_comm over RCCL: rank 0 makes the unique id, the existing process group hands the 128 bytes around."""
+        from quantum_simulations_amd.kernel.device import Comm
+        box = [Comm.unique_id() if rank == 0 else None]
+        dist.broadcast_object_list(box, src=0)
+        self.comm = Comm(self.device, rank, world, box[0])
+
+    def exchange_bg(self, send: str, recv: str, entries) -> None:
+        """entries [(peer, offset_amps, count_amps)] (one count): one RCCL group on the communicator's transfer stream,
+        behind everything queued on the shard's stream so far; later work on that stream does not wait for it."""
+        peers = [e[0] for e in entries]
+        offs = [e[1] for e in entries]
+        return self.comm.exchange_bg(peers, self.chunk(send), offs, self.chunk(recv), offs, entries[0][2])
+
+    def exchange_wait(self, ticket: int) -> None:
+        self.comm.wait(self.chunk("state"), ticket)
+
+    def pack_all(self, bits, dst: str, skip_pattern: int, piece: int = 0, n_pieces: int = 1) -> None:
+        self.chunk("state").pack_all(bits, self.chunk(dst), skip_pattern, piece, n_pieces)
+
+    def unpack_all(self, bits, src: str, skip_pattern: int, piece: int = 0, n_pieces: int = 1) -> None:
+        self.chunk("state").unpack_all(bits, self.chunk(src), skip_pattern, piece, n_pieces)
+
+    def expectation_pauli(self, x_masks, z_masks) -> np.ndarray:
+        """<shard|P_t|shard> of Pauli strings on LOCAL index bits (unnormalised, qsim_expectation_pauli)."""
+        return self.chunk("state").expectation_pauli(x_masks, z_masks)
+
+    def closed_form_error(self, kind: str, n_total: int, base_index: int, log_to_phys) -> float:
+        return self.chunk("state").max_abs_err_closed_form(kind, n_total, base_index, log_to_phys)
+
+    def fingerprint(self, n_total: int, base_index: int, log_to_phys, seed: int, sel_mask: int = 0, sel_value: int = 0) -> complex:
+        return self.chunk("state").fingerprint(n_total, base_index, log_to_phys, seed, sel_mask, sel_value)
+
+    def release_buffers(self) -> None:
+        """Give the exchange buffers back to the device (they are re-created on demand): room for a one-GPU reference
+        run of the whole state next to the shard."""
+        self.sync()
+        for name in [n for n in self._tensors if n != "state"]:
+            self._chunks.pop(name).close()
+            del self._tensors[name]
+        self.torch.cuda.empty_cache()
+
+    def profile_begin(self) -> None:
+        self.chunk("state").profile_begin()
+
+    def profile_end(self):
+        return self.chunk("state").profile_end()
+
+    def close(self) -> None:
+        self.sync()
+        if getattr(self, "comm", None) is not None:
+            self.comm.close()
+            self.comm = None
+        for c in self._chunks.values():
+            c.close()
+        self._chunks.clear()
+        self._tensors.clear()
+
+
+def split_pieces(k: int, m: int, parts: int) -> list:
+    """[(offset, amplitudes)] of the pieces the split form of qsim_apply_ops_io cuts every slab into -- the library's rule
+    (qsim_split_piece_count: as many as asked for while a piece keeps >= 2^20 amplitudes; negative `parts`: no floor)
+    restated for backends without the library (dry runs, the CPU test double; tests compare the two)."""
+    want, floor = abs(parts), (20 if parts > 0 else 3)
+    nb = 0
+    while nb < 3 and (2 << nb) <= want and (k - m) - (nb + 1) >= floor:
+        nb += 1
+    piece = (1 << (k - m)) >> nb
+    return [(j * piece, piece) for j in range(1 << nb)]
+
+
+class _FakeTensor:
+    """Stand-in for a shard / exchange buffer in dry runs: knows its length, checks slice bounds."""
+    is_cuda = False
+
+    def __init__(self, n: int):
+        self.n = n
+
+    def __getitem__(self, sl):
+        start, stop, step = sl.indices(self.n) if isinstance(sl, slice) else (sl, sl + 1, 1)
+        if not isinstance(sl, slice) or step != 1 or (sl.start or 0) < 0 or (sl.stop is not None and sl.stop > self.n) or stop < start:
+            raise IndexError(f"slice {sl} outside a buffer of {self.n} elements")
+        return _FakeTensor(stop - start)
+
+    def numel(self) -> int:
+        return self.n
+
+    @staticmethod
+    def element_size() -> int:
+        return 8
+
+
+class DryBackend:
+    """No memory, no arithmetic: lets the engine run its communication schedule at full problem sizes
+    (bench.py --dry-run, tests); every transfer is recorded in DistributedEngine.trace instead of posted."""
+    dry = True
+
+    def __init__(self, k: int):
+        self.k = k
+        self.local_passes = 0
+
+    def tensor(self, name: str):
+        return _FakeTensor(2 << self.k)
+
+    def init_zero(self, set_amp0: bool) -> None:
+        pass
+
+    def sync(self) -> None:
+        pass
+
+    def apply_ops(self, ops, src=None, dst=None, parts: int = 0, src_parts: int = 0, tiles=None) -> int:
+        self._io_ends(src, dst, parts, src_parts)
+        self.local_passes += 1
+        # (a dry run knows no pass counts: it takes the one-pass branch -- own slab into "state", buffers trade names --
+        # whenever the engine offers it, which exercises the role bookkeeping; the transfers are the same either way)
+        self._own_in_state = src is not None and dst is not None and dst[2] == src[0]
+        return 1
+
+    def _io_ends(self, src, dst, parts: int, src_parts: int) -> None:
+        """The fused re-layout ends of an `apply_ops`: slab bits checked, the pieces `load_part` / `store_part` will name."""
+        self._loads = len(split_pieces(self.k, len(src[1]), src_parts)) if (src is not None and src_parts) else 0
+        for side in (src, dst):
+            if side is not None:
+                self._check(side[1], 0, 1)
+        if dst is not None and parts:
+            self._parts = split_pieces(self.k, len(dst[1]), parts)
+
+    def own_slab_in_state(self) -> bool:
+        return self._own_in_state
+
+    def swap_names(self, a: str, b: str) -> None:
+        pass
+
+    def pending_parts(self) -> list:
+        return self._parts
+
+    def store_part(self, j: int) -> None:
+        if not 0 <= j < len(self._parts):
+            raise ValueError("bad part")
+
+    def load_part(self, j: int) -> None:
+        if not 0 <= j < self._loads:
+            raise ValueError("bad source piece")
+
+    def pack_all(self, bits, buf, skip_pattern, piece=0, n_pieces=1) -> None:
+        self._check(bits, piece, n_pieces)
+
+    unpack_all = pack_all                # (without memory a pack and an unpack are the same check)
+
+    def _check(self, bits, piece, n_pieces) -> None:
+        if not 1 <= len(bits) <= 3 or len(set(bits)) != len(bits) or any(not 0 <= b < self.k for b in bits):
+            raise ValueError(f"re-layout bits {bits} invalid for {self.k} local qubits")
+        if n_pieces not in (1, 2, 4, 8) or not 0 <= piece < n_pieces:
+            raise ValueError("bad piece")
+
+    def close(self) -> None:
+        pass
+
+
+class PlanningBackend(DryBackend):
+    """A dry backend that knows what the library WOULD do with every op list: the HBM passes of `qsim_apply_ops_io` (the host
+    planner `qsim_plan_ops` on exactly the ops a rank runs, plus the pack / unpack passes of ends that cannot ride in a tile
+    pass: slab bits inside a 128-byte line, a slab bit among the tile bits of the last pass, nothing to plan) and, from 26
+    local qubits on, each pass weighted by the tile-cost model's prediction for its tile's index bits (runner/tile_layout.py,
+    in units of the model's average pass).  `DistributedEngine.choose_initial_layout` executes candidate schedules on it."""
+
+    def __init__(self, k: int):
+        super().__init__(k)
+        from quantum_simulations_amd.runner import tile_layout
+        self._tile_layout = tile_layout
+        self.model = tile_layout.model_for(k) if k >= 26 else None
+        self.model_ref = 1.0
+        if self.model is not None:
+            rng = np.random.default_rng(7)
+            top = min(k - 1, self.model["top"])
+            self.model_ref = float(np.mean([tile_layout.tile_cost(self.model, rng.choice(np.arange(3, top + 1), size=8, replace=False))
+                                            for _ in range(256)]))
+        self._images = np.zeros((64, 4096), dtype=np.uint8)
+        self.weight = 0.0                # model-weighted passes since the last reset
+        self.passes = 0
+        self.record: list | None = None  # (tools/shard_compute_probe.py: (op list, named tiles) as the rank would run them)
+
+    def _plan(self, ops, tiles=None) -> tuple:
+        """(passes, their model weight, tile bits of the last pass) of the fused plan of `ops` (tile passes possible)"""
+        import ctypes as C
+
+        from quantum_simulations_amd import _lib
+        from quantum_simulations_amd.kernel.device import pack_ops
+        nq, qubits, mats = pack_ops(ops)
+        lib = _lib.load()
+        count = C.c_int32()
+        tm = np.ascontiguousarray(tiles if tiles is not None else [], dtype=np.uint64)
+        args = (self.k, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p), mats.ctypes.data_as(C.c_void_p),
+                len(tm), tm.ctypes.data_as(C.c_void_p) if len(tm) else None)
+        images = self._images
+        _lib.check(lib.qsim_plan_ops_tiled(*args, images.ctypes.data_as(C.c_void_p), images.nbytes, C.byref(count)))
+        if count.value > len(images):    # (a buffer too small only reports the count)
+            images = self._images = np.zeros((2 * count.value, 4096), dtype=np.uint8)
+            _lib.check(lib.qsim_plan_ops_tiled(*args, images.ctypes.data_as(C.c_void_p), images.nbytes, C.byref(count)))
+        weight, last = 0.0, set()
+        for p in range(count.value):     # (pass image = the kernel-argument block: T at byte 12, the tile's high bits from 16)
+            T = int(images[p, 12:16].view("<i4")[0])
+            last = {int(b) for b in images[p, 16:16 + T - 3]}
+            weight += self._tile_layout.tile_cost(self.model, sorted(last)) / self.model_ref if self.model is not None else 1.0
+        return count.value, weight, last
+
+    def apply_ops(self, ops, src=None, dst=None, parts: int = 0, src_parts: int = 0, tiles=None) -> int:
+        self._io_ends(src, dst, parts, src_parts)
+        ops = list(ops)
+        if self.record is not None and ops:
+            self.record.append((ops, None if tiles is None else [int(m) for m in tiles]))
+        if ops and 8 <= self.k <= 35:
+            passes, weight, last = self._plan(ops, tiles)
+        else:                            # (shards too small for tile passes: one launch per gate)
+            passes, weight, last = len(ops), float(len(ops)), None
+        tiles = last is not None and passes > 0
+        fused_in = src is not None and tiles and min(src[1]) >= 3
+        fused_out = dst is not None and tiles and min(dst[1]) >= 3 and not (set(dst[1]) & last)
+        extra = int(src is not None and not fused_in) + int(dst is not None and not fused_out)
+        self.last_extra = extra
+        # (qsim_apply_ops_io_own_slab: ONE pass reads the source and stores the slabs)
+        self._own_in_state = bool(src is not None and dst is not None and dst[2] == src[0] and fused_in and fused_out and passes == 1)
+        self.local_passes += 1
+        self.passes += passes + extra
+        self.weight += weight + extra
+        return passes + extra
+
+    def pack_all(self, bits, buf, skip_pattern, piece=0, n_pieces=1) -> None:
+        super().pack_all(bits, buf, skip_pattern, piece, n_pieces)
+        self.weight += 1.0 / n_pieces
+
+    unpack_all = pack_all
+

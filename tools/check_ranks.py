@@ -13,7 +13,8 @@ def worker(rank, world, port):
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
         from oracle import c_oracle
         from quantum_simulations_amd.circuits import random_clifford_t_circuit
-        from quantum_simulations_amd.runner.distributed import DistributedEngine, HipShardBackend
+        from quantum_simulations_amd.runner.distributed import DistributedEngine
+        from quantum_simulations_amd.runner.shard_backends import HipShardBackend
         c_oracle.set_threads(4)
 
         class Checked(HipShardBackend):

@@ -7,7 +7,8 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from quantum_simulations_amd.circuits import random_1q_cx_circuit, random_clifford_t_circuit, generate_ghz_qft, generate_ghz_circuit
 from quantum_simulations_amd.circuit.io import validate_circuit_dict
-from quantum_simulations_amd.runner.distributed import DistributedEngine, DryBackend
+from quantum_simulations_amd.runner.distributed import DistributedEngine
+from quantum_simulations_amd.runner.shard_backends import DryBackend
 n, world = int(sys.argv[1]), int(sys.argv[2])
 p = world.bit_length() - 1
 eng = DistributedEngine(n, world, 0, backend=DryBackend(n - p), init_process_group=False, layout="search")

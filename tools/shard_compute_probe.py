@@ -18,7 +18,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from quantum_simulations_amd import circuits as gen  # noqa: E402
 from quantum_simulations_amd.circuit.io import validate_circuit_dict  # noqa: E402
 from quantum_simulations_amd.kernel.device import DeviceChunk, pack_ops  # noqa: E402
-from quantum_simulations_amd.runner.distributed import DistributedEngine, PlanningBackend  # noqa: E402
+from quantum_simulations_amd.runner.distributed import DistributedEngine  # noqa: E402
+from quantum_simulations_amd.runner.shard_backends import PlanningBackend  # noqa: E402
 
 n, world = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (32, 4)
 repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 8

@@ -10,7 +10,8 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from quantum_simulations_amd.circuit.io import validate_circuit_dict
 from quantum_simulations_amd.circuits import generate_ghz_circuit, generate_ghz_qft, random_1q_cx_circuit, random_clifford_t_circuit
-from quantum_simulations_amd.runner.distributed import DistributedEngine, PlanningBackend
+from quantum_simulations_amd.runner.distributed import DistributedEngine
+from quantum_simulations_amd.runner.shard_backends import PlanningBackend
 
 n, world = int(sys.argv[1]), int(sys.argv[2])
 methods = sys.argv[3:] or ["heuristic", "belady", "tiles", "ilp"]
