@@ -1,0 +1,223 @@
+// abi_plan.h -- C ABI: the host-only planning entry points (no device, no chunk): what the pass builder would do with an op
+// list, pass counts under several layouts, the layout search, the piece rule of the split form.
+// Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
+extern "C" {
+// Forget the cached pass images (run_fused keeps those of the last few op lists): the next call plans again.  For callers
+// that time a COLD call (bench.py `api_path`) or changed their mind about memory.
+int qsim_plan_cache_clear(void) {
+  std::lock_guard<std::mutex> lock(g_plan_cache_mu);
+  g_plan_cache.clear();
+  return QSIM_OK;
+}
+
+static_assert(sizeof(TileArgs) == QSIM_PASS_IMAGE_BYTES, "pass image = the kernel-argument block of k_tile");
+
+int qsim_plan_ops(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                  void* out, uint64_t out_capacity_bytes, int32_t* n_passes) {
+  return qsim_plan_ops_tiled(n_local_qubits, n_ops, nq, qubits, mats, 0, nullptr, out, out_capacity_bytes, n_passes);
+}
+
+int qsim_plan_ops_tiled(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                        int n_tiles, const uint64_t* tile_masks, void* out, uint64_t out_capacity_bytes, int32_t* n_passes) {
+  if (n_tiles < 0 || (n_tiles && !tile_masks)) return fail(QSIM_ERR_INVALID, "qsim_plan_ops_tiled: bad tile list");
+  if (!n_passes) return fail(QSIM_ERR_INVALID, "qsim_plan_ops: n_passes is null");
+  if (n_local_qubits < kTileMinChunk || n_local_qubits > kTileMaxQubits)
+    return fail(QSIM_ERR_INVALID, "qsim_plan_ops: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
+  int rc = check_op_list(n_ops, nq, qubits, mats, n_local_qubits, kQubitOfPlan);
+  if (rc) return rc;
+  std::vector<FusedOp> ops;
+  classify_ops(n_ops, nq, qubits, mats, &ops);
+  int passes = 0;
+  char* dst = (char*)out;
+  uint64_t used = 0;
+  const TileHint hint = {tile_masks, n_tiles};
+  rc = plan_fused(n_local_qubits, ops, &passes, [&](TileArgs& a, int T, double, bool, bool) {
+    if (dst) {
+      if (used + sizeof(TileArgs) > out_capacity_bytes) return fail(QSIM_ERR_INVALID, "qsim_plan_ops: output buffer too small");
+      std::memcpy(dst + used, &a, sizeof a);
+    }
+    used += sizeof(TileArgs);
+    return (int)QSIM_OK;
+  }, n_tiles ? &hint : nullptr);
+  *n_passes = passes;
+  return rc;
+}
+
+// The NEXT fused pass of a partly executed op list on a partitioned state (the partition planner's view of the pass builder,
+// runner/partition_plan.py): qubits are index bits of the WHOLE state, the bits >= n_local_qubits are rank bits -- an op may
+// use them as controls or phase bits (the rank applies or skips it by its own bits) but an op that TARGETS one has to wait
+// for a re-layout and blocks what depends on it.  done[i] != 0: op i ran already.  Out: the high tile bits the pass builder
+// would choose now (tile_mask, filled to a whole tile; need_mask: the ones its ops need), and the ops it would hold
+// (members, ascending; capacity n_ops).  avoid_mask: bits the fill should leave out (slab bits of the re-layout that follows).
+// hint_mask != 0: that tile instead of a searched one.  An empty pass (everything waits for a rank bit) is reported as
+// *n_members = 0.  Host only, no device.
+int qsim_plan_peek_pass(int n_local_qubits, int n_total_qubits, int n_ops, const int32_t* nq, const int32_t* qubits,
+                        const double* mats, const uint8_t* done, uint64_t avoid_mask, uint64_t hint_mask, uint64_t* tile_mask,
+                        uint64_t* need_mask, int32_t* n_members, int32_t* members) {
+  if (!done || !tile_mask || !n_members || !members) return fail(QSIM_ERR_INVALID, "qsim_plan_peek_pass: null argument");
+  if (n_local_qubits < kTileMinChunk || n_local_qubits > kTileMaxQubits)
+    return fail(QSIM_ERR_INVALID, "qsim_plan_peek_pass: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
+  if (n_total_qubits < n_local_qubits || n_total_qubits > 63) return fail(QSIM_ERR_INVALID, "qsim_plan_peek_pass: bad total qubit count %d", n_total_qubits);
+  int rc = check_op_list(n_ops, nq, qubits, mats, n_total_qubits, kQubitOfState);
+  if (rc) return rc;
+  std::vector<FusedOp> ops;
+  std::vector<int32_t> origin;                 // classified op -> index in the caller's list (identities drop out)
+  classify_ops(n_ops, nq, qubits, mats, &ops, &origin);
+  std::vector<uint8_t> done_ops;
+  for (int32_t i : origin) done_ops.push_back(done[i]);
+  std::vector<size_t> held;
+  PeekPlan peek;
+  peek.n_total = n_total_qubits;
+  peek.done = done_ops.data();
+  peek.avoid = avoid_mask;
+  peek.tile_mask = peek.need_mask = 0;
+  peek.members = &held;
+  int passes = 0;
+  const TileHint hint = {&hint_mask, 1};
+  rc = plan_fused(n_local_qubits, ops, &passes, [](TileArgs&, int, double, bool, bool) { return (int)QSIM_OK; },
+                  hint_mask ? &hint : nullptr, &peek);
+  if (rc) return rc;
+  *tile_mask = peek.tile_mask;
+  if (need_mask) *need_mask = peek.need_mask;
+  *n_members = (int32_t)held.size();
+  for (size_t j = 0; j < held.size(); ++j) members[j] = origin[held[j]];
+  return QSIM_OK;
+}
+
+// Pass counts of ONE op list under several qubit layouts (layouts[l * n_local_qubits + q] = the index bit of logical qubit q
+// in layout l), planned in parallel on the host: the greedy pass builder's result depends on which three qubits live on the
+// line bits (they belong to every tile) -- 17 to 20 passes for the 28-qubit bench circuit -- so an engine that is free to
+// choose the layout (runner/engine.py) tries a few dozen and keeps the cheapest.  No device involved.
+int qsim_plan_count_layouts(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                            int n_layouts, const int32_t* layouts, int32_t* n_passes, int n_threads) {
+  if (!n_passes || n_layouts < 0 || (n_layouts && !layouts)) return fail(QSIM_ERR_INVALID, "qsim_plan_count_layouts: bad arguments");
+  if (n_local_qubits < kTileMinChunk || n_local_qubits > kTileMaxQubits)
+    return fail(QSIM_ERR_INVALID, "qsim_plan_count_layouts: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
+  const int bad_ops = check_op_list(n_ops, nq, qubits, mats, n_local_qubits, kQubitOfPlan);
+  if (bad_ops) return bad_ops;
+  for (int l = 0; l < n_layouts; ++l) {
+    u64 seen = 0;
+    for (int q = 0; q < n_local_qubits; ++q) {
+      const int b = layouts[(size_t)l * n_local_qubits + q];
+      if (b < 0 || b >= n_local_qubits || ((seen >> b) & 1)) return fail(QSIM_ERR_INVALID, "qsim_plan_count_layouts: layout %d is not a permutation", l);
+      seen |= 1ull << b;
+    }
+  }
+  (void)tuning();                                          // (initialised before the threads start)
+  std::atomic<int> next{0}, bad{0};
+  auto work = [&]() {
+    std::vector<FusedOp> ops;
+    for (;;) {
+      const int l = next.fetch_add(1);
+      if (l >= n_layouts) return;
+      const int32_t* lay = layouts + (size_t)l * n_local_qubits;
+      ops.clear();
+      for (int i = 0; i < n_ops; ++i) {
+        const int32_t q[2] = {lay[qubits[2 * i]], nq[i] == 2 ? lay[qubits[2 * i + 1]] : -1};
+        FusedOp o;
+        if (classify_op(nq[i], q, mats + 32 * (size_t)i, &o)) ops.push_back(o);
+      }
+      int passes = 0;
+      const int rc = plan_fused(n_local_qubits, ops, &passes, [](TileArgs&, int, double, bool, bool) { return (int)QSIM_OK; });
+      if (rc) bad.store(1);
+      n_passes[l] = rc ? -1 : passes;
+    }
+  };
+  const int nt = std::max(1, std::min(n_threads > 0 ? n_threads : 1, std::min(n_layouts, 64)));
+  std::vector<std::thread> pool;
+  for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+  work();
+  for (std::thread& t : pool) t.join();
+  if (bad.load()) return fail(QSIM_ERR_INVALID, "qsim_plan_count_layouts: a layout could not be planned");
+  return QSIM_OK;
+}
+
+// Which index bit should every qubit live on so that the tiles of the given passes fall on index-bit sets with a good DRAM
+// pattern?  Simulated annealing over the assignment (bits 0..2, the 128-byte line, stay) under the caller's cost model of
+// a tile-bit set: c0 + sum_b bit_cost[b - 3] + sum_{a < b} pair_cost[(a - 3) * nb + (b - 3)], nb = top_bit - 2, bits above
+// top_bit priced like top_bit (runner/tile_layout.py holds the coefficients: ridge fits to measured passes).  tile_masks[p] =
+// the high tile bits of pass p as LOGICAL qubits; out_l2p[q] = the index bit chosen for qubit q.  Host only.
+int qsim_choose_layout(int n_local_qubits, int n_tiles, const uint64_t* tile_masks, int top_bit, const double* bit_cost,
+                       const double* pair_cost, const double* triple_cost, uint64_t seed, int sweeps, int32_t* out_l2p,
+                       double* cost_identity, double* cost_chosen) {
+  const int n = n_local_qubits, low = kTileLow;
+  if (n < low + 2 || n > 62 || n_tiles < 0 || (n_tiles && !tile_masks) || !bit_cost || !pair_cost || !out_l2p || top_bit < low || top_bit > 62 || sweeps < 1)
+    return fail(QSIM_ERR_INVALID, "qsim_choose_layout: bad arguments");
+  const int nb = top_bit - low + 1;
+  std::vector<std::vector<int>> tiles((size_t)n_tiles);
+  std::vector<std::vector<int>> member((size_t)n);
+  for (int t = 0; t < n_tiles; ++t)
+    for (int q = low; q < n; ++q)
+      if ((tile_masks[t] >> q) & 1) { tiles[(size_t)t].push_back(q); member[(size_t)q].push_back(t); }
+  std::vector<double> sym((size_t)nb * nb, 0.0);
+  for (int a = 0; a < nb; ++a)
+    for (int b = a + 1; b < nb; ++b) sym[(size_t)a * nb + b] = sym[(size_t)b * nb + a] = pair_cost[(size_t)a * nb + b];
+  std::vector<int> l2p((size_t)n);
+  for (int q = 0; q < n; ++q) l2p[(size_t)q] = q;
+  // (optional third-order terms: triple_cost[(a * nb + b) * nb + c] for a < b < c, zero elsewhere)
+  auto cost_of = [&](int t) {
+    int idx[64], m = 0;
+    for (int q : tiles[(size_t)t]) idx[m++] = std::min(l2p[(size_t)q], top_bit) - low;
+    double c = 0;
+    for (int i = 0; i < m; ++i) {
+      c += bit_cost[idx[i]];
+      for (int j = i + 1; j < m; ++j) c += sym[(size_t)idx[i] * nb + idx[j]];
+    }
+    if (triple_cost) {
+      std::sort(idx, idx + m);
+      for (int i = 0; i < m; ++i)
+        for (int j = i + 1; j < m; ++j) {
+          if (idx[j] == idx[i]) continue;
+          const double* row = triple_cost + ((size_t)idx[i] * nb + idx[j]) * nb;
+          for (int l = j + 1; l < m; ++l) if (idx[l] != idx[j]) c += row[idx[l]];
+        }
+    }
+    return c;
+  };
+  std::vector<double> costs((size_t)n_tiles);
+  double cur = 0;
+  for (int t = 0; t < n_tiles; ++t) cur += (costs[(size_t)t] = cost_of(t));
+  const double identity = cur;
+  double best = cur;
+  std::vector<int> best_l2p = l2p;
+  u64 rs = seed * 0x9E3779B97F4A7C15ull + 0x2545F4914F6CDD1Dull;
+  auto rnd = [&]() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; };
+  const int np_ = n - low;
+  const long steps = (long)sweeps * np_ * np_ / 2;
+  const double T0 = std::max(1e-3, 0.03 * identity / std::max(1, n_tiles));
+  std::vector<int> touched;
+  std::vector<double> fresh;
+  for (long it = 0; it < steps && n_tiles > 0; ++it) {
+    const int a = low + (int)(rnd() % (u64)np_);
+    int b = low + (int)(rnd() % (u64)(np_ - 1));
+    if (b >= a) ++b;
+    touched.clear();
+    for (int t : member[(size_t)a]) touched.push_back(t);
+    for (int t : member[(size_t)b]) if (std::find(touched.begin(), touched.end(), t) == touched.end()) touched.push_back(t);
+    if (touched.empty()) continue;
+    std::swap(l2p[(size_t)a], l2p[(size_t)b]);
+    fresh.clear();
+    double delta = 0;
+    for (int t : touched) { fresh.push_back(cost_of(t)); delta += fresh.back() - costs[(size_t)t]; }
+    const double T = T0 * (1.0 - (double)it / (double)steps) + 1e-4;
+    const double u = (double)(rnd() >> 11) * 0x1p-53;
+    if (delta < 0 || u < std::exp(-delta / T)) {
+      for (size_t i = 0; i < touched.size(); ++i) costs[(size_t)touched[i]] = fresh[i];
+      cur += delta;
+      if (cur < best - 1e-12) { best = cur; best_l2p = l2p; }
+    } else {
+      std::swap(l2p[(size_t)a], l2p[(size_t)b]);
+    }
+  }
+  for (int q = 0; q < n; ++q) out_l2p[q] = best_l2p[(size_t)q];
+  if (cost_identity) *cost_identity = identity;
+  if (cost_chosen) *cost_chosen = best;
+  return QSIM_OK;
+}
+
+// (k, m, pieces asked for) -> pieces made: the rule of the split form as a pure function (schedulers, dry runs, tests)
+int qsim_split_piece_count(int n_local_qubits, int m, int dst_parts) {
+  if (m < 1 || m > 3 || m > n_local_qubits || dst_parts == 0) return 1;
+  return 1 << piece_bits_for(n_local_qubits, m, dst_parts < 0 ? -dst_parts : dst_parts, dst_parts < 0 ? kTileLow : 20);
+}
+}  // extern "C"

@@ -1,0 +1,355 @@
+// abi_readout.h -- C ABI: what is read off a chunk without changing it: norm, outcome probabilities, Pauli-sum
+// expectation values, sparse export, the closed-form checkers and the fingerprint.
+// Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
+extern "C" {
+int qsim_norm2(qsim_chunk* c, double* out) {
+  int rc = check_chunk(c, "qsim_norm2");
+  if (rc) return rc;
+  if (!out) return fail(QSIM_ERR_INVALID, "out is null");
+  if ((rc = ensure_scratch(c))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const unsigned grid = std::min<unsigned>(stream_grid(amps(c)), kReduceBlocks);
+  hipLaunchKernelGGL(k_norm2_partial, dim3(grid), dim3(kBlock), 0, c->stream, c->amp, amps(c), c->scratch);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> host(grid);
+  HIP_TRY(hipMemcpyAsync(host.data(), c->scratch, sizeof(double) * grid, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  long double total = 0;
+  for (double v : host) total += v;
+  *out = (double)total;
+  return QSIM_OK;
+}
+
+// Joint outcome probabilities of r measured qubits: k_hist (one read-only pass, partial histograms per workgroup) and
+// k_hist_sum (the partials in workgroup order); 2^r doubles cross to the host.  Bits of the chunk index are dealt out as
+// described at k_hist: 0..7 threads, then item bits, workgroup bits and loop bits, selected qubits first.
+int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out) {
+  int rc = check_chunk(c, "qsim_probabilities");
+  if (rc) return rc;
+  if (!qubits || !out) return fail(QSIM_ERR_INVALID, "qsim_probabilities: null argument");
+  if (r < 1 || r > 8) return fail(QSIM_ERR_INVALID, "qsim_probabilities: 1 <= r <= 8 qubits expected, got %d", r);
+  if ((rc = require_no_parts(c, "qsim_probabilities"))) return rc;
+  u64 sel = 0;
+  for (int i = 0; i < r; ++i) {
+    if ((rc = check_local_qubit(c, qubits[i]))) return rc;
+    for (int j = 0; j < i; ++j) if (qubits[j] == qubits[i]) return fail(QSIM_ERR_INVALID, "qsim_probabilities: repeated qubit %d", qubits[i]);
+    sel |= 1ull << qubits[i];
+  }
+  if ((rc = ensure_hist(c))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const int k = c->k;
+  const int above = std::max(0, k - 8);
+  const int n_item = std::min(3, above);
+  const int n_wg = std::min(kHistWgBits, above - n_item);
+  HistArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.amp = c->amp;
+  a.n = amps(c);
+  a.r = r;
+  for (int i = 0; i < r; ++i) a.q[i] = qubits[i];
+  a.lane_sel = (int)(sel & 63);
+  // selected bits above the thread bits first (item bits, then workgroup bits), then the free bits: the lowest ones as
+  // item bits (a thread's loads stay close), the highest as workgroup bits (each XCD's workgroups cover one region)
+  std::vector<int> hi_sel, free_bits;
+  for (int b = 8; b < k; ++b) ((sel >> b) & 1 ? hi_sel : free_bits).push_back(b);
+  size_t si = 0, lo = 0, hi = free_bits.size();
+  u64 used = 0;
+  for (int j = 0; j < n_item; ++j) { const int b = si < hi_sel.size() ? hi_sel[si++] : free_bits[lo++]; a.item_bit[j] = b; used |= 1ull << b; }
+  std::vector<int> wg;
+  for (int j = 0; j < n_wg; ++j) { const int b = si < hi_sel.size() ? hi_sel[si++] : free_bits[--hi]; wg.push_back(b); used |= 1ull << b; }
+  if (si != hi_sel.size() || lo > hi) return fail(QSIM_ERR_INVALID, "internal: qsim_probabilities could not place the selected bits");
+  std::sort(wg.begin(), wg.end());
+  for (int j = 0; j < n_wg; ++j) a.wg_bit[j] = wg[(size_t)j];
+  a.n_wg_bits = n_wg;
+  const u64 all_hi = k > 8 ? (((1ull << k) - 1) & ~255ull) : 0;
+  a.loop_mask = all_hi & ~used;
+  a.partial = c->hist;
+  const int nbins = 1 << r;
+  const unsigned grid = 1u << n_wg;
+  double* dev_out = c->hist + ((u64)grid << 8);
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  {
+    ProfileScope prof(8, 16.0 * (double)amps(c), c->stream, nt);
+#define QSIM_HIST_LAUNCH(IB)                                                                                     \
+    if (nt) hipLaunchKernelGGL((k_hist<IB, true>), dim3(grid), dim3(kBlock), 0, c->stream, a);                    \
+    else hipLaunchKernelGGL((k_hist<IB, false>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+    switch (n_item) {
+      case 0: QSIM_HIST_LAUNCH(0) break;
+      case 1: QSIM_HIST_LAUNCH(1) break;
+      case 2: QSIM_HIST_LAUNCH(2) break;
+      default: QSIM_HIST_LAUNCH(3) break;
+    }
+#undef QSIM_HIST_LAUNCH
+    HIP_TRY(hipGetLastError());
+    prof.done(c->stream);
+  }
+  hipLaunchKernelGGL(k_hist_sum, dim3(nbins), dim3(kBlock), 0, c->stream, (const double*)c->hist, (int)grid, nbins, dev_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, dev_out, sizeof(double) * nbins, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return QSIM_OK;
+}
+
+// Pauli-sum expectation values (expect_kernels.h): the pass plan on the host, then per pass k_expect_tile (or
+// k_expect_wide) and k_hist_sum (the workgroup rows in workgroup order) into a device array of per-term results, in
+// pass order; one copy of n_terms doubles to the host at the end.
+int qsim_plan_expectation(int n_local_qubits, int n_terms, const uint64_t* x_masks, int32_t* pass_of_term, uint64_t* tile_masks, int* n_passes) {
+  if (!n_passes || (n_terms > 0 && (!pass_of_term || !tile_masks)))
+    return fail(QSIM_ERR_INVALID, "qsim_plan_expectation: null argument");
+  ExpPlan p;
+  const int rc = plan_expectation(n_local_qubits, n_terms, x_masks, &p);
+  if (rc) return rc;
+  for (int t = 0; t < n_terms; ++t) pass_of_term[t] = p.pass_of[(size_t)t];
+  for (size_t q = 0; q < p.tile.size(); ++q) tile_masks[q] = p.tile[q];
+  *n_passes = (int)p.tile.size();
+  return QSIM_OK;
+}
+
+static int ensure_expect(qsim_chunk* c, u64 bytes) {
+  if (c->expect_bytes >= bytes) return QSIM_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->expect) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipFree(c->expect));
+    c->expect = nullptr;
+    c->expect_bytes = 0;
+  }
+  HIP_TRY(hipMalloc(&c->expect, bytes));
+  c->expect_bytes = bytes;
+  return QSIM_OK;
+}
+
+int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, const uint64_t* z_masks, double* out, int* n_passes) {
+  int rc = check_chunk(c, "qsim_expectation_pauli");
+  if (rc) return rc;
+  if (n_terms < 0) return fail(QSIM_ERR_INVALID, "qsim_expectation_pauli: n_terms = %d", n_terms);
+  if (!n_passes || (n_terms > 0 && (!x_masks || !z_masks || !out)))
+    return fail(QSIM_ERR_INVALID, "qsim_expectation_pauli: null argument");
+  if ((rc = require_no_parts(c, "qsim_expectation_pauli"))) return rc;
+  const int k = c->k;
+  const u64 all = (1ull << k) - 1;
+  for (int t = 0; t < n_terms; ++t)
+    if ((x_masks[t] | z_masks[t]) & ~all)
+      return fail(QSIM_ERR_NONLOCAL, "qsim_expectation_pauli: term %d acts on index bit %d >= log2(chunk_size)=%d", t,
+                  63 - __builtin_clzll((x_masks[t] | z_masks[t]) & ~all), k);
+  ExpPlan p;
+  if ((rc = plan_expectation(k, n_terms, x_masks, &p))) return rc;
+  *n_passes = 0;
+  if (n_terms == 0) return QSIM_OK;
+  const int np = (int)p.tile.size();
+  // term tables of the tile passes (in pass order) and the result slot of every term
+  std::vector<int> first(np + 1, 0);
+  for (int q = 0; q < np; ++q) first[q + 1] = first[q] + p.count[q];
+  std::vector<int> fill(first.begin(), first.end() - 1), order((size_t)n_terms);
+  for (int t = 0; t < n_terms; ++t) order[(size_t)t] = fill[(size_t)p.pass_of[(size_t)t]]++;   // result slot of term t
+  std::vector<ExpTerm> table((size_t)n_terms);
+  std::memset(table.data(), 0, sizeof(ExpTerm) * table.size());
+  std::vector<int> wide_term((size_t)np, -1);       // the term of a wide-X pass
+  for (int t = 0; t < n_terms; ++t) {
+    const u64 T = p.tile[(size_t)p.pass_of[(size_t)t]];
+    const u64 x = x_masks[t], z = z_masks[t];
+    ExpTerm& e = table[(size_t)order[(size_t)t]];
+    exp_phase(x, z, &e.cr, &e.ci);
+    if (!T && x) {                                  // wide-X: the masks go as launch arguments
+      wide_term[(size_t)p.pass_of[(size_t)t]] = t;
+      continue;
+    }
+    e.xi = (unsigned)exp_pext(x, T);
+    e.zi = (unsigned)exp_pext(z & T, T);
+    e.zo = z & ~T;
+    e.h = e.xi ? 31 - __builtin_clz(e.xi) : -1;
+  }
+  const u64 n_tiles_max = 1ull << (k - std::min(k, kExpTileBits));
+  const unsigned grid_tile = (unsigned)std::min<u64>(n_tiles_max, kExpMaxWg);
+  int max_count = 1;
+  for (int q = 0; q < np; ++q) max_count = std::max(max_count, p.count[q]);
+  const u64 partial_bytes = sizeof(double) * (u64)kExpMaxWg * (u64)max_count;
+  const u64 table_off = partial_bytes, out_off = table_off + sizeof(ExpTerm) * (u64)n_terms;
+  if ((rc = ensure_expect(c, out_off + sizeof(double) * (u64)n_terms))) return rc;
+  char* base = static_cast<char*>(c->expect);
+  double* partial = reinterpret_cast<double*>(base);
+  ExpTerm* dev_table = reinterpret_cast<ExpTerm*>(base + table_off);
+  double* dev_out = reinterpret_cast<double*>(base + out_off);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(dev_table, table.data(), sizeof(ExpTerm) * table.size(), hipMemcpyHostToDevice, c->stream));
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  for (int q = 0; q < np; ++q) {
+    const u64 T = p.tile[(size_t)q];
+    if (wide_term[(size_t)q] >= 0) {
+      const int t = wide_term[(size_t)q];
+      ExpWideArgs w;
+      std::memset(&w, 0, sizeof w);
+      w.amp = c->amp;
+      w.partial = partial;
+      w.half = amps(c) >> 1;
+      w.x = x_masks[t];
+      w.z = z_masks[t];
+      w.h = 63 - __builtin_clzll(w.x);
+      w.cr = table[(size_t)first[q]].cr;
+      w.ci = table[(size_t)first[q]].ci;
+      const unsigned grid = (unsigned)std::min<u64>(std::max<u64>(w.half / kBlock, 1), kExpMaxWg);
+      if (nt) hipLaunchKernelGGL((k_expect_wide<true>), dim3(grid), dim3(kBlock), 0, c->stream, w);
+      else hipLaunchKernelGGL((k_expect_wide<false>), dim3(grid), dim3(kBlock), 0, c->stream, w);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_hist_sum, dim3(1), dim3(kBlock), 0, c->stream, (const double*)partial, (int)grid, 1,
+                         dev_out + first[q]);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
+    ExpArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.amp = c->amp;
+    a.terms = dev_table + first[q];
+    a.partial = partial;
+    a.tb = __builtin_popcountll(T);
+    for (int b = 0, j = 0; b < k; ++b)
+      if ((T >> b) & 1) a.tile_bit[j++] = b;
+    a.outer_mask = all & ~T;
+    a.n_tiles = 1ull << (k - a.tb);
+    a.n_terms = p.count[q];
+    int slices = 1;
+    while (slices * 2 * a.n_terms <= kBlock) slices *= 2;
+    a.slices = slices;
+    const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, grid_tile);
+    if (nt) hipLaunchKernelGGL((k_expect_tile<true>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_expect_tile<false>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_hist_sum, dim3(a.n_terms), dim3(kBlock), 0, c->stream, (const double*)partial, (int)grid,
+                       a.n_terms, dev_out + first[q]);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<double> res((size_t)n_terms);
+  HIP_TRY(hipMemcpyAsync(res.data(), dev_out, sizeof(double) * (u64)n_terms, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int t = 0; t < n_terms; ++t) out[t] = res[(size_t)order[(size_t)t]];
+  *n_passes = np;
+  return QSIM_OK;
+}
+
+// Sparse export: the amplitudes with |re| > eps or |im| > eps as rows (index, re, im), ascending by index.
+int qsim_count_nonzero(qsim_chunk* c, double eps, uint64_t* count) {
+  int rc = check_chunk(c, "qsim_count_nonzero");
+  if (rc) return rc;
+  if (!count || !(eps >= 0)) return fail(QSIM_ERR_INVALID, "qsim_count_nonzero: bad arguments");
+  if ((rc = ensure_scratch(c))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  unsigned long long* dcount = reinterpret_cast<unsigned long long*>(c->scratch);
+  HIP_TRY(hipMemsetAsync(dcount, 0, sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(k_count_kept, dim3(stream_grid(amps(c))), dim3(kBlock), 0, c->stream, c->amp, amps(c), eps, dcount);
+  HIP_TRY(hipGetLastError());
+  unsigned long long host = 0;
+  HIP_TRY(hipMemcpyAsync(&host, dcount, sizeof host, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *count = host;
+  return QSIM_OK;
+}
+
+int qsim_export_nonzero(qsim_chunk* c, double eps, uint64_t capacity, uint64_t* out_idx, double* out_re_im, uint64_t* n_rows) {
+  int rc = check_chunk(c, "qsim_export_nonzero");
+  if (rc) return rc;
+  if (!n_rows || !(eps >= 0) || (capacity && (!out_idx || !out_re_im))) return fail(QSIM_ERR_INVALID, "qsim_export_nonzero: bad arguments");
+  if ((rc = ensure_scratch(c))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  u64* didx = nullptr;
+  double2* damp = nullptr;
+  if (capacity) {
+    if (hipMalloc((void**)&didx, sizeof(u64) * capacity) != hipSuccess) return fail(QSIM_ERR_NOMEM, "qsim_export_nonzero: no device memory for %llu rows", (u64)capacity);
+    if (hipMalloc((void**)&damp, sizeof(double2) * capacity) != hipSuccess) { (void)hipFree(didx); return fail(QSIM_ERR_NOMEM, "qsim_export_nonzero: no device memory for %llu rows", (u64)capacity); }
+  }
+  unsigned long long* cursor = reinterpret_cast<unsigned long long*>(c->scratch);
+  auto cleanup = [&]() { if (didx) (void)hipFree(didx); if (damp) (void)hipFree(damp); };
+  hipError_t e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), c->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_append_kept, dim3(stream_grid(amps(c))), dim3(kBlock), 0, c->stream, c->amp, amps(c), eps, cursor, (u64)capacity, didx, damp);
+    e = hipGetLastError();
+  }
+  unsigned long long total = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&total, cursor, sizeof total, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  const u64 got = std::min<u64>(total, capacity);
+  std::vector<u64> idx(got);
+  std::vector<double2> amp(got);
+  if (e == hipSuccess && got) e = hipMemcpy(idx.data(), didx, sizeof(u64) * got, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && got) e = hipMemcpy(amp.data(), damp, sizeof(double2) * got, hipMemcpyDeviceToHost);
+  cleanup();
+  if (e != hipSuccess) return fail(QSIM_ERR_HIP, "qsim_export_nonzero: %s", hipGetErrorString(e));
+  *n_rows = total;
+  if (total > capacity) return QSIM_OK;             // the caller sees n_rows > capacity and comes back with room (nothing written)
+  std::vector<u64> order(got);
+  for (u64 i = 0; i < got; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](u64 a, u64 b) { return idx[a] < idx[b]; });
+  for (u64 i = 0; i < got; ++i) {
+    out_idx[i] = idx[order[i]];
+    out_re_im[2 * i] = amp[order[i]].x;
+    out_re_im[2 * i + 1] = amp[order[i]].y;
+  }
+  return QSIM_OK;
+}
+
+static int bit_perm_from(const int32_t* log_to_phys, int n_total_qubits, BitPerm* perm, const char* what) {
+  std::memset(perm, 0, sizeof *perm);
+  if (!log_to_phys) return QSIM_OK;
+  u64 seen = 0;
+  for (int q = 0; q < n_total_qubits; ++q) {
+    const int ph = log_to_phys[q];
+    if (ph < 0 || ph >= n_total_qubits || (seen >> ph) & 1) return fail(QSIM_ERR_INVALID, "%s: log_to_phys is not a permutation", what);
+    seen |= 1ull << ph;
+    perm->to_logical[ph] = (unsigned char)q;
+    if (ph != q) perm->active = 1;
+  }
+  return QSIM_OK;
+}
+
+int qsim_max_abs_err_closed_form(qsim_chunk* c, int kind, int n_total_qubits, uint64_t base_index, double* out) {
+  return qsim_max_abs_err_closed_form_perm(c, kind, n_total_qubits, base_index, nullptr, out);
+}
+
+int qsim_max_abs_err_closed_form_perm(qsim_chunk* c, int kind, int n_total_qubits, uint64_t base_index, const int32_t* log_to_phys, double* out) {
+  int rc = check_chunk(c, "qsim_max_abs_err_closed_form");
+  if (rc) return rc;
+  if (!out || (kind != 0 && kind != 1) || n_total_qubits < c->k || n_total_qubits > 52)
+    return fail(QSIM_ERR_INVALID, "qsim_max_abs_err_closed_form: bad arguments");
+  BitPerm perm;
+  if ((rc = bit_perm_from(log_to_phys, n_total_qubits, &perm, "qsim_max_abs_err_closed_form"))) return rc;
+  if ((rc = ensure_scratch(c))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const unsigned grid = std::min<unsigned>(stream_grid(amps(c)), kReduceBlocks);
+  hipLaunchKernelGGL(k_closed_form_err, dim3(grid), dim3(kBlock), 0, c->stream, c->amp, amps(c), kind,
+                     n_total_qubits, (u64)base_index, c->scratch, perm);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> host(grid);
+  HIP_TRY(hipMemcpyAsync(host.data(), c->scratch, sizeof(double) * grid, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  double worst = 0;
+  for (double v : host) worst = std::max(worst, v);
+  *out = worst;
+  return QSIM_OK;
+}
+
+// sum over the chunk's amplitudes whose logical index passes the filter of amp * w(logical index): see k_fingerprint
+int qsim_fingerprint(qsim_chunk* c, int n_total_qubits, uint64_t base_index, const int32_t* log_to_phys, uint64_t seed,
+                     uint64_t sel_mask, uint64_t sel_value, double out[2]) {
+  int rc = check_chunk(c, "qsim_fingerprint");
+  if (rc) return rc;
+  if (!out || n_total_qubits < c->k || n_total_qubits > 52) return fail(QSIM_ERR_INVALID, "qsim_fingerprint: bad arguments");
+  if (base_index & (amps(c) - 1)) return fail(QSIM_ERR_INVALID, "qsim_fingerprint: base_index must be a multiple of the chunk length");
+  if (n_total_qubits < 64 && ((base_index + amps(c) - 1) >> n_total_qubits)) return fail(QSIM_ERR_INVALID, "qsim_fingerprint: the chunk does not fit a state of %d qubits at that base", n_total_qubits);
+  if (sel_value & ~sel_mask) return fail(QSIM_ERR_INVALID, "qsim_fingerprint: sel_value has bits outside sel_mask");
+  BitPerm perm;
+  if ((rc = bit_perm_from(log_to_phys, n_total_qubits, &perm, "qsim_fingerprint"))) return rc;
+  if ((rc = ensure_scratch(c))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const unsigned grid = std::min<unsigned>(stream_grid(amps(c)), kReduceBlocks / 2);
+  hipLaunchKernelGGL(k_fingerprint, dim3(grid), dim3(kBlock), 0, c->stream, c->amp, amps(c), n_total_qubits, (u64)base_index,
+                     fp_mix((u64)seed), (u64)sel_mask, (u64)sel_value, c->scratch, perm);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> host(2 * (size_t)grid);
+  HIP_TRY(hipMemcpyAsync(host.data(), c->scratch, sizeof(double) * host.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  long double re = 0, im = 0;
+  for (unsigned b = 0; b < grid; ++b) { re += host[2 * b]; im += host[2 * b + 1]; }
+  out[0] = (double)re;
+  out[1] = (double)im;
+  return QSIM_OK;
+}
+}  // extern "C"

@@ -1205,15 +1205,21 @@ static int piece_bits_for(int k, int m, int want, int min_piece_bits) {
   return nb;
 }
 
+// The top nb index bits of a k-bit index that are none of the m slab bits, ascending (the piece bits of the split form).
+static void top_free_bits(int k, int m, const int32_t* slab_bits, int nb, int* out) {
+  for (int b = k - 1, found = 0; b >= 0 && found < nb; --b) {
+    bool slab = false;
+    for (int i = 0; i < m; ++i) slab = slab || slab_bits[i] == b;
+    if (!slab) out[nb - 1 - found++] = b;
+  }
+}
+
 static void plan_parts(PendingLast* p, int k, int want, const uint8_t* tile_high, int n_tile_high, int min_piece_bits) {
-  auto is_slab = [&](int b) { for (int i = 0; i < p->m; ++i) if (p->bits[i] == b) return true; return false; };
   auto is_tile = [&](int b) { for (int j = 0; j < n_tile_high; ++j) if (tile_high[j] == b) return true; return false; };
   p->nb = piece_bits_for(k, p->m, want, min_piece_bits);
-  int top[3], found = 0;
-  for (int b = k - 1; b >= 0 && found < p->nb; --b) if (!is_slab(b)) top[found++] = b;    // descending
-  for (int i = 0; i < p->nb; ++i) p->piece_bit[i] = top[p->nb - 1 - i];
+  top_free_bits(k, p->m, p->bits, p->nb, p->piece_bit);
   p->nb_free = 0;
-  while (p->nb_free < p->nb && !is_tile(top[p->nb_free])) ++p->nb_free;
+  while (p->nb_free < p->nb && !is_tile(p->piece_bit[p->nb - 1 - p->nb_free])) ++p->nb_free;    // from the top
   p->stored = p->launched = 0;
 }
 
