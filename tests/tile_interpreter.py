@@ -23,6 +23,10 @@ OPC = dict(DENSE1=1, SWAP1=10, ANTI1=19, PHASE=28, DENSE2=36, REAL1=45, YLIKE1=5
 DIRECT_IN, DIRECT_OUT = 0x10, 0x20     # TileArgs::order flags
 _FAMILIES = ("DENSE1", "SWAP1", "ANTI1", "PHASE", "DENSE2", "REAL1", "YLIKE1", "PHASE_NEG", "PHASE_I", "PHASE_NI", "DIAGR",
              "HAD1", "SCALE", "ASWAP1")
+# entries of the engine's branch table per family: 1q variants (target register x optional control register), 3 * JA + JB,
+# a register mask, the four merged-run shapes, one
+FAMILY_WIDTH = {f: (9 if f in ("DENSE1", "SWAP1", "ANTI1", "DENSE2", "REAL1", "YLIKE1", "HAD1", "ASWAP1")
+                    else 8 if f.startswith("PHASE") else 4 if f == "DIAGR" else 1) for f in _FAMILIES}
 _IMAGE = np.dtype([("amp", "<u8"), ("nrec", "<i4"), ("T", "<i4"), ("h", "u1", (11,)), ("order", "u1"), ("ntiles", "<u4"),
                    ("lay_in", "u1", (12,)), ("lay_out", "u1", (12,)), ("amp_out", "<u8"),
                    # re-layout fused into a pass (planned images carry none: all zero)
@@ -94,8 +98,7 @@ def records(img):
             outer = int(d[2]) << 3
             # the second dispatch of a predicated gate may only reach a gate case (the engine's control-flow checks,
             # tests/test_engine_asm_static.py, rely on it)
-            assert any(OPC[f] <= case < OPC[f] + (9 if f in ("DENSE1", "SWAP1", "ANTI1", "DENSE2", "REAL1", "YLIKE1", "HAD1", "ASWAP1")
-                                                   else 8 if f.startswith("PHASE") else 4 if f == "DIAGR" else 1) for f in _FAMILIES), case
+            assert any(OPC[f] <= case < OPC[f] + FAMILY_WIDTH[f] for f in _FAMILIES), case
             if entry == OPC["PRED_LANE"]:
                 assert blk
             elif entry == OPC["PRED_OUTER_ZERO"]:      # the listed outer bits must all be 0: reported as a NEGATIVE mask
