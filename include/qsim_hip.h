@@ -184,6 +184,13 @@ int qsim_plan_peek_pass(int n_local_qubits, int n_total_qubits, int n_ops, const
                         const double* mats, const uint8_t* done, uint64_t avoid_mask, uint64_t hint_mask, uint64_t* tile_mask,
                         uint64_t* need_mask, int32_t* n_members, int32_t* members);
 
+/* The searching pass builder: the tiles (high tile bits, one mask per pass) of a plan with as few passes as a beam
+ * search of width `beam` finds (<= 0: the default), never more than qsim_plan_ops needs; qsim_plan_ops_tiled and
+ * qsim_apply_ops_tiled turn them into exactly *n_passes passes.  out_masks may be NULL to count only.  Host only; a few
+ * hundred times the planning time of qsim_plan_ops: for plans that run many times. */
+int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, int beam,
+                     uint64_t* out_masks, int out_capacity, int32_t* n_passes);
+
 /* Pass counts of ONE op list under n_layouts qubit layouts (layouts[l * n_local_qubits + q] = index bit of logical qubit q),
  * planned in parallel on n_threads host threads, no device: the pass builder's result depends on which qubits live on the
  * three line bits (they belong to every tile), so a host that is free to choose the layout tries several. */

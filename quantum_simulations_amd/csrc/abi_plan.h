@@ -43,6 +43,34 @@ int qsim_plan_ops_tiled(int n_local_qubits, int n_ops, const int32_t* nq, const 
   return rc;
 }
 
+// The searching pass builder (tile_search.h): the tiles of a plan of the op list with as few passes as a beam search of
+// width `beam` finds (<= 0: the default width), never more than qsim_plan_ops needs.  out_masks[p] = the high tile bits of
+// pass p (capacity out_capacity masks; may be NULL to count only); handed to qsim_plan_ops_tiled / qsim_apply_ops_tiled
+// they give exactly *n_passes passes.  Host only, no device.
+int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, int beam,
+                     uint64_t* out_masks, int out_capacity, int32_t* n_passes) {
+  if (!n_passes || out_capacity < 0) return fail(QSIM_ERR_INVALID, "qsim_plan_search: bad arguments");
+  if (n_local_qubits < kTileMinChunk || n_local_qubits > kTileMaxQubits)
+    return fail(QSIM_ERR_INVALID, "qsim_plan_search: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
+  int rc = check_op_list(n_ops, nq, qubits, mats, n_local_qubits, kQubitOfPlan);
+  if (rc) return rc;
+  std::vector<FusedOp> ops;
+  classify_ops(n_ops, nq, qubits, mats, &ops);
+#ifdef QSIM_PROBES
+  if (beam <= 0) if (const char* e = getenv("QSIM_PLAN_BEAM")) beam = atoi(e);
+#endif
+  std::vector<u64> masks;
+  int passes = 0;
+  rc = plan_search(n_local_qubits, ops, beam, &masks, &passes);
+  if (rc) return rc;
+  *n_passes = passes;
+  if (out_masks) {
+    if ((int)masks.size() > out_capacity) return fail(QSIM_ERR_INVALID, "qsim_plan_search: output buffer too small");
+    for (size_t p = 0; p < masks.size(); ++p) out_masks[p] = masks[p];
+  }
+  return QSIM_OK;
+}
+
 // The NEXT fused pass of a partly executed op list on a partitioned state (the partition planner's view of the pass builder,
 // runner/partition_plan.py): qubits are index bits of the WHOLE state, the bits >= n_local_qubits are rank bits -- an op may
 // use them as controls or phase bits (the rank applies or skips it by its own bits) but an op that TARGETS one has to wait

@@ -823,54 +823,33 @@ struct PeekPlan {
   uint64_t need_mask;          // out: ... of which the pass's ops need
   std::vector<size_t>* members;  // out: indices into ops_in
 };
-template <class Sink>
-static int plan_fused(int k, const std::vector<FusedOp>& ops_in, int* n_passes, Sink&& sink, const TileHint* hint = nullptr,
-                      PeekPlan* peek = nullptr) {
+
+// The op list a builder plans: the caller's, after the library-side fusion of commuting 1q gates (off by default).
+static std::vector<FusedOp> planned_ops(const std::vector<FusedOp>& ops_in) {
   const Tuning& tune = tuning();
   std::vector<FusedOp> ops = ops_in;
   if (tune.tile_commute_fuse == 1 || tune.tile_commute_fuse == 4) commute_fuse_1q(&ops, false);
   if (tune.tile_commute_fuse >= 2) commute_fuse_1q(&ops, true);
   if (tune.tile_commute_fuse == 3) commute_fuse_1q(&ops, false);
-  const int T = k < kTileBitsMax ? k : kTileBitsMax;
-  const int low = kTileLow;
-  const int cap = T - low;                      // tile high-bit capacity
-  const size_t n_ops = ops.size();
-  std::vector<char> done(n_ops, 0);
-  std::vector<u64> qm(n_ops), need(n_ops);     // all qubits of an op; its target bits above the low bits
-  std::vector<u64> tm(n_ops);                  // the qubits an op acts on NON-diagonally (its targets); qm & ~tm: controls, phase bits
-  std::vector<u64> xm(n_ops);                  // ... of those, the ones it acts on as 1 or X only (X, CNOT targets): X-diagonal
-  for (size_t i = 0; i < n_ops; ++i) {
-    qm[i] = op_qmask(ops[i]);
-    need[i] = 0;
-    tm[i] = xm[i] = 0;
-    for (int t = 0; t < ops[i].ntargets; ++t) {
-      tm[i] |= 1ull << ops[i].target[t];
-      if (ops[i].target[t] >= low) need[i] |= 1ull << ops[i].target[t];
-    }
-    if (ops[i].kind == TG_SWAP1 && tune.plan_commute >= 2) xm[i] = tm[i];
-    if (!tune.plan_commute) tm[i] = qm[i];     // (off: every qubit of a waiting op blocks everything on it)
-  }
-  // Two ops commute when each acts diagonally on every qubit they share (CNOTs with a common control, a phase gate on
-  // a control, CZ / CR among themselves ...) -- or, plan_commute >= 2, both as 1 / X (CNOTs with a common target, X on a
-  // CNOT target).  An op that has to wait therefore blocks its general TARGET qubits for everything, its diagonal
-  // qubits for ops that target them and its X-type targets for everything but X-type targets:
-  // `bt` = qubits blocked for all, `bd` = blocked for targets, `bx` = blocked for all but X-type targets.
-  auto admissible3 = [&](size_t i, u64 bt, u64 bd, u64 bx) {
-    return !(qm[i] & bt) && !(tm[i] & bd) && !((qm[i] & ~xm[i]) & bx);
-  };
-  const int n_bits = peek ? peek->n_total : k;
-  const u64 all_qubits = n_bits >= 64 ? ~0ull : ((1ull << n_bits) - 1);
-  const u64 rank_bits = all_qubits & ~(k >= 64 ? ~0ull : ((1ull << k) - 1));   // (peek mode only: no tile bit, no target)
-  const bool lookahead = tune.plan_lookahead >= 0 ? tune.plan_lookahead != 0 : k >= 24;
-  size_t remaining = n_ops;
-  size_t first = 0;
-  *n_passes = 0;
-  if (peek) {
-    remaining = 0;
-    for (size_t i = 0; i < n_ops; ++i) { done[i] = peek->done[i] != 0; remaining += !done[i]; }
-    peek->tile_mask = peek->need_mask = 0;
-    peek->members->clear();
-  }
+  return ops;
+}
+
+// The rules of pass building, one copy for the greedy builder (plan_fused) and the searching one (tile_search.h): which ops
+// a tile holds (`holds`), which tiles are worth trying (`candidates`, `grow`), what a tile costs in memory pattern
+// (`conflicts`) and what a pass on a tile really emits (`emit`).  The state is the done-set of the op list; `begin_pass`
+// brings the scan bounds up to date with it.
+struct PassBuilder {
+  const Tuning& tune;
+  const std::vector<FusedOp>& ops;
+  const int k, T, low, cap;                    // cap: tile high-bit capacity
+  const size_t n_ops;
+  std::vector<char> done;
+  std::vector<u64> qm, need;                   // all qubits of an op; its target bits above the low bits
+  std::vector<u64> tm;                         // the qubits an op acts on NON-diagonally (its targets); qm & ~tm: controls, phase bits
+  std::vector<u64> xm;                         // ... of those, the ones it acts on as 1 or X only (X, CNOT targets): X-diagonal
+  u64 all_qubits, rank_bits;                   // (rank bits: peek mode only: no tile bit, no target)
+  bool lookahead;
+  size_t remaining, first = 0;
   // How far behind `first` a pass looks for ops (counted in ops not yet done).  The scans below end early once every
   // qubit is blocked for everything (`bt`), which never happens while some qubit is used only as a control, phase bit or
   // X target (a GHZ root, a phase-estimation ancilla, an idle qubit): every scan then walked the whole remaining list --
@@ -879,9 +858,63 @@ static int plan_fused(int k, const std::vector<FusedOp>& ops_in, int* n_passes, 
   // by accident; it runs a pass later.  Lists shorter than the window (the bench circuits, QFT(33)) plan as before.
   // (byte-identical plans to the unbounded scan on the 28- / 30-qubit bench and Clifford+T circuits from 384 on; lists
   // of more than four windows use two thirds of it: 7.5 -> 1.4 ms per pass on a 4000-op list with a control-only qubit)
-  int scan_window = tune.plan_scan_window;
+  int scan_window;
+  // A pass is memory bound up to ~32 descriptors and pays ~0.03 ms for each one beyond that
+  // (tools/gate_cost_probe.py), so holding more than kSaturated ops buys nothing: a first-come pass
+  // that is already that full is kept (phase-heavy circuits: QFT).
+  static constexpr int kSaturated = 64;
+  bool tie_break;                              // plan_conflict_cost = -1: conflicts only break ties between tiles that hold the same number of ops
+  u64 jit_state;
+  u64 forced_static = 0;                       // (probe) bits that every tile holds
+  // Anchored tiles (tuning().plan_anchor = s > 0, evaluation knob of round 4): every tile after the first shares at
+  // least s of its high bits with the tile of the pass before it (`prev`): those s qubits can stay on the physical
+  // positions next to the line bits (2^(s+7)-byte contiguous pieces per tile, the fast DRAM pattern) while the pass's
+  // store permutes the tile's qubits among the tile's positions.  The carried bits are grown greedily from the
+  // previous tile (the bit that lets the pass hold the most ops, one at a time).
+  int anchor;
+
+  PassBuilder(int k_, const std::vector<FusedOp>& ops_, int n_bits)
+      : tune(tuning()), ops(ops_), k(k_), T(k_ < kTileBitsMax ? k_ : kTileBitsMax), low(kTileLow), cap(T - kTileLow),
+        n_ops(ops_.size()), done(ops_.size(), 0), qm(ops_.size()), need(ops_.size()), tm(ops_.size()), xm(ops_.size()) {
+    for (size_t i = 0; i < n_ops; ++i) {
+      qm[i] = op_qmask(ops[i]);
+      need[i] = 0;
+      tm[i] = xm[i] = 0;
+      for (int t = 0; t < ops[i].ntargets; ++t) {
+        tm[i] |= 1ull << ops[i].target[t];
+        if (ops[i].target[t] >= low) need[i] |= 1ull << ops[i].target[t];
+      }
+      if (ops[i].kind == TG_SWAP1 && tune.plan_commute >= 2) xm[i] = tm[i];
+      if (!tune.plan_commute) tm[i] = qm[i];     // (off: every qubit of a waiting op blocks everything on it)
+    }
+    all_qubits = n_bits >= 64 ? ~0ull : ((1ull << n_bits) - 1);
+    rank_bits = all_qubits & ~(k >= 64 ? ~0ull : ((1ull << k) - 1));
+    lookahead = tune.plan_lookahead >= 0 ? tune.plan_lookahead != 0 : k >= 24;
+    remaining = n_ops;
+    scan_window = tune.plan_scan_window;
+    tie_break = tune.plan_conflict_cost < 0;
+    jit_state = 0x9E3779B97F4A7C15ull * (u64)(tune.plan_jitter + 1);
+    for (int b = low; b < low + tune.plan_force_low && b < k && __builtin_popcountll(forced_static) < cap; ++b) forced_static |= 1ull << b;
+    anchor = tune.plan_anchor;
+  }
+
+  // Two ops commute when each acts diagonally on every qubit they share (CNOTs with a common control, a phase gate on
+  // a control, CZ / CR among themselves ...) -- or, plan_commute >= 2, both as 1 / X (CNOTs with a common target, X on a
+  // CNOT target).  An op that has to wait therefore blocks its general TARGET qubits for everything, its diagonal
+  // qubits for ops that target them and its X-type targets for everything but X-type targets:
+  // `bt` = qubits blocked for all, `bd` = blocked for targets, `bx` = blocked for all but X-type targets.
+  bool admissible3(size_t i, u64 bt, u64 bd, u64 bx) const {
+    return !(qm[i] & bt) && !(tm[i] & bd) && !((qm[i] & ~xm[i]) & bx);
+  }
+
+  // the scan bounds of the next pass, from the done-set
+  void begin_pass() {
+    while (first < n_ops && done[first]) ++first;
+    scan_window = remaining > 4 * (size_t)tune.plan_scan_window ? std::max(1, tune.plan_scan_window * 2 / 3) : tune.plan_scan_window;
+  }
+
   // ops a pass with the given high bits would hold (optionally listed)
-  auto holds = [&](u64 tile_mask, std::vector<size_t>* out) -> int {
+  int holds(u64 tile_mask, std::vector<size_t>* out) const {
     u64 bt = 0, bd = 0, bx = 0;
     int count = 0, seen = 0;
     for (size_t i = first; i < n_ops && count < tune.max_gates_per_pass; ++i) {
@@ -898,44 +931,65 @@ static int plan_fused(int k, const std::vector<FusedOp>& ops_in, int* n_passes, 
       if (out) out->push_back(i);
     }
     return count;
-  };
-  // A pass is memory bound up to ~32 descriptors and pays ~0.03 ms for each one beyond that
-  // (tools/gate_cost_probe.py), so holding more than kSaturated ops buys nothing: a first-come pass
-  // that is already that full is kept (phase-heavy circuits: QFT).
-  constexpr int kSaturated = 64;
+  }
   // Memory pattern of a tile (profiles/r02z_tile_bits_samples.txt, 2500 gate-less passes): index bits b and b + 7
   // with b = 13..16 in ONE tile cost +0.13-0.17 ms each at 28 qubits (+9 %; byte-address bits 17-20 select the
   // bank, 24-27 are row bits folded into it: both varying inside a tile puts two rows on one bank), bits 18 / 26 and
   // 19 / 27 half of that.  Counted in units of ops a pass holds (tuning().plan_conflict_cost each).
-  auto conflicts = [&](u64 mask) -> int {
+  static int conflicts(u64 mask) {
     int c = 0;
     for (int b = 13; b <= 16; ++b) c += 2 * (int)(((mask >> b) & (mask >> (b + 7)) & 1));
     for (int b = 18; b <= 19; ++b) c += (int)(((mask >> b) & (mask >> (b + 8)) & 1));
     return c;
-  };
-  auto penalty = [&](u64 mask) -> int { return tune.plan_conflict_cost > 0 ? tune.plan_conflict_cost * conflicts(mask) / 2 : 0; };
-  // plan_conflict_cost = -1: conflicts only break ties between tiles that hold the same number of ops
-  const bool tie_break = tune.plan_conflict_cost < 0;
+  }
+  int penalty(u64 mask) const { return tune.plan_conflict_cost > 0 ? tune.plan_conflict_cost * conflicts(mask) / 2 : 0; }
   // (the fitted per-bit + pair model of the same samples as the tie-break instead of the conflict count: 159 instead of
   // 155 passes over 8 circuits, +2.3 % time -- breaking every tie perturbs the greedy growth more than it saves)
-  u64 jit_state = 0x9E3779B97F4A7C15ull * (u64)(tune.plan_jitter + 1);
-  auto jitter = [&]() -> unsigned { jit_state ^= jit_state << 13; jit_state ^= jit_state >> 7; jit_state ^= jit_state << 17; return (unsigned)(jit_state >> 33); };
-  auto keyed = [&](int count, u64 mask) -> int {
+  unsigned jitter() { jit_state ^= jit_state << 13; jit_state ^= jit_state >> 7; jit_state ^= jit_state << 17; return (unsigned)(jit_state >> 33); }
+  int keyed(int count, u64 mask) {
     if (tune.plan_jitter > 0) return (count - (int)(jitter() % 8 == 0) - (int)(jitter() % 16 == 0)) * 64 + (int)(jitter() % 64);
     return tie_break ? count * 64 - conflicts(mask) : count;
-  };
-  auto mask_of = [](const std::vector<int>& bits, size_t n) { u64 m = 0; for (size_t i = 0; i < n && i < bits.size(); ++i) m |= 1ull << bits[i]; return m; };
+  }
+  static u64 mask_of(const std::vector<int>& bits, size_t n) { u64 m = 0; for (size_t i = 0; i < n && i < bits.size(); ++i) m |= 1ull << bits[i]; return m; }
+
+  // look-ahead growth of a tile: add the bit that lets the pass hold the most ops, one at a time, up to a whole tile
+  u64 grow(u64 mask) {
+    while (__builtin_popcountll(mask) < cap) {
+      int pick = -1, pick_count = -(1 << 20);
+      for (int b = low; b < k; ++b) {
+        if ((mask >> b) & 1) continue;
+        const int c = keyed(holds(mask | (1ull << b), nullptr) - penalty(mask | (1ull << b)), mask | (1ull << b));
+        if (c > pick_count) { pick_count = c; pick = b; }
+      }
+      if (pick < 0) break;
+      mask |= 1ull << pick;
+    }
+    return mask;
+  }
+
+  // first come: an op that still fits claims the bits it needs (`claimed`: in that order); returns the tile
+  u64 first_come(u64 forced, std::vector<int>* claimed) const {
+    const int n_forced = __builtin_popcountll(forced);
+    u64 bt = 0, bd = 0, bx = 0, mask = forced;
+    int count = 0, seen = 0;
+    for (size_t i = first; i < n_ops && count < tune.max_gates_per_pass; ++i) {
+      if (done[i]) continue;
+      if (++seen > scan_window) break;
+      bool ok = admissible3(i, bt, bd, bx);
+      const u64 extra = need[i] & ~mask;
+      if (ok && (n_forced + (int)claimed->size() + __builtin_popcountll(extra) > cap || (extra & rank_bits))) ok = false;
+      if (!ok) { bt |= tm[i] & ~xm[i]; bx |= xm[i]; bd |= qm[i] & ~tm[i]; if (bt == all_qubits) break; continue; }
+      for (u64 e = extra; e; e &= e - 1) claimed->push_back(__builtin_ctzll(e));
+      mask |= extra;
+      ++count;
+    }
+    return mask;
+  }
+
   // candidate tiles for the next pass from the current `done` / `first`: [0] = first come, then the
-  // look-ahead ones grown from the first `seed` claimed bits
-  u64 forced_static = 0;                        // (probe) bits that every tile holds
-  for (int b = low; b < low + tune.plan_force_low && b < k && __builtin_popcountll(forced_static) < cap; ++b) forced_static |= 1ull << b;
-  // Anchored tiles (tuning().plan_anchor = s > 0, evaluation knob of round 4): every tile after the first shares at
-  // least s of its high bits with the tile of the pass before it (`prev`): those s qubits can stay on the physical
-  // positions next to the line bits (2^(s+7)-byte contiguous pieces per tile, the fast DRAM pattern) while the pass's
-  // store permutes the tile's qubits among the tile's positions.  The carried bits are grown greedily from the
-  // previous tile (the bit that lets the pass hold the most ops, one at a time).
-  const int anchor = tune.plan_anchor;
-  auto candidates = [&](std::vector<u64>* out, size_t max_seed, size_t seed_step, u64 prev) {
+  // look-ahead ones grown from the first `seed` claimed bits (`always`: also where the greedy builder does without
+  // the look-ahead, small states)
+  void candidates(std::vector<u64>* out, size_t max_seed, size_t seed_step, u64 prev, bool always = false) {
     u64 forced = forced_static;
     if (anchor > 0 && prev) {
       for (int picked = 0; picked < anchor && picked < cap; ++picked) {
@@ -949,88 +1003,118 @@ static int plan_fused(int k, const std::vector<FusedOp>& ops_in, int* n_passes, 
         forced |= 1ull << pick;
       }
     }
-    const int n_forced = __builtin_popcountll(forced);
     std::vector<int> claimed;                   // high bits in the order they were claimed
-    {
-      u64 bt = 0, bd = 0, bx = 0, mask = forced;
-      int count = 0, seen = 0;
-      for (size_t i = first; i < n_ops && count < tune.max_gates_per_pass; ++i) {
-        if (done[i]) continue;
-        if (++seen > scan_window) break;
-        bool ok = admissible3(i, bt, bd, bx);
-        const u64 extra = need[i] & ~mask;
-        if (ok && (n_forced + (int)claimed.size() + __builtin_popcountll(extra) > cap || (extra & rank_bits))) ok = false;
-        if (!ok) { bt |= tm[i] & ~xm[i]; bx |= xm[i]; bd |= qm[i] & ~tm[i]; if (bt == all_qubits) break; continue; }
-        for (u64 e = extra; e; e &= e - 1) claimed.push_back(__builtin_ctzll(e));
-        mask |= extra;
-        ++count;
-      }
-    }
+    first_come(forced, &claimed);
     out->clear();
     out->push_back(forced | mask_of(claimed, claimed.size()));
-    if (!(lookahead && k - low > cap) || holds(out->front(), nullptr) >= kSaturated) return;
-    for (size_t seed = 0; seed <= max_seed && seed <= claimed.size(); seed += seed_step) {
-      u64 mask = forced | mask_of(claimed, seed);
-      while (__builtin_popcountll(mask) < cap) {
-        int pick = -1, pick_count = -(1 << 20);
-        for (int b = low; b < k; ++b) {
-          if ((mask >> b) & 1) continue;
-          const int c = keyed(holds(mask | (1ull << b), nullptr) - penalty(mask | (1ull << b)), mask | (1ull << b));
-          if (c > pick_count) { pick_count = c; pick = b; }
-        }
-        if (pick < 0) break;
-        mask |= 1ull << pick;
+    if (!((lookahead || always) && k - low > cap) || holds(out->front(), nullptr) >= kSaturated) return;
+    for (size_t seed = 0; seed <= max_seed && seed <= claimed.size(); seed += seed_step)
+      out->push_back(grow(forced | mask_of(claimed, seed)));
+  }
+
+  // the high bits of a tile mask, filled with the lowest unused bits so the tile always has T bits (bits 3.. conflict
+  // with nothing), ascending
+  std::vector<int> filled(std::vector<int> high) const {
+    for (int b = low; (int)high.size() < cap && b < k; ++b)
+      if (std::find(high.begin(), high.end(), b) == high.end()) high.push_back(b);
+    std::sort(high.begin(), high.end());
+    return high;
+  }
+  std::vector<int> bits_of(u64 mask) const {
+    std::vector<int> high;
+    for (int b = low; b < k; ++b) if ((mask >> b) & 1) high.push_back(b);
+    return high;
+  }
+
+  // The register groups of one pass: `members` on the tile `high`; emitted[mi]: member mi got its records (the others did
+  // not fit the record budget and wait for the next pass).
+  void emit(const std::vector<size_t>& members, const std::vector<int>& high, std::vector<TileGroup>* groups, std::vector<char>* emitted) const {
+    emitted->assign(members.size(), 0);
+    emit_groups(ops, members, high, T, groups, emitted);
+    if (lookahead && tune.tile_direct && tune.tile_last_search && T == kTileBitsMax) {
+      // second plan of the same pass with the last group chosen from the end (see emit_groups); LDS round trips of a
+      // tile = group changes + a first group that is not loaded in place + a last group that is not stored in place
+      auto trips = [&](const std::vector<TileGroup>& g) {
+        return g.empty() ? 1 << 20 : (int)g.size() + (g.front().s[0] < kTileLow) + (g.back().s[0] < kTileLow);
+      };
+      auto count = [](const std::vector<char>& e) { size_t c = 0; for (char x : e) c += x != 0; return c; };
+      std::vector<char> emitted2(members.size(), 0);
+      std::vector<TileGroup> groups2;
+      emit_groups(ops, members, high, T, &groups2, &emitted2, true);
+      if (count(emitted2) > count(*emitted) || (count(emitted2) == count(*emitted) && trips(groups2) < trips(*groups))) {
+        groups->swap(groups2);
+        emitted->swap(emitted2);
       }
-      out->push_back(mask);
+      // (four more variants -- the first group's preference for a direct triple off / stronger, each with and without the
+      // last-group search -- save one more round trip in 84 on the bench circuit: not worth three times the planning)
     }
-  };
+  }
+};
+
+template <class Sink>
+static int plan_fused(int k, const std::vector<FusedOp>& ops_in, int* n_passes, Sink&& sink, const TileHint* hint = nullptr,
+                      PeekPlan* peek = nullptr) {
+  const Tuning& tune = tuning();
+  const std::vector<FusedOp> ops = planned_ops(ops_in);
+  PassBuilder pb(k, ops, peek ? peek->n_total : k);
+  const int T = pb.T, low = pb.low, cap = pb.cap;
+  const size_t n_ops = pb.n_ops;
+  std::vector<char>& done = pb.done;
+  size_t& remaining = pb.remaining;
+  size_t& first = pb.first;
+  constexpr int kSaturated = PassBuilder::kSaturated;
+  *n_passes = 0;
+  if (peek) {
+    remaining = 0;
+    for (size_t i = 0; i < n_ops; ++i) { done[i] = peek->done[i] != 0; remaining += !done[i]; }
+    peek->tile_mask = peek->need_mask = 0;
+    peek->members->clear();
+  }
   const bool depth2 = tune.plan_lookahead >= 0 ? tune.plan_lookahead >= 2 : k >= 26;
   std::vector<u64> cands, cands2;
   std::vector<size_t> trial;
   u64 prev_mask = 0;                            // high bits of the pass before (anchored tiles)
   while (remaining) {
-    while (first < n_ops && done[first]) ++first;
-    scan_window = remaining > 4 * (size_t)tune.plan_scan_window ? std::max(1, tune.plan_scan_window * 2 / 3) : tune.plan_scan_window;
+    pb.begin_pass();
     u64 best_mask = 0;
     bool hinted = false;
     if (hint && *n_passes < hint->n) {
-      const u64 m = hint->masks[*n_passes] & all_qubits & ~((1ull << low) - 1);
-      if (m && __builtin_popcountll(m) <= cap && holds(m, nullptr) > 0) { best_mask = m; hinted = true; }
+      const u64 m = hint->masks[*n_passes] & pb.all_qubits & ~((1ull << low) - 1);
+      if (m && __builtin_popcountll(m) <= cap && pb.holds(m, nullptr) > 0) { best_mask = m; hinted = true; }
     }
     if (!hinted) {
-    candidates(&cands, 6, 2, prev_mask);
+    pb.candidates(&cands, 6, 2, prev_mask);
     best_mask = cands[0];
     int best_score = -(1 << 20);
     for (size_t ci = 0; ci < cands.size(); ++ci) {
       trial.clear();
-      int score = std::min(holds(cands[ci], &trial), kSaturated) - penalty(cands[ci]);
+      int score = std::min(pb.holds(cands[ci], &trial), kSaturated) - pb.penalty(cands[ci]);
       if (depth2 && cands.size() > 1 && trial.size() < remaining) {
         // what the pass AFTER this one could hold (a smaller candidate set)
         const size_t first_saved = first;
         for (size_t i : trial) done[i] = 1;
         while (first < n_ops && done[first]) ++first;
-        candidates(&cands2, 4, 4, cands[ci]);
+        pb.candidates(&cands2, 4, 4, cands[ci]);
         int next_best = 0;
-        for (u64 m2 : cands2) next_best = std::max(next_best, std::min(holds(m2, nullptr), kSaturated) - penalty(m2));
+        for (u64 m2 : cands2) next_best = std::max(next_best, std::min(pb.holds(m2, nullptr), kSaturated) - pb.penalty(m2));
         for (size_t i : trial) done[i] = 0;
         first = first_saved;
         score += next_best;
       } else if (depth2 && trial.size() >= remaining) {
         score += 2 * kSaturated;                // finishes the list
       }
-      score = keyed(score, cands[ci]);
+      score = pb.keyed(score, cands[ci]);
       if (score > best_score) { best_score = score; best_mask = cands[ci]; }
     }
     }
-    std::vector<int> high;                      // chosen high bits
-    for (int b = low; b < k; ++b) if ((best_mask >> b) & 1) high.push_back(b);
+    std::vector<int> high = pb.bits_of(best_mask);   // chosen high bits
     std::vector<size_t> members;
-    holds(best_mask, &members);
+    pb.holds(best_mask, &members);
     if (peek) {
       // (everything that is left may be waiting for a rank bit: an empty pass is an answer here, not an error)
       if (members.empty()) { *n_passes = 0; return QSIM_OK; }
       u64 needed = 0;
-      for (size_t i : members) needed |= need[i];
+      for (size_t i : members) needed |= pb.need[i];
       std::vector<int> kept;
       for (int b : high) if ((needed >> b) & 1) kept.push_back(b);
       for (int b = low; (int)kept.size() < cap && b < k; ++b)                        // the fill: not the bits to avoid
@@ -1039,10 +1123,7 @@ static int plan_fused(int k, const std::vector<FusedOp>& ops_in, int* n_passes, 
       peek->need_mask = needed;
     }
     if (members.empty()) return fail(QSIM_ERR_INVALID, "internal: fused planner made no progress");
-    // fill the tile with the lowest unused bits so it always has T bits
-    for (int b = low; (int)high.size() < cap && b < k; ++b)
-      if (std::find(high.begin(), high.end(), b) == high.end()) high.push_back(b);   // (bits 3.. conflict with nothing)
-    std::sort(high.begin(), high.end());
+    high = pb.filled(high);
     prev_mask = 0;
     for (int b : high) prev_mask |= 1ull << b;
 #ifdef QSIM_PROBES
@@ -1060,26 +1141,9 @@ static int plan_fused(int k, const std::vector<FusedOp>& ops_in, int* n_passes, 
     std::memset(&a, 0, sizeof a);
     a.T = T;
     for (size_t j = 0; j < high.size(); ++j) a.h[j] = (uint8_t)high[j];
-    std::vector<char> emitted(members.size(), 0);
+    std::vector<char> emitted;
     std::vector<TileGroup> groups;
-    emit_groups(ops, members, high, T, &groups, &emitted);
-    if (lookahead && tune.tile_direct && tune.tile_last_search && T == kTileBitsMax) {
-      // second plan of the same pass with the last group chosen from the end (see emit_groups); LDS round trips of a
-      // tile = group changes + a first group that is not loaded in place + a last group that is not stored in place
-      auto trips = [&](const std::vector<TileGroup>& g) {
-        return g.empty() ? 1 << 20 : (int)g.size() + (g.front().s[0] < kTileLow) + (g.back().s[0] < kTileLow);
-      };
-      auto count = [](const std::vector<char>& e) { size_t c = 0; for (char x : e) c += x != 0; return c; };
-      std::vector<char> emitted2(members.size(), 0);
-      std::vector<TileGroup> groups2;
-      emit_groups(ops, members, high, T, &groups2, &emitted2, true);
-      if (count(emitted2) > count(emitted) || (count(emitted2) == count(emitted) && trips(groups2) < trips(groups))) {
-        groups.swap(groups2);
-        emitted.swap(emitted2);
-      }
-      // (four more variants -- the first group's preference for a direct triple off / stronger, each with and without the
-      // last-group search -- save one more round trip in 84 on the bench circuit: not worth three times the planning)
-    }
+    pb.emit(members, high, &groups, &emitted);
     size_t n_emitted = 0;
     double alg_bytes = 0;   // dense 32N, diagonal / controlled / SWAP 16N, CZ/CR 8N
     for (size_t mi = 0; mi < members.size(); ++mi)

@@ -38,21 +38,23 @@ class SingleGpuEngine:
 
     layout = "auto" (fused mode, states of >= 26 qubits, plans made for >= 8 executions) / "search" (always): `plan`
     decides which index bit every logical qubit lives on --
-      * the three qubits on the LINE bits 0..2 belong to every tile, so which three they are changes how many passes the
-        greedy pass builder needs (17-20 for the 28-qubit bench circuit): a few dozen random choices are planned on the
-        host in parallel (`qsim_plan_count_layouts`) and the cheapest kept;
+      * the three qubits on the LINE bits 0..2 belong to every tile, so which three they are changes how many passes a
+        plan needs (16-18 for the 28-qubit bench circuit under the searching pass builder, `qsim_plan_search`; the
+        greedy builder of one-shot calls needs 17-20): a few dozen random triples are searched on the host in parallel
+        and the cheapest kept;
       * the other qubits are placed so that the passes' tiles fall on index-bit sets with a good DRAM pattern
         (runner/tile_layout.py: a cost model fitted to measured passes, annealed by `qsim_choose_layout`) --
     and hands the SAME passes to the library on the new bits (`qsim_apply_ops_tiled`).  The state is then held in that
     layout -- the reference's `log_to_phys` notion (staging.py:587-658) -- and `state_vector()` / `logical_index()` undo
-    it.  About a second of host work per plan, outside every timed region: worth it for plans that run many times.
+    it.  A few seconds of host work per plan, outside every timed region: worth it for plans that run many times.
     layout = "identity": index bit = qubit, no search."""
 
     world = 1
     rank = 0
     LAYOUT_MIN_QUBITS = 26
     LAYOUT_MIN_REPEATS = 8         # layout = "auto": plans for fewer executions are not worth a second of search
-    LAYOUT_CANDIDATES = 384        # random relabellings (a quarter of them: only the three line-bit qubits) that are planned and counted
+    LAYOUT_CANDIDATES = 31         # random line-qubit triples (next to the identity) whose plans are searched
+    LAYOUT_BEAM = 0                # beam width of the pass search (0: the library's default)
     LAYOUT_FINALISTS = 8           # minimum-pass layouts timed on the device (tune_on_device, |0..0> state only)
 
     def __init__(self, n_qubits: int, device: int = 0, mode: str = "fused", layout: str = "auto", tune_on_device: bool = False):
@@ -123,7 +125,7 @@ class SingleGpuEngine:
         t0 = time.perf_counter()
         tune = self.tune_on_device and self._zero            # (timing runs overwrite the state: only |0..0> can be put back)
         finalists = choose_plan_layout(self.n, batches, self.LAYOUT_CANDIDATES, n_finalists=self.LAYOUT_FINALISTS if tune else 4,
-                                       all_finalists=True)
+                                       all_finalists=True, beam=self.LAYOUT_BEAM)
 
         def build(l2p, masks, info):
             plan = GpuPlan([pack_ops([([l2p[q] for q in qs], U) for qs, U in ops]) for ops in batches])
@@ -390,42 +392,97 @@ def _count_passes(n: int, batches, layouts: np.ndarray, threads: int) -> np.ndar
     return total
 
 
-def choose_plan_layout(n: int, batches, n_candidates: int = 384, seed: int = 20260504, n_finalists: int = 4,
-                       all_finalists: bool = False):
-    """(l2p, tile masks per batch on the chosen index bits, info) for the op lists `batches` (logical qubits): the line-bit
-    qubits that need the fewest passes among `n_candidates` random choices (the identity included), then the other
-    qubits placed by the tile-cost model (runner/tile_layout.py).  Host only.  all_finalists: the list of up to
-    n_finalists minimum-pass layouts, best model cost first (the engine may time them on the device)."""
-    import os
+def _search_tiles(n: int, ops, beam: int) -> np.ndarray:
+    """The tiles (one uint64 mask of high tile bits per pass) of the library's searching pass builder for `ops` on n qubits
+    (qsim_plan_search: a beam search over the passes' tiles, host only; never more passes than qsim_plan_ops)."""
+    import ctypes as C
 
+    from quantum_simulations_amd import _lib
+    from quantum_simulations_amd.kernel.device import pack_ops
+    nq, qubits, mats = pack_ops(ops)
+    if len(nq) < 2:
+        return np.zeros(0, dtype=np.uint64)
+    lib = _lib.load()
+    count = C.c_int32()
+    out = np.zeros(len(nq), dtype=np.uint64)
+    _lib.check(lib.qsim_plan_search(n, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p),
+                                    mats.ctypes.data_as(C.c_void_p), beam, out.ctypes.data_as(C.c_void_p), len(out), C.byref(count)))
+    return out[:count.value].copy()
+
+
+def _tiled_pass_count(n: int, ops, masks) -> int:
+    """Passes the library makes of `ops` when handed the tiles `masks` (qsim_plan_ops_tiled, host only)."""
+    import ctypes as C
+
+    from quantum_simulations_amd import _lib
+    from quantum_simulations_amd.kernel.device import pack_ops
+    nq, qubits, mats = pack_ops(ops)
+    count = C.c_int32()
+    ms = np.ascontiguousarray(masks, dtype=np.uint64)
+    _lib.check(_lib.load().qsim_plan_ops_tiled(n, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p),
+                                               mats.ctypes.data_as(C.c_void_p), len(ms), ms.ctypes.data_as(C.c_void_p), None, 0,
+                                               C.byref(count)))
+    return count.value
+
+
+def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 20260504, n_finalists: int = 4,
+                       all_finalists: bool = False, beam: int = 0):
+    """(l2p, tile masks per batch on the chosen index bits, info) for the op lists `batches` (logical qubits).  The three
+    qubits on the line bits belong to every tile, so they decide how many passes a plan needs; which index bits the OTHER
+    qubits live on does not (a relabelling of the bits >= 3 maps every valid pass sequence to a valid one).  So: for the
+    identity and `n_candidates` random line-qubit triples the library's searching pass builder (qsim_plan_search, beam
+    width `beam`, 0 = its default) plans the batches, in parallel on the host; the triples that need the fewest passes
+    are kept and their other qubits placed by the tile-cost model (runner/tile_layout.py).  Host only.  all_finalists: the
+    list of up to n_finalists minimum-pass layouts, best model cost first (the engine may time them on the device)."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+
+    from quantum_simulations_amd import _lib
     from quantum_simulations_amd.runner import tile_layout
     rng = np.random.default_rng(seed)
     layouts = np.tile(np.arange(n, dtype=np.int32), (n_candidates + 1, 1))
-    for i, row in enumerate(layouts[1:]):
-        if i % 4 == 0:                                      # a quarter: only the three line-bit qubits change
-            for bit, q in enumerate(int(x) for x in rng.choice(n, size=3, replace=False)):
-                j = int(np.flatnonzero(row == bit)[0])      # the qubit on `bit` trades places with q
-                row[j], row[q] = row[q], bit
-        else:                                               # the rest: every qubit somewhere else (the greedy builder's
-            row[:] = rng.permutation(n)                     # tie-breaks walk the bits in order: other labels, other plans)
+    for row in layouts[1:]:
+        for bit, q in enumerate(int(x) for x in rng.choice(n, size=3, replace=False)):
+            j = int(np.flatnonzero(row == bit)[0])          # the qubit on `bit` trades places with q
+            row[j], row[q] = row[q], bit
     try:
         threads = len(os.sched_getaffinity(0))
     except AttributeError:
         threads = os.cpu_count() or 1
-    counts = _count_passes(n, batches, layouts, max(1, min(16, threads)))
+    threads = max(1, min(16, threads))
+    _lib.load()
+
+    def relabelled(lay):
+        return [[([int(lay[q]) for q in qs], U) for qs, U in ops] for ops in batches]
+
+    def search(lay):                                        # (the library call releases the interpreter lock)
+        return [_search_tiles(n, ops, beam) for ops in relabelled(lay)]
+    with ThreadPoolExecutor(threads) as pool:
+        found = list(pool.map(search, layouts))
+    short = sum(len(ops) for ops in batches if len(ops) < 2)                    # (a single op is not searched: one pass)
+    counts = np.array([short + sum(len(ms) for ms in f) for f in found], dtype=np.int64)
     best = int(counts.min())
     finalists = [int(i) for i in np.flatnonzero(counts == best)][:max(1, n_finalists)]   # (the identity first when it ties)
+    greedy_identity = int(_count_passes(n, batches, layouts[:1], 1)[0])
     out = []
     for f in finalists:
         first = [int(x) for x in layouts[f]]
-        moved = [[([first[q] for q in qs], U) for qs, U in ops] for ops in batches]
-        masks = [_planned_tile_masks(n, ops) for ops in moved]
+        moved = relabelled(first)
+        masks = found[f]
         tiles = [[b for b in range(tile_layout.LOW, n) if (int(m) >> b) & 1] for ms in masks for m in ms]
         second, cost0, cost1 = min((tile_layout.choose_layout(tiles, n, seed=s) for s in range(1, 9)), key=lambda r: r[2])
-        l2p = [second[first[q]] for q in range(n)]
         final_masks = [np.array([sum(1 << second[b] for b in range(n) if (int(m) >> b) & 1) for m in ms], dtype=np.uint64) for ms in masks]
-        info = {"passes_identity": int(counts[0]), "passes_chosen": best, "candidates": n_candidates + 1,
+        # The pass count does not depend on the placement, but the records of a pass are written in the order of its tile
+        # bits, and a pass at the edge of its record budget may hold one op fewer in another order: a placement that would
+        # grow the plan at execution time is dropped for the one the search ran on.
+        replanned = sum(_tiled_pass_count(n, [([second[b] for b in qs], U) for qs, U in ops], ms) if len(ops) >= 2 else len(ops)
+                        for ops, ms in zip(moved, final_masks))
+        if replanned != best:
+            second, final_masks, cost1 = list(range(n)), [np.array(ms, dtype=np.uint64) for ms in masks], cost0
+        l2p = [second[first[q]] for q in range(n)]
+        info = {"passes_identity": greedy_identity, "passes_chosen": best, "candidates": n_candidates + 1,
                 "candidates_by_passes": {int(c): int((counts == c).sum()) for c in np.unique(counts)},
+                "passes_identity_searched": int(counts[0]), "beam": int(beam) if beam > 0 else "default",
                 "model_ms": (round(cost0, 3), round(cost1, 3))}
         out.append((l2p, final_masks, info))
     out.sort(key=lambda r: r[2]["model_ms"][1])
