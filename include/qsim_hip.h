@@ -369,6 +369,23 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
  * A bit >= n_local_qubits in x fails with QSIM_ERR_NONLOCAL. */
 int qsim_plan_expectation(int n_local_qubits, int n_terms, const uint64_t* x_masks, int32_t* pass_of_term,
                           uint64_t* tile_masks, int* n_passes);
+/* Shot sampling of the full register: n_shots samples of the chunk-local index from |amp|^2 / total.  randnums[s] in
+ * [0, 1) is the caller's uniform for shot s (the caller owns the generator); out_indices[s] is the smallest i with
+ * cdf(i) > randnums[s] * total in the device's fixed summation order; results come back in the order of randnums.  An
+ * index with |amp|^2 = 0 is never returned.  *total = sum |amp|^2.  Two read-only passes, no atomics, two calls give the
+ * same bits: pass A sums |amp|^2 over blocks of 2^qsim_sample_block_bits() contiguous amplitudes (one read of the chunk),
+ * the host scans the block sums and finds every shot's block (qsim_sample_locate), pass B reads each hit block once more
+ * and walks its shots down the block's summation tree, the tree pass A summed it with.  *n_passes: 1 + 1 if pass B ran
+ * (n_shots == 0: 0, nothing launched, *total = 0).  n_shots > 2^24, a randnum outside [0, 1) or NaN, a null argument
+ * and total == 0 fail with QSIM_ERR_INVALID.  Blocks until out_indices is written. */
+int qsim_sample(qsim_chunk* c, uint64_t n_shots, const double* randnums, uint64_t* out_indices, double* total, int* n_passes);
+/* The host part of qsim_sample as a pure function (no GPU): from the inclusive block prefix block_cdf[n_blocks] and
+ * n_shots randnums, per shot the block (the smallest b with block_cdf[b] > randnums[s] * block_cdf[last]) and the local
+ * threshold randnums[s] * block_cdf[last] - block_cdf[b - 1].  Zero-weight blocks are never chosen; a threshold at or
+ * above block_cdf[last] goes to the last block with weight. */
+int qsim_sample_locate(uint64_t n_blocks, const double* block_cdf, uint64_t n_shots, const double* randnums,
+                       uint64_t* out_block, double* out_local);
+int qsim_sample_block_bits(void);   /* log2 of the block length of qsim_sample, for tests and hosts */
 /* max_i |amp_i - expected_i| for closed-form states, evaluated on the device:
  * kind 0: GHZ (1/sqrt2 at local index 0 of the first chunk and at the last index of the
  *         last), kind 1: GHZ+QFT  2^-(n+1)/2 (1 + exp(-2 pi i y / 2^n)), y = base + i.  */

@@ -65,6 +65,7 @@ int qsim_destroy(qsim_chunk* c) {
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->hist) (void)hipFree(c->hist);
   if (c->expect) (void)hipFree(c->expect);
+  if (c->sample) (void)hipFree(c->sample);
   delete c->pending;
   delete c->deferred;
   if (c->owns_memory && c->amp) {

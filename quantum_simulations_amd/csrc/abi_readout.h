@@ -226,6 +226,94 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
   return QSIM_OK;
 }
 
+// Shot sampling (sample_kernels.h): pass A (block sums), the block prefix and the shots' blocks on the host, the shots
+// grouped by block, pass B (one workgroup per hit block), the indices back in the order of randnums.
+int qsim_sample_block_bits(void) { return kSampleBlockBits; }
+
+int qsim_sample_locate(uint64_t n_blocks, const double* block_cdf, uint64_t n_shots, const double* randnums,
+                       uint64_t* out_block, double* out_local) {
+  if (!n_blocks || !block_cdf || (n_shots && (!randnums || !out_block || !out_local)))
+    return fail(QSIM_ERR_INVALID, "qsim_sample_locate: null argument or no blocks");
+  if (!(block_cdf[n_blocks - 1] > 0.0) || !std::isfinite(block_cdf[n_blocks - 1]))
+    return fail(QSIM_ERR_INVALID, "qsim_sample_locate: the total weight is %g (a positive finite number expected)", block_cdf[n_blocks - 1]);
+  for (u64 s = 0; s < n_shots; ++s)
+    if (!sample_randnum_ok(randnums[s]))
+      return fail(QSIM_ERR_INVALID, "qsim_sample_locate: randnums[%llu] = %g is outside [0, 1)", (u64)s, randnums[s]);
+  sample_locate(n_blocks, block_cdf, n_shots, randnums, out_block, out_local);
+  return QSIM_OK;
+}
+
+int qsim_sample(qsim_chunk* c, uint64_t n_shots, const double* randnums, uint64_t* out_indices, double* total, int* n_passes) {
+  int rc = check_chunk(c, "qsim_sample");
+  if (rc) return rc;
+  if (!total || !n_passes || (n_shots && (!randnums || !out_indices))) return fail(QSIM_ERR_INVALID, "qsim_sample: null argument");
+  if (n_shots > kSampleMaxShots) return fail(QSIM_ERR_INVALID, "qsim_sample: %llu shots in one call, at most 2^24", (u64)n_shots);
+  if ((rc = require_no_parts(c, "qsim_sample"))) return rc;
+  for (u64 s = 0; s < n_shots; ++s)
+    if (!sample_randnum_ok(randnums[s]))
+      return fail(QSIM_ERR_INVALID, "qsim_sample: randnums[%llu] = %g is outside [0, 1)", (u64)s, randnums[s]);
+  *total = 0.0;
+  *n_passes = 0;
+  if (!n_shots) return QSIM_OK;
+  const u64 n = amps(c), n_blocks = std::max<u64>(n >> kSampleBlockBits, 1);
+  // device scratch: block sums | shot slots | hit blocks | first shot of every hit block (+ 1)
+  const u64 slot_off = sizeof(double) * n_blocks, hit_off = slot_off + sizeof(u64) * n_shots;
+  const u64 first_off = hit_off + sizeof(u64) * n_shots;
+  if ((rc = ensure_sample(c, first_off + sizeof(unsigned) * (n_shots + 1)))) return rc;
+  char* base = static_cast<char*>(c->sample);
+  double* dev_sums = reinterpret_cast<double*>(base);
+  u64* dev_slot = reinterpret_cast<u64*>(base + slot_off);
+  u64* dev_hit = reinterpret_cast<u64*>(base + hit_off);
+  unsigned* dev_first = reinterpret_cast<unsigned*>(base + first_off);
+  HIP_TRY(hipSetDevice(c->device));
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  {
+    ProfileScope prof(9, 16.0 * (double)n, c->stream, nt);
+    if (nt) hipLaunchKernelGGL((k_sample_block_sums<true>), grid_for(n_blocks), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, dev_sums);
+    else hipLaunchKernelGGL((k_sample_block_sums<false>), grid_for(n_blocks), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, dev_sums);
+    HIP_TRY(hipGetLastError());
+    prof.done(c->stream);
+  }
+  std::vector<double> cdf(n_blocks);
+  HIP_TRY(hipMemcpyAsync(cdf.data(), dev_sums, sizeof(double) * n_blocks, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *n_passes = 1;
+  long double run = 0;                               // the block prefix, in block order (rounding to double keeps it monotone)
+  for (u64 b = 0; b < n_blocks; ++b) { run += cdf[b]; cdf[b] = (double)run; }
+  *total = cdf[n_blocks - 1];
+  if (!(*total > 0.0) || !std::isfinite(*total)) return fail(QSIM_ERR_INVALID, "qsim_sample: sum |amp|^2 = %g, nothing to sample from", *total);
+  std::vector<uint64_t> block(n_shots);
+  std::vector<double> local(n_shots);
+  sample_locate(n_blocks, cdf.data(), n_shots, randnums, block.data(), local.data());
+  std::vector<unsigned> order(n_shots);              // the shots grouped by block (ties in the order of randnums)
+  for (u64 s = 0; s < n_shots; ++s) order[s] = (unsigned)s;
+  std::sort(order.begin(), order.end(), [&](unsigned a, unsigned b) { return block[a] != block[b] ? block[a] < block[b] : a < b; });
+  std::vector<u64> slot(n_shots), hit;
+  std::vector<unsigned> first;
+  for (u64 j = 0; j < n_shots; ++j) {
+    const unsigned s = order[j];
+    if (!j || block[s] != hit.back()) { hit.push_back(block[s]); first.push_back((unsigned)j); }
+    std::memcpy(&slot[j], &local[s], sizeof(double));
+  }
+  first.push_back((unsigned)n_shots);
+  const u64 n_hit = hit.size();
+  HIP_TRY(hipMemcpyAsync(dev_slot, slot.data(), sizeof(u64) * n_shots, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dev_hit, hit.data(), sizeof(u64) * n_hit, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dev_first, first.data(), sizeof(unsigned) * (n_hit + 1), hipMemcpyHostToDevice, c->stream));
+  {
+    ProfileScope prof(10, 16.0 * (double)std::min<u64>(n, n_hit << kSampleBlockBits), c->stream, nt);
+    if (nt) hipLaunchKernelGGL((k_sample_resolve<true>), grid_for(n_hit), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, (const u64*)dev_hit, (const unsigned*)dev_first, n_hit, dev_slot);
+    else hipLaunchKernelGGL((k_sample_resolve<false>), grid_for(n_hit), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, (const u64*)dev_hit, (const unsigned*)dev_first, n_hit, dev_slot);
+    HIP_TRY(hipGetLastError());
+    prof.done(c->stream);
+  }
+  HIP_TRY(hipMemcpyAsync(slot.data(), dev_slot, sizeof(u64) * n_shots, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (u64 j = 0; j < n_shots; ++j) out_indices[order[j]] = slot[j];
+  *n_passes = 2;
+  return QSIM_OK;
+}
+
 // Sparse export: the amplitudes with |re| > eps or |im| > eps as rows (index, re, im), ascending by index.
 int qsim_count_nonzero(qsim_chunk* c, double eps, uint64_t* count) {
   int rc = check_chunk(c, "qsim_count_nonzero");

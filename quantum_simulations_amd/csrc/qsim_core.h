@@ -35,6 +35,8 @@ struct qsim_chunk {
   double* hist;          // qsim_probabilities: partial histograms (lazily allocated, owned)
   void* expect;          // qsim_expectation_pauli: partial rows, term tables, results (grown on demand, owned)
   u64 expect_bytes;
+  void* sample;          // qsim_sample: block sums, hit-block lists, shot slots (grown on demand, owned)
+  u64 sample_bytes;
   int last_passes;       // HBM passes of the last qsim_apply_ops
   u64 span_bytes;        // size of the allocation the chunk lives in (cache-policy choice)
   struct PendingLast* pending;   // split form of qsim_apply_ops_io: the slab-storing pass, planned but not yet launched (owned)

@@ -51,6 +51,7 @@ typedef unsigned long long u64;
 #include "misc_kernels.h"
 #include "dense_kernels.h"
 #include "expect_kernels.h"
+#include "sample_kernels.h"
 #include "comm_rccl.h"
 
 // The C ABI, by topic.  abi_pending.h first: every topic asks whether a split call has left pieces pending on a chunk.

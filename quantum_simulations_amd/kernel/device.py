@@ -313,6 +313,20 @@ class DeviceChunk:
         x, z = obs.masks(l2p)
         return obs.value(self.expectation_pauli(x, z))
 
+    def sample(self, randnums) -> np.ndarray:
+        """One sampled PHYSICAL index of this chunk per uniform of `randnums` (each in [0, 1); `sampling.draw` makes
+        them), drawn from |amp|^2 / total on the device (qsim_sample: one read-only pass over the chunk and one over the
+        blocks that were hit, a fixed summation order -- two calls give the same bits; an index with |amp|^2 = 0 is
+        never returned).  uint64, in the order of `randnums`.  `self.last_sample_total` = sum |amp|^2 (0.0 for no
+        shots: nothing is launched), `self.last_sample_passes` = the passes that ran."""
+        r = np.ascontiguousarray(randnums, dtype=np.float64).reshape(-1)
+        out = np.empty(r.size, dtype=np.uint64)
+        total, passes = C.c_double(0.0), C.c_int(0)
+        _lib.check(_lib.load().qsim_sample(self._h, int(r.size), r.ctypes.data_as(C.c_void_p),
+                                           out.ctypes.data_as(C.c_void_p), C.byref(total), C.byref(passes)))
+        self.last_sample_total, self.last_sample_passes = total.value, passes.value
+        return out
+
     def max_abs_err_closed_form(self, kind: str, n_total: int, base_index: int = 0,
                                 log_to_phys=None) -> float:
         """max |amp - closed form| over this chunk; `log_to_phys` maps a staged layout back."""
@@ -403,6 +417,23 @@ def plan_expectation(k: int, x_masks) -> tuple[np.ndarray, np.ndarray]:
                                                  pass_of.ctypes.data_as(C.c_void_p), tiles.ctypes.data_as(C.c_void_p),
                                                  C.byref(n)))
     return pass_of, tiles[: n.value].copy()
+
+
+def sample_block_bits() -> int:
+    """log2 of the block length of `DeviceChunk.sample` (qsim_sample_block_bits)."""
+    return int(_lib.load().qsim_sample_block_bits())
+
+
+def sample_locate(block_cdf, randnums) -> tuple[np.ndarray, np.ndarray]:
+    """qsim_sample_locate (host only): (block, local threshold) of every uniform, from the inclusive block prefix."""
+    cdf = np.ascontiguousarray(block_cdf, dtype=np.float64).reshape(-1)
+    r = np.ascontiguousarray(randnums, dtype=np.float64).reshape(-1)
+    block = np.empty(r.size, dtype=np.uint64)
+    local = np.empty(r.size, dtype=np.float64)
+    _lib.check(_lib.load().qsim_sample_locate(int(cdf.size), cdf.ctypes.data_as(C.c_void_p), int(r.size),
+                                              r.ctypes.data_as(C.c_void_p), block.ctypes.data_as(C.c_void_p),
+                                              local.ctypes.data_as(C.c_void_p)))
+    return block, local
 
 
 def device_count() -> int:

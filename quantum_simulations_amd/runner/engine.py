@@ -93,6 +93,14 @@ class SingleGpuEngine:
         evaluated on the device through the current layout; the state does not move."""
         return self.state.expectation(obs, l2p=self.l2p if self.l2p is not None else list(range(self.n)))
 
+    def sample(self, shots: int, seed: int = 0, qubits=None) -> np.ndarray:
+        """`shots` samples of the register, drawn on the device through the current layout (the state does not move;
+        `sampling.draw(shots, seed)` gives the uniforms): LOGICAL basis-state indices as uint64, or with `qubits` the
+        marginal values (bit j = qubit qubits[j]).  `sampling.counts` turns them into {bitstring: count}."""
+        from quantum_simulations_amd import sampling
+        values = sampling.to_logical(self.state.sample(sampling.draw(shots, seed)), self.l2p)
+        return values if qubits is None else sampling.marginal(values, qubits)
+
     def logical_index(self, offset: int, count: int) -> np.ndarray:
         """Logical amplitude indices of the physical range [offset, offset + count) of the state in its current layout."""
         x = offset + np.arange(count, dtype=np.int64)

@@ -310,6 +310,16 @@ def expectation(buf: HbmStateBuffer, obs) -> float:
     return buf.state.expectation(obs, l2p=l2p)
 
 
+def sample(buf: HbmStateBuffer, shots: int, seed: int = 0, qubits=None) -> np.ndarray:
+    """`shots` samples of the final state of `run`, drawn on the device through the staging layout `buf.log_to_phys`
+    (nothing is downloaded or permuted; `sampling.draw(shots, seed)` gives the uniforms): LOGICAL basis-state indices as
+    uint64, or with `qubits` the marginal values (bit j = qubit qubits[j])."""
+    from quantum_simulations_amd import sampling
+    l2p = getattr(buf, "log_to_phys", None) or None
+    values = sampling.to_logical(buf.state.sample(sampling.draw(shots, seed)), l2p)
+    return values if qubits is None else sampling.marginal(values, qubits)
+
+
 def collect_state(buf: HbmStateBuffer, apply_permutation: bool = False,
                   work_dir: str | Path | None = None) -> np.ndarray:
     """All chunks back as one complex128 vector; with `apply_permutation` and a
