@@ -84,6 +84,31 @@ def test_formula_against_kron_for_every_string(n):
         assert abs(got - want.real) < 1e-12, (letters, got, want)
 
 
+def test_operator_reference_against_the_parity_formula_and_kron():
+    """tests/pauli_reference.py (P applied to the reshaped state: the host reference of the GPU tests at 2^22 amplitudes)
+    against pauli_terms_np on a 10-qubit random state, over the single-qubit and random strings the GPU suite uses, and
+    P |psi> itself against the explicit Kronecker matrix for every string on 3 qubits (the Y phase and the axis order)."""
+    from tests.pauli_reference import apply_pauli, pauli_terms_operator
+    from tests.test_gpu_expectation import _terms
+    n = 10
+    rng = np.random.default_rng(10)
+    psi = rng.standard_normal(1 << n) + 1j * rng.standard_normal(1 << n)
+    psi /= np.linalg.norm(psi)
+    x, z = _terms(n, 110)
+    assert len(x) == 1 + 3 * n + 3 * n
+    got, want = pauli_terms_operator(psi, x, z), pauli_terms_np(psi, x, z)
+    # both are double sums of 2^10 products whose moduli add up to at most 1 (Cauchy-Schwarz): each within 2^10 eps = 1.1e-13
+    assert float(np.max(np.abs(got - want))) < 2.5e-13, int(np.argmax(np.abs(got - want)))
+    assert float(np.max(np.abs(want[1:]))) > 1e-3                   # (not a comparison of zeros)
+    phi = rng.standard_normal(8) + 1j * rng.standard_normal(8)
+    for letters in itertools.product("IXYZ", repeat=3):
+        ops = {q: letters[q] for q in range(3) if letters[q] != "I"}
+        p = PauliSum([(1.0, ops)], n_qubits=3)
+        np.testing.assert_allclose(apply_pauli(phi, p.x[0], p.z[0]), _kron_matrix(ops, 3) @ phi, rtol=0, atol=1e-15)
+    with pytest.raises(ValueError):
+        apply_pauli(phi, 1 << 3, 0)
+
+
 def test_value_applies_coefficients_in_order():
     p = PauliSum({"Z0": 2.0, "X1": -0.5}, n_qubits=2)
     assert p.value([0.25, 1.0]) == 2.0 * 0.25 - 0.5
