@@ -182,6 +182,12 @@ def load() -> C.CDLL:
     return lib
 
 
+def ptr(a):
+    """The `void*` of a C-contiguous numpy array for a call into the library; None stays None (a null pointer).  The
+    caller keeps the array alive over the call."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
 def check(rc: int) -> None:
     """Map a C return code to the exception the reference's Python API raises."""
     if rc == QSIM_OK:

@@ -17,7 +17,7 @@ def _mat_ptr(U: np.ndarray, dim: int):
     m = np.ascontiguousarray(U, dtype=np.complex128)
     if m.shape != (dim, dim):
         raise ValueError(f"expected a {dim}x{dim} matrix, got shape {m.shape}")
-    return m, m.ctypes.data_as(C.c_void_p)
+    return m, _lib.ptr(m)
 
 
 def pack_ops(ops) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -34,6 +34,14 @@ def pack_ops(ops) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
             raise ValueError(f"op {i}: matrix size {flat.size} does not fit {len(qubits)} qubit(s)")
         mats[i, : flat.size] = flat
     return nq, qs, mats
+
+
+def as_packed(ops) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`ops` in the form the C calls take: the tuple `pack_ops` returns as it is (plans that run repeatedly pack once, and
+    nothing is copied here), [(qubits, U), ...] packed now."""
+    if isinstance(ops, tuple) and len(ops) == 3 and isinstance(ops[0], np.ndarray):
+        return ops
+    return pack_ops(ops)
 
 
 class DeviceChunk:
@@ -108,24 +116,24 @@ class DeviceChunk:
 
     def upload(self, arr: np.ndarray, offset: int = 0) -> None:
         host = np.ascontiguousarray(arr, dtype=np.complex128)
-        _lib.check(_lib.load().qsim_upload(self._h, host.ctypes.data_as(C.c_void_p), offset, host.size))
+        _lib.check(_lib.load().qsim_upload(self._h, _lib.ptr(host), offset, host.size))
 
     def download(self, offset: int = 0, count: int | None = None) -> np.ndarray:
         count = len(self) - offset if count is None else count
         out = np.empty(count, dtype=np.complex128)
-        _lib.check(_lib.load().qsim_download(self._h, out.ctypes.data_as(C.c_void_p), offset, count))
+        _lib.check(_lib.load().qsim_download(self._h, _lib.ptr(out), offset, count))
         return out
 
     def download_c64(self, offset: int = 0, count: int | None = None) -> np.ndarray:
         """Amplitudes as complex64, rounded on the device (the reference's chunk-file dtype)."""
         count = len(self) - offset if count is None else count
         out = np.empty(count, dtype=np.complex64)
-        _lib.check(_lib.load().qsim_download_c64(self._h, out.ctypes.data_as(C.c_void_p), int(offset), int(count)))
+        _lib.check(_lib.load().qsim_download_c64(self._h, _lib.ptr(out), int(offset), int(count)))
         return out
 
     def upload_c64(self, arr: np.ndarray, offset: int = 0) -> None:
         a = np.ascontiguousarray(arr, dtype=np.complex64)
-        _lib.check(_lib.load().qsim_upload_c64(self._h, a.ctypes.data_as(C.c_void_p), int(offset), int(a.size)))
+        _lib.check(_lib.load().qsim_upload_c64(self._h, _lib.ptr(a), int(offset), int(a.size)))
 
     def copy_from(self, other: "DeviceChunk", variant: int = 0) -> None:
         """variant (measurement aid, qsim_copy_variant): 0 the library's choice, 1 non-temporal kernel, 2 plain kernel, 3 hipMemcpyAsync"""
@@ -150,16 +158,15 @@ class DeviceChunk:
         m = np.ascontiguousarray(M, dtype=np.complex128)
         if m.shape != (1 << len(q), 1 << len(q)):
             raise ValueError(f"a {len(q)}-qubit block needs a {1 << len(q)} x {1 << len(q)} matrix, got {m.shape}")
-        _lib.check(_lib.load().qsim_apply_fused_k(self._h, len(q), q.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p)))
+        _lib.check(_lib.load().qsim_apply_fused_k(self._h, len(q), _lib.ptr(q), _lib.ptr(m)))
 
     def apply_ops_tiled(self, ops, tile_masks) -> int:
         """`apply_ops` (fused) with the high tile bits of the first passes given (qsim_apply_ops_tiled): `tile_masks` =
         uint64 array, bit b of entry p = index bit b is a tile bit of pass p.  Returns the HBM round trips."""
-        nq, qs, mats = ops if (isinstance(ops, tuple) and len(ops) == 3 and isinstance(ops[0], np.ndarray)) else pack_ops(ops)
+        nq, qs, mats = as_packed(ops)
         tm = np.ascontiguousarray(tile_masks, dtype=np.uint64)
         lib = _lib.load()
-        _lib.check(lib.qsim_apply_ops_tiled(self._h, len(nq), nq.ctypes.data_as(C.c_void_p), qs.ctypes.data_as(C.c_void_p),
-                                            mats.ctypes.data_as(C.c_void_p), len(tm), tm.ctypes.data_as(C.c_void_p)))
+        _lib.check(lib.qsim_apply_ops_tiled(self._h, len(nq), _lib.ptr(nq), _lib.ptr(qs), _lib.ptr(mats), len(tm), _lib.ptr(tm)))
         return lib.qsim_last_pass_count(self._h)
 
     def apply_ops(self, ops, fused: bool = True) -> int:
@@ -168,16 +175,11 @@ class DeviceChunk:
         `ops` may also be the tuple returned by `pack_ops` (plans that run repeatedly pack once)."""
         if not len(ops):
             return 0
-        if isinstance(ops, tuple) and len(ops) == 3 and isinstance(ops[0], np.ndarray):
-            nq, qs, mats = ops
-            ops = nq
-        else:
-            nq, qs, mats = pack_ops(ops)
+        nq, qs, mats = as_packed(ops)
         lib = _lib.load()
         fn = lib.qsim_apply_ops if fused else lib.qsim_apply_ops_unfused
-        _lib.check(fn(self._h, len(ops), nq.ctypes.data_as(C.c_void_p), qs.ctypes.data_as(C.c_void_p),
-                      mats.ctypes.data_as(C.c_void_p)))
-        return lib.qsim_last_pass_count(self._h) if fused else len(ops)
+        _lib.check(fn(self._h, len(nq), _lib.ptr(nq), _lib.ptr(qs), _lib.ptr(mats)))
+        return lib.qsim_last_pass_count(self._h) if fused else len(nq)
 
     # ---- sync / reductions / timing -------------------------------------------------
     def apply_ops_io(self, ops, src=None, dst=None, parts: int = 0, src_parts: int = 0, tiles=None) -> int:
@@ -191,7 +193,7 @@ class DeviceChunk:
         piece with `load_part(j)` once its transfer is ordered on this chunk's stream -- the first pass starts on the
         tiles whose pieces are there, the rest runs with the last piece.  `tiles`: uint64 masks, the high tile bits of the
         first passes named by the caller (qsim_ops_io::tile_masks; as in `apply_ops_tiled`)."""
-        nq, qs, mats = pack_ops(ops) if not (isinstance(ops, tuple) and len(ops) == 3 and isinstance(ops[0], np.ndarray)) else ops
+        nq, qs, mats = as_packed(ops)
         io = _lib.OpsIo()
         keep = []
         if tiles is not None and len(tiles):
@@ -216,8 +218,7 @@ class DeviceChunk:
         io.dst_parts = int(parts) if dst is not None else 0
         io.src_parts = int(src_parts) if src is not None else 0
         passes = C.c_int()
-        _lib.check(_lib.load().qsim_apply_ops_io(self._h, len(nq), nq.ctypes.data_as(C.c_void_p), qs.ctypes.data_as(C.c_void_p),
-                                                 mats.ctypes.data_as(C.c_void_p), C.byref(io), C.byref(passes)))
+        _lib.check(_lib.load().qsim_apply_ops_io(self._h, len(nq), _lib.ptr(nq), _lib.ptr(qs), _lib.ptr(mats), C.byref(io), C.byref(passes)))
         return passes.value
 
     def own_slab_in_chunk(self) -> bool:
@@ -266,8 +267,7 @@ class DeviceChunk:
         idx = np.empty(capacity, dtype=np.uint64)
         amp = np.empty(capacity, dtype=np.complex128)
         n = C.c_uint64()
-        _lib.check(_lib.load().qsim_export_nonzero(self._h, float(eps), int(capacity), idx.ctypes.data_as(C.c_void_p),
-                                                   amp.ctypes.data_as(C.c_void_p), C.byref(n)))
+        _lib.check(_lib.load().qsim_export_nonzero(self._h, float(eps), int(capacity), _lib.ptr(idx), _lib.ptr(amp), C.byref(n)))
         if n.value > capacity:
             return None
         return idx[:n.value], amp[:n.value]
@@ -285,8 +285,7 @@ class DeviceChunk:
         if not 1 <= len(q) <= 8:
             raise ValueError(f"probabilities: 1 to 8 qubits expected, got {len(q)}")
         out = np.empty(1 << len(q), dtype=np.float64)
-        _lib.check(_lib.load().qsim_probabilities(self._h, len(q), q.ctypes.data_as(C.c_void_p),
-                                                  out.ctypes.data_as(C.c_void_p)))
+        _lib.check(_lib.load().qsim_probabilities(self._h, len(q), _lib.ptr(q), _lib.ptr(out)))
         return out
 
     def expectation_pauli(self, x_masks, z_masks) -> np.ndarray:
@@ -299,9 +298,7 @@ class DeviceChunk:
             raise ValueError(f"expectation_pauli: {x.size} x masks, {z.size} z masks")
         out = np.empty(x.size, dtype=np.float64)
         passes = C.c_int(0)
-        _lib.check(_lib.load().qsim_expectation_pauli(self._h, int(x.size), x.ctypes.data_as(C.c_void_p),
-                                                      z.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
-                                                      C.byref(passes)))
+        _lib.check(_lib.load().qsim_expectation_pauli(self._h, int(x.size), _lib.ptr(x), _lib.ptr(z), _lib.ptr(out), C.byref(passes)))
         self.last_expectation_passes = passes.value
         return out
 
@@ -322,8 +319,7 @@ class DeviceChunk:
         r = np.ascontiguousarray(randnums, dtype=np.float64).reshape(-1)
         out = np.empty(r.size, dtype=np.uint64)
         total, passes = C.c_double(0.0), C.c_int(0)
-        _lib.check(_lib.load().qsim_sample(self._h, int(r.size), r.ctypes.data_as(C.c_void_p),
-                                           out.ctypes.data_as(C.c_void_p), C.byref(total), C.byref(passes)))
+        _lib.check(_lib.load().qsim_sample(self._h, int(r.size), _lib.ptr(r), _lib.ptr(out), C.byref(total), C.byref(passes)))
         self.last_sample_total, self.last_sample_passes = total.value, passes.value
         return out
 
@@ -333,9 +329,7 @@ class DeviceChunk:
         out = C.c_double()
         code = {"ghz": 0, "ghz_qft": 1}[kind]
         perm = None if log_to_phys is None else np.asarray(log_to_phys, dtype=np.int32)
-        _lib.check(_lib.load().qsim_max_abs_err_closed_form_perm(
-            self._h, code, n_total, base_index,
-            None if perm is None else perm.ctypes.data_as(C.c_void_p), C.byref(out)))
+        _lib.check(_lib.load().qsim_max_abs_err_closed_form_perm(self._h, code, n_total, base_index, _lib.ptr(perm), C.byref(out)))
         return out.value
 
     def fingerprint(self, n_total: int, base_index: int = 0, log_to_phys=None, seed: int = 0,
@@ -344,9 +338,7 @@ class DeviceChunk:
         sel_value (qsim_fingerprint: counter-based weights, layout-aware, evaluated on the device)."""
         out = (C.c_double * 2)()
         perm = None if log_to_phys is None else np.asarray(log_to_phys, dtype=np.int32)
-        _lib.check(_lib.load().qsim_fingerprint(
-            self._h, n_total, base_index, None if perm is None else perm.ctypes.data_as(C.c_void_p),
-            seed, sel_mask, sel_value, out))
+        _lib.check(_lib.load().qsim_fingerprint(self._h, n_total, base_index, _lib.ptr(perm), seed, sel_mask, sel_value, out))
         return complex(out[0], out[1])
 
     def time_begin(self) -> None:
@@ -381,23 +373,21 @@ class DeviceChunk:
 
     def pack_bits(self, bits, pattern: int, buf: "DeviceChunk", buf_offset: int = 0) -> None:
         b = np.asarray(bits, dtype=np.int32)
-        _lib.check(_lib.load().qsim_pack_bits(self._h, len(b), b.ctypes.data_as(C.c_void_p), int(pattern),
-                                              buf._h, int(buf_offset)))
+        _lib.check(_lib.load().qsim_pack_bits(self._h, len(b), _lib.ptr(b), int(pattern), buf._h, int(buf_offset)))
 
     def unpack_bits(self, bits, pattern: int, buf: "DeviceChunk", buf_offset: int = 0) -> None:
         b = np.asarray(bits, dtype=np.int32)
-        _lib.check(_lib.load().qsim_unpack_bits(self._h, len(b), b.ctypes.data_as(C.c_void_p), int(pattern),
-                                                buf._h, int(buf_offset)))
+        _lib.check(_lib.load().qsim_unpack_bits(self._h, len(b), _lib.ptr(b), int(pattern), buf._h, int(buf_offset)))
     def pack_all(self, bits, buf: "DeviceChunk", skip_pattern: int = -1, piece: int = 0, n_pieces: int = 1) -> None:
         """Every slab of the all-to-all re-layout in one pass (qsim_pack_all); `piece` of `n_pieces`
         = the same contiguous sub-range of every slab."""
         b = np.asarray(bits, dtype=np.int32)
-        _lib.check(_lib.load().qsim_pack_all(self._h, len(b), b.ctypes.data_as(C.c_void_p), buf._h, int(skip_pattern),
+        _lib.check(_lib.load().qsim_pack_all(self._h, len(b), _lib.ptr(b), buf._h, int(skip_pattern),
                                              int(piece), int(n_pieces)))
 
     def unpack_all(self, bits, buf: "DeviceChunk", skip_pattern: int = -1, piece: int = 0, n_pieces: int = 1) -> None:
         b = np.asarray(bits, dtype=np.int32)
-        _lib.check(_lib.load().qsim_unpack_all(self._h, len(b), b.ctypes.data_as(C.c_void_p), buf._h, int(skip_pattern),
+        _lib.check(_lib.load().qsim_unpack_all(self._h, len(b), _lib.ptr(b), buf._h, int(skip_pattern),
                                                int(piece), int(n_pieces)))
 
 
@@ -413,9 +403,7 @@ def plan_expectation(k: int, x_masks) -> tuple[np.ndarray, np.ndarray]:
     pass_of = np.empty(x.size, dtype=np.int32)
     tiles = np.empty(max(x.size, 1), dtype=np.uint64)
     n = C.c_int(0)
-    _lib.check(_lib.load().qsim_plan_expectation(int(k), int(x.size), x.ctypes.data_as(C.c_void_p),
-                                                 pass_of.ctypes.data_as(C.c_void_p), tiles.ctypes.data_as(C.c_void_p),
-                                                 C.byref(n)))
+    _lib.check(_lib.load().qsim_plan_expectation(int(k), int(x.size), _lib.ptr(x), _lib.ptr(pass_of), _lib.ptr(tiles), C.byref(n)))
     return pass_of, tiles[: n.value].copy()
 
 
@@ -430,9 +418,7 @@ def sample_locate(block_cdf, randnums) -> tuple[np.ndarray, np.ndarray]:
     r = np.ascontiguousarray(randnums, dtype=np.float64).reshape(-1)
     block = np.empty(r.size, dtype=np.uint64)
     local = np.empty(r.size, dtype=np.float64)
-    _lib.check(_lib.load().qsim_sample_locate(int(cdf.size), cdf.ctypes.data_as(C.c_void_p), int(r.size),
-                                              r.ctypes.data_as(C.c_void_p), block.ctypes.data_as(C.c_void_p),
-                                              local.ctypes.data_as(C.c_void_p)))
+    _lib.check(_lib.load().qsim_sample_locate(int(cdf.size), _lib.ptr(cdf), int(r.size), _lib.ptr(r), _lib.ptr(block), _lib.ptr(local)))
     return block, local
 
 
@@ -448,10 +434,8 @@ def relayout_plan(rank: int, world: int, k: int, local_bits, global_bits, n_piec
     lb, gb = np.asarray(local_bits, dtype=np.int32), np.asarray(global_bits, dtype=np.int32)
     n_p, n_peers, own = C.c_int32(), C.c_int32(), C.c_int32()
     peers, offs, part = np.zeros(7, dtype=np.int32), np.zeros(7, dtype=np.uint64), C.c_uint64()
-    _lib.check(_lib.load().qsim_comm_relayout_plan(int(rank), int(world), int(k), len(lb), lb.ctypes.data_as(C.c_void_p),
-                                                   gb.ctypes.data_as(C.c_void_p), int(n_pieces), C.byref(n_p), C.byref(n_peers),
-                                                   C.byref(own), peers.ctypes.data_as(C.c_void_p),
-                                                   offs.ctypes.data_as(C.c_void_p), C.byref(part)))
+    _lib.check(_lib.load().qsim_comm_relayout_plan(int(rank), int(world), int(k), len(lb), _lib.ptr(lb), _lib.ptr(gb), int(n_pieces),
+                                                   C.byref(n_p), C.byref(n_peers), C.byref(own), _lib.ptr(peers), _lib.ptr(offs), C.byref(part)))
     return {"pieces": n_p.value, "own_pattern": own.value, "peers": [int(x) for x in peers[:n_peers.value]],
             "slab_offsets": [int(x) for x in offs[:n_peers.value]], "piece_amps": int(part.value)}
 
@@ -481,18 +465,15 @@ class Comm:
     def exchange(self, peers, send: DeviceChunk, send_off, recv: DeviceChunk, recv_off, count: int) -> None:
         p = np.asarray(peers, dtype=np.int32)
         so, ro = np.asarray(send_off, dtype=np.uint64), np.asarray(recv_off, dtype=np.uint64)
-        _lib.check(_lib.load().qsim_comm_exchange(self._h, len(p), p.ctypes.data_as(C.c_void_p), send._h,
-                                                  so.ctypes.data_as(C.c_void_p), recv._h,
-                                                  ro.ctypes.data_as(C.c_void_p), int(count)))
+        _lib.check(_lib.load().qsim_comm_exchange(self._h, len(p), _lib.ptr(p), send._h, _lib.ptr(so), recv._h, _lib.ptr(ro), int(count)))
 
     def exchange_bg(self, peers, send: DeviceChunk, send_off, recv: DeviceChunk, recv_off, count: int) -> int:
         """qsim_comm_exchange_bg: the group on the communicator's transfer stream, beside later work on the chunks' stream."""
         p = np.asarray(peers, dtype=np.int32)
         so, ro = np.asarray(send_off, dtype=np.uint64), np.asarray(recv_off, dtype=np.uint64)
         ticket = C.c_uint32()
-        _lib.check(_lib.load().qsim_comm_exchange_bg(self._h, len(p), p.ctypes.data_as(C.c_void_p), send._h,
-                                                     so.ctypes.data_as(C.c_void_p), recv._h,
-                                                     ro.ctypes.data_as(C.c_void_p), int(count), C.byref(ticket)))
+        _lib.check(_lib.load().qsim_comm_exchange_bg(self._h, len(p), _lib.ptr(p), send._h, _lib.ptr(so), recv._h, _lib.ptr(ro),
+                                                     int(count), C.byref(ticket)))
         return ticket.value
 
     def join(self, chunk: DeviceChunk) -> None:
@@ -505,17 +486,14 @@ class Comm:
     def relayout(self, state: DeviceChunk, buf0: DeviceChunk, buf1: DeviceChunk, local_bits, global_bits,
                  n_pieces: int = 4) -> None:
         lb, gb = np.asarray(local_bits, dtype=np.int32), np.asarray(global_bits, dtype=np.int32)
-        _lib.check(_lib.load().qsim_comm_relayout(self._h, state._h, buf0._h, buf1._h, len(lb),
-                                                  lb.ctypes.data_as(C.c_void_p), gb.ctypes.data_as(C.c_void_p),
-                                                  int(n_pieces)))
+        _lib.check(_lib.load().qsim_comm_relayout(self._h, state._h, buf0._h, buf1._h, len(lb), _lib.ptr(lb), _lib.ptr(gb), int(n_pieces)))
 
     def relayout_loopback(self, state: DeviceChunk, buf0: DeviceChunk, buf1: DeviceChunk, local_bits, global_bits,
                           n_pieces: int, as_rank: int, as_world: int) -> None:
         """qsim_comm_relayout's pipeline as rank `as_rank` of `as_world` would run it, every transfer looped back
         to this rank (one GPU): the state is unchanged afterwards, buf1 holds the 'received' slabs."""
         lb, gb = np.asarray(local_bits, dtype=np.int32), np.asarray(global_bits, dtype=np.int32)
-        _lib.check(_lib.load().qsim_comm_relayout_loopback(self._h, state._h, buf0._h, buf1._h, len(lb),
-                                                           lb.ctypes.data_as(C.c_void_p), gb.ctypes.data_as(C.c_void_p),
+        _lib.check(_lib.load().qsim_comm_relayout_loopback(self._h, state._h, buf0._h, buf1._h, len(lb), _lib.ptr(lb), _lib.ptr(gb),
                                                            int(n_pieces), int(as_rank), int(as_world)))
 
     def relayout_fused(self, shard: DeviceChunk, send: DeviceChunk, recv: DeviceChunk, before, after, local_bits,
@@ -534,7 +512,7 @@ class Comm:
             lists.append(ol)
         passes = C.c_int()
         _lib.check(_lib.load().qsim_comm_relayout_fused(self._h, shard._h, send._h, recv._h, C.byref(lists[0]), C.byref(lists[1]),
-                                                        len(lb), lb.ctypes.data_as(C.c_void_p), gb.ctypes.data_as(C.c_void_p),
+                                                        len(lb), _lib.ptr(lb), _lib.ptr(gb),
                                                         int(n_pieces), int(as_rank), int(as_world), C.byref(passes)))
         return passes.value
 
@@ -543,7 +521,7 @@ class Comm:
         rank holds chunk `my_index`.  ranks = [r] * 4 with r = this rank: one-GPU loopback form."""
         m, p = _mat_ptr(U, 4)
         r = np.asarray(ranks, dtype=np.int32)
-        _lib.check(_lib.load().qsim_apply_2q_quad_remote(self._h, shard._h, buf._h, r.ctypes.data_as(C.c_void_p), int(my_index), p))
+        _lib.check(_lib.load().qsim_apply_2q_quad_remote(self._h, shard._h, buf._h, _lib.ptr(r), int(my_index), p))
 
     def apply_1q_pair_remote(self, shard: DeviceChunk, buf: DeviceChunk, partner: int, my_side: int, U) -> None:
         m, p = _mat_ptr(U, 2)

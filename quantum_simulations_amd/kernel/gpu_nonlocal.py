@@ -76,5 +76,4 @@ def swap_global_local(chunks, global_bits, local_bits) -> None:
     arr = (C.c_void_p * len(chunks))(*[c._h for c in chunks])
     gb = np.asarray(global_bits, dtype=np.int32)
     lb = np.asarray(local_bits, dtype=np.int32)
-    _lib.check(_lib.load().qsim_swap_global_local(arr, len(chunks), gb.ctypes.data_as(C.c_void_p),
-                                                  lb.ctypes.data_as(C.c_void_p), len(gb)))
+    _lib.check(_lib.load().qsim_swap_global_local(arr, len(chunks), _lib.ptr(gb), _lib.ptr(lb), len(gb)))

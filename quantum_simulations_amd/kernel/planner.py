@@ -1,0 +1,103 @@
+"""The host planner of libqsim_hip.so in Python: what the pass builder would do with an op list, without a device
+(csrc/abi_plan.h: qsim_plan_ops, qsim_plan_ops_tiled, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass).
+
+A thin binding.  `ops` is [(qubits, U), ...] or the tuple `pack_ops` returns (`device.as_packed`).  Return codes become
+the exceptions of `_lib.check` and nothing else is read into them: what a caller makes of a list too short to plan is
+the caller's business.  No module-level state: the layout search and the partition planner call in from thread pools
+(the calls go through the `ctypes.CDLL` of `_lib.load()`, which releases the interpreter lock while the library runs).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from quantum_simulations_amd import _lib
+from quantum_simulations_amd._lib import ptr
+from quantum_simulations_amd.kernel.device import as_packed
+
+IMAGE_BYTES = 4096                 # QSIM_PASS_IMAGE_BYTES (include/qsim_hip.h)
+STREAM_OFF = 192                   # byte offset of the first record (csrc/tile_kernel.h kTileStreamOff)
+# One pass image = the kernel-argument block `TileArgs` of k_tile (csrc/tile_kernel.h), field by field
+PASS_IMAGE = np.dtype([("amp", "<u8"), ("nrec", "<i4"), ("T", "<i4"), ("h", "u1", (11,)), ("order", "u1"), ("ntiles", "<u4"),
+                       ("lay_in", "u1", (12,)), ("lay_out", "u1", (12,)), ("amp_out", "<u8"),
+                       # re-layout fused into a pass (planned images carry none: all zero)
+                       ("amp_out_own", "<u8"), ("own_mask", "<u8"), ("own_value", "<u8"),
+                       ("slab_in", "u1", (40,)), ("slab_out", "u1", (40,)), ("nbits", "u1"), ("perm", "u1"), ("reserved", "u1", (22,)),
+                       ("stream", "u1", (IMAGE_BYTES - STREAM_OFF,))])
+assert PASS_IMAGE.itemsize == IMAGE_BYTES
+_FIRST_BUFFER = 64                 # images the first call of `plan_ops` has room for
+
+
+def tile_bits(image) -> list:
+    """The high tile bits of a pass (ascending; the line bits 0..2 belong to every tile and are not listed)."""
+    return [int(b) for b in image["h"][:int(image["T"]) - 3]]
+
+
+def tile_masks(images) -> np.ndarray:
+    """`tile_bits` of every pass as one uint64 mask each: what `search_tiles` returns and the `tiles` arguments take."""
+    return np.array([sum(1 << b for b in tile_bits(img)) for img in images], dtype=np.uint64)
+
+
+def _plan(n: int, ops, tiles, images) -> tuple:
+    """(return code, pass count) of one qsim_plan_ops / qsim_plan_ops_tiled call; `images`: None to count only."""
+    nq, qubits, mats = as_packed(ops)
+    lib, count = _lib.load(), C.c_int32()
+    head = (n, len(nq), ptr(nq), ptr(qubits), ptr(mats))
+    tail = (ptr(images), 0 if images is None else images.nbytes, C.byref(count))
+    tm = np.ascontiguousarray(tiles if tiles is not None else [], dtype=np.uint64)
+    rc = lib.qsim_plan_ops_tiled(*head, len(tm), ptr(tm), *tail) if len(tm) else lib.qsim_plan_ops(*head, *tail)
+    return rc, count.value
+
+
+def plan_ops(n: int, ops, tiles=None) -> np.ndarray:
+    """The pass images (PASS_IMAGE) of the fused plan of `ops` on n qubits; `tiles`: uint64 masks, the high tile bits of
+    the first passes named by the caller (qsim_plan_ops_tiled).  Planned once when the plan has up to 64 passes: the
+    library fills the buffer it is given and fails at the first image that does not fit, the count then being the images
+    written -- a full buffer is planned again into one of twice the size."""
+    room = _FIRST_BUFFER
+    while True:
+        images = np.zeros(room, dtype=PASS_IMAGE)
+        rc, count = _plan(n, ops, tiles, images)
+        if rc != _lib.QSIM_ERR_INVALID or count < room:     # (any other failure leaves the buffer short of full, or shows again below)
+            _lib.check(rc)
+            return images[:count]
+        room *= 2
+
+
+def pass_count(n: int, ops, tiles=None) -> int:
+    """len(plan_ops(n, ops, tiles)) without the images."""
+    rc, count = _plan(n, ops, tiles, None)
+    _lib.check(rc)
+    return count
+
+
+def search_tiles(n: int, ops, beam: int = 0) -> np.ndarray:
+    """The tiles (one uint64 mask of high tile bits per pass) of the library's searching pass builder (qsim_plan_search:
+    a beam search over the passes' tiles, `beam` 0 = its default width; never more passes than `plan_ops` makes)."""
+    nq, qubits, mats = as_packed(ops)
+    count = C.c_int32()
+    out = np.zeros(len(nq), dtype=np.uint64)
+    _lib.check(_lib.load().qsim_plan_search(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), beam, ptr(out), len(out), C.byref(count)))
+    return out[:count.value].copy()
+
+
+def count_layouts(n: int, ops, layouts, threads: int) -> np.ndarray:
+    """Passes of ONE op list under each layout (rows of `layouts`: qubit -> index bit), planned by `threads` threads of
+    the library (qsim_plan_count_layouts): int32, one per row."""
+    nq, qubits, mats = as_packed(ops)
+    lay = np.ascontiguousarray(layouts, dtype=np.int32)
+    out = np.zeros(len(lay), dtype=np.int32)
+    _lib.check(_lib.load().qsim_plan_count_layouts(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), len(lay), ptr(lay), ptr(out), threads))
+    return out
+
+
+def peek_pass(k: int, n: int, nq, qubits, mats, done, members, avoid: int = 0, hint: int = 0) -> tuple:
+    """(tile mask, needed bits, member op indices) of the NEXT pass of a partly executed op list on a partitioned state
+    (qsim_plan_peek_pass: index bits >= k of the n are rank bits; done[i] != 0: op i ran; `avoid`: bits the fill leaves
+    out; `hint` != 0 names the tile).  The arrays are handed over as they are -- packed int32 / complex128, `done` uint8,
+    `members` an int32 scratch of len(nq) or more -- because the partition planner asks thousands of times per schedule."""
+    mask, need, count = C.c_uint64(), C.c_uint64(), C.c_int32()
+    _lib.check(_lib.load().qsim_plan_peek_pass(k, n, len(nq), ptr(nq), ptr(qubits), ptr(mats), ptr(done), avoid, hint,
+                                               C.byref(mask), C.byref(need), C.byref(count), ptr(members)))
+    return int(mask.value), int(need.value), [int(i) for i in members[:count.value]]

@@ -15,7 +15,7 @@ import numpy as np
 
 from quantum_simulations_amd.circuit.fusion import batch_levels
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
-from quantum_simulations_amd.kernel import gates as gate_table
+from quantum_simulations_amd.kernel import gates as gate_table, planner
 from quantum_simulations_amd.kernel.device import DeviceChunk
 
 
@@ -380,57 +380,10 @@ def layout_swaps(cur, want, n: int) -> list:
 
 def _count_passes(n: int, batches, layouts: np.ndarray, threads: int) -> np.ndarray:
     """Fused passes of the batches under each layout (rows of `layouts`: qubit -> index bit), planned on the host."""
-    import ctypes as C
-
-    from quantum_simulations_amd import _lib
-    from quantum_simulations_amd.kernel.device import pack_ops
-    lib = _lib.load()
     total = np.zeros(len(layouts), dtype=np.int64)
-    lay = np.ascontiguousarray(layouts, dtype=np.int32)
-    for ops in batches:
-        nq, qubits, mats = pack_ops(ops)
-        if len(nq) < 2:
-            total += len(nq)
-            continue
-        out = np.zeros(len(lay), dtype=np.int32)
-        _lib.check(lib.qsim_plan_count_layouts(n, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p),
-                                               mats.ctypes.data_as(C.c_void_p), len(lay), lay.ctypes.data_as(C.c_void_p),
-                                               out.ctypes.data_as(C.c_void_p), threads))
-        total += out
+    for ops in batches:                                     # (a single op is not planned: one pass)
+        total += planner.count_layouts(n, ops, layouts, threads) if len(ops) >= 2 else len(ops)
     return total
-
-
-def _search_tiles(n: int, ops, beam: int) -> np.ndarray:
-    """The tiles (one uint64 mask of high tile bits per pass) of the library's searching pass builder for `ops` on n qubits
-    (qsim_plan_search: a beam search over the passes' tiles, host only; never more passes than qsim_plan_ops)."""
-    import ctypes as C
-
-    from quantum_simulations_amd import _lib
-    from quantum_simulations_amd.kernel.device import pack_ops
-    nq, qubits, mats = pack_ops(ops)
-    if len(nq) < 2:
-        return np.zeros(0, dtype=np.uint64)
-    lib = _lib.load()
-    count = C.c_int32()
-    out = np.zeros(len(nq), dtype=np.uint64)
-    _lib.check(lib.qsim_plan_search(n, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p),
-                                    mats.ctypes.data_as(C.c_void_p), beam, out.ctypes.data_as(C.c_void_p), len(out), C.byref(count)))
-    return out[:count.value].copy()
-
-
-def _tiled_pass_count(n: int, ops, masks) -> int:
-    """Passes the library makes of `ops` when handed the tiles `masks` (qsim_plan_ops_tiled, host only)."""
-    import ctypes as C
-
-    from quantum_simulations_amd import _lib
-    from quantum_simulations_amd.kernel.device import pack_ops
-    nq, qubits, mats = pack_ops(ops)
-    count = C.c_int32()
-    ms = np.ascontiguousarray(masks, dtype=np.uint64)
-    _lib.check(_lib.load().qsim_plan_ops_tiled(n, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p),
-                                               mats.ctypes.data_as(C.c_void_p), len(ms), ms.ctypes.data_as(C.c_void_p), None, 0,
-                                               C.byref(count)))
-    return count.value
 
 
 def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 20260504, n_finalists: int = 4,
@@ -464,7 +417,8 @@ def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 2026
         return [[([int(lay[q]) for q in qs], U) for qs, U in ops] for ops in batches]
 
     def search(lay):                                        # (the library call releases the interpreter lock)
-        return [_search_tiles(n, ops, beam) for ops in relabelled(lay)]
+        none = np.zeros(0, dtype=np.uint64)
+        return [planner.search_tiles(n, ops, beam) if len(ops) >= 2 else none for ops in relabelled(lay)]
     with ThreadPoolExecutor(threads) as pool:
         found = list(pool.map(search, layouts))
     short = sum(len(ops) for ops in batches if len(ops) < 2)                    # (a single op is not searched: one pass)
@@ -483,7 +437,7 @@ def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 2026
         # The pass count does not depend on the placement, but the records of a pass are written in the order of its tile
         # bits, and a pass at the edge of its record budget may hold one op fewer in another order: a placement that would
         # grow the plan at execution time is dropped for the one the search ran on.
-        replanned = sum(_tiled_pass_count(n, [([second[b] for b in qs], U) for qs, U in ops], ms) if len(ops) >= 2 else len(ops)
+        replanned = sum(planner.pass_count(n, [([second[b] for b in qs], U) for qs, U in ops], ms) if len(ops) >= 2 else len(ops)
                         for ops, ms in zip(moved, final_masks))
         if replanned != best:
             second, final_masks, cost1 = list(range(n)), [np.array(ms, dtype=np.uint64) for ms in masks], cost0
@@ -498,26 +452,9 @@ def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 2026
 
 
 def _planned_tile_masks(n: int, ops) -> np.ndarray:
-    """The high tile bits of the fused passes the library plans for `ops` on n qubits, one uint64 mask per pass
-    (qsim_plan_ops: the host planner without a device; offset of `h` in a pass image: csrc/tile_kernel.h TileArgs)."""
-    import ctypes as C
-
-    from quantum_simulations_amd import _lib
-    from quantum_simulations_amd.kernel.device import pack_ops
-    nq, qubits, mats = pack_ops(ops)
-    lib = _lib.load()
-    count = C.c_int32()
-    if len(nq) < 2:
-        return np.zeros(0, dtype=np.uint64)
-    args = (n, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p), mats.ctypes.data_as(C.c_void_p))
-    _lib.check(lib.qsim_plan_ops(*args, None, 0, C.byref(count)))
-    images = np.zeros((count.value, 4096), dtype=np.uint8)
-    _lib.check(lib.qsim_plan_ops(*args, images.ctypes.data_as(C.c_void_p), images.nbytes, C.byref(count)))
-    out = np.zeros(count.value, dtype=np.uint64)
-    for p in range(count.value):
-        T = int(images[p, 12:16].view("<i4")[0])
-        out[p] = sum(1 << int(b) for b in images[p, 16:16 + T - 3])
-    return out
+    """The earlier name of `planner.tile_masks(planner.plan_ops(n, ops))` (no masks for fewer than two ops), kept because
+    callers outside the package import it; new code uses the planner module."""
+    return planner.tile_masks(planner.plan_ops(n, ops)) if len(ops) >= 2 else np.zeros(0, dtype=np.uint64)
 
 
 def make_engine(n_qubits: int, world: int = 1, rank: int = 0, local_rank: int = 0,

@@ -28,12 +28,11 @@ Host only: needs libqsim_hip.so (the pass builder is host code of the library), 
 """
 from __future__ import annotations
 
-import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from quantum_simulations_amd.kernel import gates as gate_table
+from quantum_simulations_amd.kernel import gates as gate_table, planner
 
 _SWAP = gate_table.SWAP()
 _I2 = np.eye(2, dtype=np.complex128)
@@ -84,7 +83,7 @@ class PackedOps:
         return other
 
 
-def _peek(lib, check, packed: PackedOps, k: int, cur, done, members, avoid: int = 0, cache: dict | None = None):
+def _peek(packed: PackedOps, k: int, cur, done, members, avoid: int = 0, cache: dict | None = None):
     """(tile mask, needed bits, member ops) of the next pass.  `cache`: planner runs that differ only in their thin-pass
     threshold make the same decisions up to the first pass whose size lies between the thresholds: the same (layout, done
     set) is asked again and again."""
@@ -94,20 +93,16 @@ def _peek(lib, check, packed: PackedOps, k: int, cur, done, members, avoid: int 
         hit = cache.get(key)
         if hit is not None:
             return hit
-    out = _peek_uncached(lib, check, packed, k, cur, done, members, avoid)
+    out = _peek_uncached(packed, k, cur, done, members, avoid)
     if cache is not None:
         cache[key] = out
     return out
 
 
-def _peek_uncached(lib, check, packed: PackedOps, k: int, cur, done, members, avoid: int = 0):
+def _peek_uncached(packed: PackedOps, k: int, cur, done, members, avoid: int = 0):
     qs = np.ascontiguousarray(cur[packed.labels])
     qs[1::2][packed.one_q] = 0
-    mask, need, count = C.c_uint64(), C.c_uint64(), C.c_int32()
-    check(lib.qsim_plan_peek_pass(k, packed.n, len(packed.nq), packed.nq.ctypes.data_as(C.c_void_p), qs.ctypes.data_as(C.c_void_p),
-                                  packed.mats.ctypes.data_as(C.c_void_p), done.ctypes.data_as(C.c_void_p), avoid, 0,
-                                  C.byref(mask), C.byref(need), C.byref(count), members.ctypes.data_as(C.c_void_p)))
-    return int(mask.value), int(need.value), [int(i) for i in members[:count.value]]
+    return planner.peek_pass(k, packed.n, packed.nq, qs, packed.mats, done, members, avoid)
 
 
 def plan_partition(ops, n: int, k: int, min_ops: int = 20, full_width: bool = True, relayout_cost=None, cache: dict | None = None) -> dict:
@@ -115,8 +110,6 @@ def plan_partition(ops, n: int, k: int, min_ops: int = 20, full_width: bool = Tr
     -> {"steps", "moved", "passes", "relayouts", "cost", "segments", "min_ops"}: steps in the reference's format in the
     index bits of their time, moved[b] = where the qubit that started on bit b ends, passes = fused passes committed,
     relayouts = [m, ...], cost = passes + re-layouts in pass units, segments = [{"ops", "passes", "tile_masks"}, ...]."""
-    from quantum_simulations_amd import _lib
-    lib, check = _lib.load(), _lib.check
     packed = ops if isinstance(ops, PackedOps) else PackedOps(ops, n)
     ops = packed.ops
     relayout_cost = relayout_cost or RELAYOUT_COST
@@ -149,7 +142,7 @@ def plan_partition(ops, n: int, k: int, min_ops: int = 20, full_width: bool = Tr
         seg["needs"].append(need)
 
     while not done.all():
-        mask, need, members = _peek(lib, check, packed, k, cur, done, scratch, cache=cache)
+        mask, need, members = _peek(packed, k, cur, done, scratch, cache=cache)
         use = next_target_use()
         waiting = any(use[q] != never for q in range(n) if cur[q] >= k)      # an op somewhere waits for a rank bit
         fresh_segment = len(segments) > 1 and not segments[-1]["masks"]      # (a re-layout right behind a re-layout buys nothing)

@@ -262,34 +262,19 @@ class PlanningBackend(DryBackend):
             top = min(k - 1, self.model["top"])
             self.model_ref = float(np.mean([tile_layout.tile_cost(self.model, rng.choice(np.arange(3, top + 1), size=8, replace=False))
                                             for _ in range(256)]))
-        self._images = np.zeros((64, 4096), dtype=np.uint8)
         self.weight = 0.0                # model-weighted passes since the last reset
         self.passes = 0
         self.record: list | None = None  # (tools/shard_compute_probe.py: (op list, named tiles) as the rank would run them)
 
     def _plan(self, ops, tiles=None) -> tuple:
         """(passes, their model weight, tile bits of the last pass) of the fused plan of `ops` (tile passes possible)"""
-        import ctypes as C
-
-        from quantum_simulations_amd import _lib
-        from quantum_simulations_amd.kernel.device import pack_ops
-        nq, qubits, mats = pack_ops(ops)
-        lib = _lib.load()
-        count = C.c_int32()
-        tm = np.ascontiguousarray(tiles if tiles is not None else [], dtype=np.uint64)
-        args = (self.k, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p), mats.ctypes.data_as(C.c_void_p),
-                len(tm), tm.ctypes.data_as(C.c_void_p) if len(tm) else None)
-        images = self._images
-        _lib.check(lib.qsim_plan_ops_tiled(*args, images.ctypes.data_as(C.c_void_p), images.nbytes, C.byref(count)))
-        if count.value > len(images):    # (a buffer too small only reports the count)
-            images = self._images = np.zeros((2 * count.value, 4096), dtype=np.uint8)
-            _lib.check(lib.qsim_plan_ops_tiled(*args, images.ctypes.data_as(C.c_void_p), images.nbytes, C.byref(count)))
+        from quantum_simulations_amd.kernel import planner
+        images = planner.plan_ops(self.k, ops, tiles)
         weight, last = 0.0, set()
-        for p in range(count.value):     # (pass image = the kernel-argument block: T at byte 12, the tile's high bits from 16)
-            T = int(images[p, 12:16].view("<i4")[0])
-            last = {int(b) for b in images[p, 16:16 + T - 3]}
+        for img in images:
+            last = set(planner.tile_bits(img))
             weight += self._tile_layout.tile_cost(self.model, sorted(last)) / self.model_ref if self.model is not None else 1.0
-        return count.value, weight, last
+        return len(images), weight, last
 
     def apply_ops(self, ops, src=None, dst=None, parts: int = 0, src_parts: int = 0, tiles=None) -> int:
         self._io_ends(src, dst, parts, src_parts)

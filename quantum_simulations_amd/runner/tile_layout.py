@@ -86,9 +86,7 @@ def choose_layout(tiles: list, n: int, seed: int = 1, sweeps: int = 200) -> tupl
     tri = None if model.get("tri") is None else np.ascontiguousarray(model["tri"], dtype=np.float64)
     out = np.zeros(n, dtype=np.int32)
     c0, c1 = C.c_double(), C.c_double()
-    _lib.check(_lib.load().qsim_choose_layout(n, len(masks), masks.ctypes.data_as(C.c_void_p), model["top"],
-                                              bit.ctypes.data_as(C.c_void_p), pair.ctypes.data_as(C.c_void_p),
-                                              None if tri is None else tri.ctypes.data_as(C.c_void_p), seed, sweeps,
-                                              out.ctypes.data_as(C.c_void_p), C.byref(c0), C.byref(c1)))
+    _lib.check(_lib.load().qsim_choose_layout(n, len(masks), _lib.ptr(masks), model["top"], _lib.ptr(bit), _lib.ptr(pair), _lib.ptr(tri),
+                                              seed, sweeps, _lib.ptr(out), C.byref(c0), C.byref(c1)))
     base = model["c0"] * len(tiles)
     return [int(x) for x in out], c0.value + base, c1.value + base

@@ -94,8 +94,7 @@ def test_nonlocal_bit_fails():
             z = np.array([0, zm], dtype=np.uint64)
             out = np.zeros(2)
             passes = C.c_int(-1)
-            rc = lib.qsim_expectation_pauli(c._h, 2, x.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p),
-                                            out.ctypes.data_as(C.c_void_p), C.byref(passes))
+            rc = lib.qsim_expectation_pauli(c._h, 2, _lib.ptr(x), _lib.ptr(z), _lib.ptr(out), C.byref(passes))
             assert rc == _lib.QSIM_ERR_NONLOCAL
         with pytest.raises(NotImplementedError):
             c.expectation_pauli([1 << 8], [0])

@@ -187,8 +187,7 @@ def test_single_pass_both_ends_and_argument_checks():
         io.dst, io.dst_m, io.own_pattern = buf0._h, 1, -1
         io.dst_bits[0] = 13
         with pytest.raises(ValueError, match="struct_size"):
-            _lib.check(_lib.load().qsim_apply_ops_io(state._h, len(nq), nq.ctypes.data_as(C.c_void_p), qs.ctypes.data_as(C.c_void_p),
-                                                     mats.ctypes.data_as(C.c_void_p), C.byref(io), None))
+            _lib.check(_lib.load().qsim_apply_ops_io(state._h, len(nq), _lib.ptr(nq), _lib.ptr(qs), _lib.ptr(mats), C.byref(io), None))
     # ... and the tiles of the first passes may be named through it (any masks: useless ones are ignored)
     state.upload(psi0)
     hints = np.array([(1 << 5) | (1 << 9) | 0b11111 << 6, 1 << 13, 0], dtype=np.uint64)

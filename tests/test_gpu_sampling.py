@@ -196,7 +196,7 @@ def test_errors():
         c.sample([-0.0])
         r, out = np.full(4, 0.5), np.zeros(4, dtype=np.uint64)
         total, passes = C.c_double(), C.c_int()
-        rp, op = r.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+        rp, op = _lib.ptr(r), _lib.ptr(out)
         assert lib.qsim_sample(c._h, (1 << 24) + 1, rp, op, C.byref(total), C.byref(passes)) == _lib.QSIM_ERR_INVALID
         assert b"2^24" in lib.qsim_last_error()
         assert lib.qsim_sample(c._h, 4, rp, None, C.byref(total), C.byref(passes)) == _lib.QSIM_ERR_INVALID

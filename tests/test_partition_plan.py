@@ -2,17 +2,14 @@
 what `qsim_plan_peek_pass` answers, and that a planned partition schedule -- executed step by step on a full state vector
 with the re-layouts as qubit swaps -- is the circuit (amplitudes against the oracle), for every circuit family, 2 / 4 / 8
 ranks, every thin-pass threshold."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from oracle import dense_oracle as orc
-from quantum_simulations_amd import _lib
 from quantum_simulations_amd import circuits as gen
 from quantum_simulations_amd.circuit.fusion import fuse_1q_ops
 from quantum_simulations_amd.circuit.io import validate_circuit_dict
-from quantum_simulations_amd.kernel import gates as gt
+from quantum_simulations_amd.kernel import gates as gt, planner
 from quantum_simulations_amd.kernel.device import pack_ops
 from quantum_simulations_amd.runner import partition_plan as pp
 
@@ -23,24 +20,13 @@ def _ops(cd):
 
 
 def _peek(k, n, ops, done=None, avoid=0, hint=0):
-    nq, qs, mats = pack_ops(ops)
     done = np.zeros(len(ops), dtype=np.uint8) if done is None else np.asarray(done, dtype=np.uint8)
-    members = np.zeros(max(1, len(ops)), dtype=np.int32)
-    mask, need, count = C.c_uint64(), C.c_uint64(), C.c_int32()
-    _lib.check(_lib.load().qsim_plan_peek_pass(k, n, len(nq), nq.ctypes.data_as(C.c_void_p), qs.ctypes.data_as(C.c_void_p),
-                                               mats.ctypes.data_as(C.c_void_p), done.ctypes.data_as(C.c_void_p), avoid, hint,
-                                               C.byref(mask), C.byref(need), C.byref(count), members.ctypes.data_as(C.c_void_p)))
-    return int(mask.value), int(need.value), [int(i) for i in members[:count.value]]
+    return planner.peek_pass(k, n, *pack_ops(ops), done, np.zeros(max(1, len(ops)), dtype=np.int32), avoid, hint)
 
 
 def _first_pass_of_a_full_plan(k, ops):
-    nq, qs, mats = pack_ops(ops)
-    count = C.c_int32()
-    images = np.zeros((64, 4096), dtype=np.uint8)
-    _lib.check(_lib.load().qsim_plan_ops(k, len(nq), nq.ctypes.data_as(C.c_void_p), qs.ctypes.data_as(C.c_void_p),
-                                         mats.ctypes.data_as(C.c_void_p), images.ctypes.data_as(C.c_void_p), images.nbytes, C.byref(count)))
-    T = int(images[0, 12:16].view("<i4")[0])
-    return sum(1 << int(b) for b in images[0, 16:16 + T - 3]), count.value
+    images = planner.plan_ops(k, ops)
+    return int(planner.tile_masks(images)[0]), len(images)
 
 
 def test_peek_is_the_first_pass_of_a_full_plan_when_nothing_is_global():

@@ -9,34 +9,22 @@ import pytest
 
 from oracle import dense_oracle as orc
 from quantum_simulations_amd import _lib
+from quantum_simulations_amd._lib import ptr as _ptr
+from quantum_simulations_amd.kernel import planner
 from quantum_simulations_amd.kernel.device import pack_ops
 from tests import tile_interpreter as ti
 from tests.test_gpu_kernels import _rand_state, _random_ops
 
 
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def search(n, ops, beam=0):
     """(reported pass count, tile masks) of the searching builder"""
-    nq, qubits, mats = pack_ops(ops)
-    count = C.c_int32()
-    out = np.zeros(len(nq), dtype=np.uint64)
-    _lib.check(_lib.load().qsim_plan_search(n, len(nq), _ptr(nq), _ptr(qubits), _ptr(mats), beam, _ptr(out), len(out), C.byref(count)))
-    return count.value, out[:count.value].copy()
+    masks = planner.search_tiles(n, ops, beam)
+    return len(masks), masks
 
 
 def plan_tiled(n, ops, masks):
     """pass images of `ops` under the named tiles (qsim_plan_ops_tiled)"""
-    nq, qubits, mats = pack_ops(ops)
-    lib = _lib.load()
-    count = C.c_int32()
-    args = (n, len(nq), _ptr(nq), _ptr(qubits), _ptr(mats), len(masks), _ptr(masks))
-    _lib.check(lib.qsim_plan_ops_tiled(*args, None, 0, C.byref(count)))
-    out = np.zeros(count.value, dtype=ti._IMAGE)
-    _lib.check(lib.qsim_plan_ops_tiled(*args, _ptr(out), out.nbytes, C.byref(count)))
-    return out
+    return planner.plan_ops(n, ops, masks)
 
 
 def _commuting_ops(n, seed, n_hubs=40):

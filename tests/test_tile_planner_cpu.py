@@ -398,25 +398,21 @@ def test_planning_time_per_pass_is_bounded_on_long_lists():
     The scans now stop `plan_scan_window` waiting ops behind the front (csrc/tile_planner.h).  Budget: 6 ms per pass
     (measured 1.4-1.6 ms on the idle build container, up to 4 under a parallel test run; the unbounded scan took 7.5-12)
     -- and no more passes than the unbounded scan needed (100)."""
-    import ctypes as C
     import time
 
-    from quantum_simulations_amd import _lib
+    from quantum_simulations_amd.kernel import planner
     from quantum_simulations_amd.kernel.device import pack_ops
     if os.environ.get("QSIM_PLANNER_CHILD"):
         pytest.skip("pass count and budget are those of the default planner, not of a forced look-ahead setting")
     n = 28
-    nq, qubits, mats = pack_ops(_long_list_with_a_control_only_qubit(n, 4000, 1))
-    lib = _lib.load()
-    k = C.c_int32()
+    packed = pack_ops(_long_list_with_a_control_only_qubit(n, 4000, 1))
     best = 1e9
     for _ in range(3):
         t0 = time.perf_counter()
-        _lib.check(lib.qsim_plan_ops(n, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p),
-                                     mats.ctypes.data_as(C.c_void_p), None, 0, C.byref(k)))
+        k = planner.pass_count(n, packed)
         best = min(best, time.perf_counter() - t0)
-    assert k.value <= 102, k.value
-    assert best / k.value < 6e-3, f"{best / k.value * 1e3:.2f} ms of planning per pass"
+    assert k <= 102, k
+    assert best / k < 6e-3, f"{best / k * 1e3:.2f} ms of planning per pass"
 
 
 def test_bounded_scan_plans_equal_the_oracle_on_lists_longer_than_the_window():

@@ -8,15 +8,11 @@ the CPU without a GPU.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from quantum_simulations_amd import _lib
-from quantum_simulations_amd.kernel.device import pack_ops
+from quantum_simulations_amd.kernel import planner
+from quantum_simulations_amd.kernel.planner import IMAGE_BYTES, PASS_IMAGE as _IMAGE, STREAM_OFF  # noqa: F401  (the pass image's layout)
 
-IMAGE_BYTES = 4096
-STREAM_OFF = 192                   # byte offset of the first record (csrc/tile_kernel.h)
 OPC = dict(DENSE1=1, SWAP1=10, ANTI1=19, PHASE=28, DENSE2=36, REAL1=45, YLIKE1=54, PHASE_NEG=63,
            PHASE_I=71, PHASE_NI=79, DIAGR=87, PRED_OUTER=91, PRED_LANE=92, GROUP=93, GROUP_FIRST=94, END=95,
            HAD1=96, SCALE=105, ASWAP1=106, GROUP_DIRECT=115, END_DIRECT=116, PRED_OUTER_ZERO=117)
@@ -27,13 +23,6 @@ _FAMILIES = ("DENSE1", "SWAP1", "ANTI1", "PHASE", "DENSE2", "REAL1", "YLIKE1", "
 # a register mask, the four merged-run shapes, one
 FAMILY_WIDTH = {f: (9 if f in ("DENSE1", "SWAP1", "ANTI1", "DENSE2", "REAL1", "YLIKE1", "HAD1", "ASWAP1")
                     else 8 if f.startswith("PHASE") else 4 if f == "DIAGR" else 1) for f in _FAMILIES}
-_IMAGE = np.dtype([("amp", "<u8"), ("nrec", "<i4"), ("T", "<i4"), ("h", "u1", (11,)), ("order", "u1"), ("ntiles", "<u4"),
-                   ("lay_in", "u1", (12,)), ("lay_out", "u1", (12,)), ("amp_out", "<u8"),
-                   # re-layout fused into a pass (planned images carry none: all zero)
-                   ("amp_out_own", "<u8"), ("own_mask", "<u8"), ("own_value", "<u8"),
-                   ("slab_in", "u1", (40,)), ("slab_out", "u1", (40,)), ("nbits", "u1"), ("perm", "u1"), ("reserved", "u1", (22,)),
-                   ("stream", "u1", (IMAGE_BYTES - STREAM_OFF,))])
-assert _IMAGE.itemsize == IMAGE_BYTES
 
 
 def lds_slot(t: int) -> int:
@@ -122,16 +111,7 @@ def records(img):
 
 def plan(n_qubits: int, ops) -> np.ndarray:
     """ops [(qubits, U)] -> array of pass images (planned by the C library, no device involved)."""
-    nq, qubits, mats = pack_ops(ops)
-    lib = _lib.load()
-    n_passes = C.c_int32()
-    _lib.check(lib.qsim_plan_ops(n_qubits, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p),
-                                 mats.ctypes.data_as(C.c_void_p), None, 0, C.byref(n_passes)))
-    out = np.zeros(n_passes.value, dtype=_IMAGE)
-    _lib.check(lib.qsim_plan_ops(n_qubits, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p),
-                                 mats.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), out.nbytes,
-                                 C.byref(n_passes)))
-    return out
+    return planner.plan_ops(n_qubits, ops)
 
 
 def _apply_1q(psi, idx, t_bit, U, cond_mask, zero_mask=0):
@@ -165,7 +145,7 @@ def run_pass(psi: np.ndarray, img) -> int:
     T = int(img["T"])
     n = int(np.log2(psi.size))
     idx = np.arange(psi.size, dtype=np.int64)
-    h = [int(x) for x in img["h"][:T - 3]]
+    h = planner.tile_bits(img)
     assert sorted(set(h)) == h and all(3 <= b < n for b in h), h       # ascending, distinct, above the low bits
 
     def abs_bit(tile_bit: int) -> int:

@@ -12,24 +12,15 @@ ROOT = Path(__file__).resolve().parent.parent
 LIB = os.environ.get("QSIM_LIBRARY") or str(ROOT / "quantum_simulations_amd" / "libqsim_hip_probes.so")
 
 CHILD = r"""
-import ctypes as C, json, sys
+import json, sys
 sys.path.insert(0, %r)
-from quantum_simulations_amd import _lib
 from quantum_simulations_amd.circuits import random_1q_cx_circuit, random_clifford_t_circuit, generate_ghz_qft
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.circuit.fusion import batch_levels
-from quantum_simulations_amd.kernel.device import pack_ops
+from quantum_simulations_amd.kernel import planner
 n = int(sys.argv[1])
-lib = _lib.load()
-def count(cd):
-    total = 0
-    for p in batch_levels(levelize(validate_circuit_dict(cd)), n):      # what SingleGpuEngine.plan hands to qsim_apply_ops
-        nq, qubits, mats = pack_ops(p["local_ops"])
-        k = C.c_int32()
-        _lib.check(lib.qsim_plan_ops(n, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p),
-                                     mats.ctypes.data_as(C.c_void_p), None, 0, C.byref(k)))
-        total += k.value
-    return total
+def count(cd):      # over what SingleGpuEngine.plan hands to qsim_apply_ops
+    return sum(planner.pass_count(n, p["local_ops"]) for p in batch_levels(levelize(validate_circuit_dict(cd)), n))
 out = {}
 out["bench"] = count(random_1q_cx_circuit(n, depth=40))
 out["random8"] = [count(random_1q_cx_circuit(n, depth=40, seed=s)) for s in range(1, 9)]

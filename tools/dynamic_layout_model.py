@@ -11,12 +11,12 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from quantum_simulations_amd.circuits import random_1q_cx_circuit, random_clifford_t_circuit
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.circuit.fusion import batch_levels
-from quantum_simulations_amd.runner.engine import _planned_tile_masks
+from quantum_simulations_amd.kernel import planner
 from quantum_simulations_amd.runner import tile_layout
 n = int(sys.argv[1]); fam = sys.argv[2] if len(sys.argv) > 2 else "rand"
 cd = random_1q_cx_circuit(n, depth=40) if fam == "rand" else random_clifford_t_circuit(n, depth=60)
 ops = [p["local_ops"] for p in batch_levels(levelize(validate_circuit_dict(cd)), n)][0]
-masks = _planned_tile_masks(n, ops)
+masks = planner.tile_masks(planner.plan_ops(n, ops))
 tiles = [[b for b in range(3, n) if (int(m) >> b) & 1] for m in masks]
 print(len(tiles), "tiles")
 model = tile_layout.model_for(n)

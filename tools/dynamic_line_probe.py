@@ -6,7 +6,6 @@ library's planner: plan the remaining ops, take the first pass, decide its membe
 admissibility rule (restated below, record budget ignored), choose the next three line qubits among the tile's eleven by
 one-step look-ahead (the triple whose next pass holds the most ops), relabel, repeat.
     python tools/dynamic_line_probe.py [n] [seed ...]"""
-import ctypes as C
 import itertools
 import sys
 import time
@@ -16,13 +15,11 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from quantum_simulations_amd import _lib  # noqa: E402
 from quantum_simulations_amd.circuit.fusion import batch_levels  # noqa: E402
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict  # noqa: E402
 from quantum_simulations_amd.circuits import random_1q_cx_circuit  # noqa: E402
-from quantum_simulations_amd.kernel.device import pack_ops  # noqa: E402
+from quantum_simulations_amd.kernel import planner  # noqa: E402
 
-lib = _lib.load()
 LOW = 3
 
 
@@ -66,18 +63,12 @@ def members_of(ops, tile, nmax=128):
 
 def first_pass(n, ops_list, label):
     """(tile as logical qubits, planned pass count) of the first pass the library plans for the ops under `label` (qubit -> bit)"""
-    nq, qubits, mats = pack_ops([([label[q] for q in qs], U) for qs, U in ops_list])
-    count = C.c_int32()
-    args = (n, len(nq), nq.ctypes.data_as(C.c_void_p), qubits.ctypes.data_as(C.c_void_p), mats.ctypes.data_as(C.c_void_p))
-    if len(nq) < 2:
+    if len(ops_list) < 2:
         return set(range(n)), 1
-    _lib.check(lib.qsim_plan_ops(*args, None, 0, C.byref(count)))
-    img = np.zeros((count.value, 4096), dtype=np.uint8)
-    _lib.check(lib.qsim_plan_ops(*args, img.ctypes.data_as(C.c_void_p), img.nbytes, C.byref(count)))
-    T = int(img[0, 12:16].view("<i4")[0])
-    bits = {int(b) for b in img[0, 16:16 + T - 3]} | {0, 1, 2}
+    images = planner.plan_ops(n, [([label[q] for q in qs], U) for qs, U in ops_list])
+    bits = set(planner.tile_bits(images[0])) | {0, 1, 2}
     inv = {b: q for q, b in label.items()}
-    return {inv[b] for b in bits}, count.value
+    return {inv[b] for b in bits}, len(images)
 
 
 def label_with_line(n, line):

@@ -13,6 +13,7 @@ sys.path.insert(0, str(ROOT))
 from quantum_simulations_amd.circuit.fusion import batch_levels  # noqa: E402
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict  # noqa: E402
 from quantum_simulations_amd.circuits import random_1q_cx_circuit  # noqa: E402
+from quantum_simulations_amd.kernel import planner  # noqa: E402
 from quantum_simulations_amd.kernel.device import DeviceChunk, pack_ops  # noqa: E402
 from quantum_simulations_amd.runner import engine as eng_mod, tile_layout  # noqa: E402
 
@@ -35,7 +36,7 @@ cands = [0] + [int(i) for i in np.flatnonzero(counts == best)][:10] + [int(i) fo
 for f in cands:
     first = [int(x) for x in layouts[f]]
     moved = [[([first[q] for q in qs], U) for qs, U in ops] for ops in batches]
-    masks = [eng_mod._planned_tile_masks(n, ops) for ops in moved]
+    masks = [planner.tile_masks(planner.plan_ops(n, ops)) for ops in moved]
     tiles = [[b for b in range(3, n) if (int(m) >> b) & 1] for ms in masks for m in ms]
     second, c0, c1 = min((tile_layout.choose_layout(tiles, n, seed=s) for s in range(1, 9)), key=lambda r: r[2])
     l2p = [second[first[q]] for q in range(n)]

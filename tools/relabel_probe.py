@@ -18,9 +18,8 @@ sys.path.insert(0, str(ROOT))
 from quantum_simulations_amd.circuit.fusion import batch_levels  # noqa: E402
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict  # noqa: E402
 from quantum_simulations_amd.circuits import random_1q_cx_circuit  # noqa: E402
+from quantum_simulations_amd.kernel import planner  # noqa: E402
 from quantum_simulations_amd.kernel.device import pack_ops  # noqa: E402
-from quantum_simulations_amd.runner.engine import make_engine  # noqa: E402
-from tests import tile_interpreter as ti  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 28
 seeds = [int(s) for s in sys.argv[2:]] or [20260228, 1, 2, 3]
@@ -54,8 +53,7 @@ w = np.linalg.solve(A, X.T @ y)
 def tiles_of(cd):
     out = []
     for p in batch_levels(levelize(validate_circuit_dict(cd)), n):
-        for img in ti.plan(n, p["local_ops"]):
-            out.append([int(b) for b in img["h"][:8]])
+        out += [planner.tile_bits(img) for img in planner.plan_ops(n, p["local_ops"])]
     return out
 
 
@@ -100,7 +98,7 @@ def batches_of(cd):
 
 def masks_of(ops_list):
     """tile masks per batch, from the CPU planner"""
-    return [np.array([sum(1 << int(b) for b in img["h"][:8]) for img in ti.plan(n, ops)], dtype=np.uint64) for ops in ops_list]
+    return [planner.tile_masks(planner.plan_ops(n, ops)) for ops in ops_list]
 
 
 for seed in seeds:
