@@ -191,6 +191,15 @@ int qsim_plan_peek_pass(int n_local_qubits, int n_total_qubits, int n_ops, const
 int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, int beam,
                      uint64_t* out_masks, int out_capacity, int32_t* n_passes);
 
+/* The op list a plan for repeated execution is made from: X / Y gates pushed into their neighbours (an X is a bit flip of
+ * the index: it passes CNOTs and diagonal gates and is absorbed by the next dense 1q gate), CNOTs with an exact H on the
+ * target turned into CZ.  Same packed format in and out, same amplitudes up to the rounding of the 2x2 products; fewer ops
+ * that need their target inside a tile, hence fewer fused passes.  out_capacity: ops the output arrays hold (2 * n_ops +
+ * n_qubits always suffices; too small is an error, *n_out then says how many).  need_tile: NULL or two counts (before,
+ * after).  Host only. */
+int qsim_rewrite_ops(int n_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, int32_t* out_nq,
+                     int32_t* out_qubits, double* out_mats, int out_capacity, int32_t* n_out, int32_t* need_tile);
+
 /* Pass counts of ONE op list under n_layouts qubit layouts (layouts[l * n_local_qubits + q] = index bit of logical qubit q),
  * planned in parallel on n_threads host threads, no device: the pass builder's result depends on which qubits live on the
  * three line bits (they belong to every tile), so a host that is free to choose the layout tries several. */

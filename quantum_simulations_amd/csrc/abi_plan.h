@@ -71,6 +71,34 @@ int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int
   return QSIM_OK;
 }
 
+// The op list a plan for repeated execution is made from (op_rewrite.h): X / Y gates pushed into their neighbours, CNOTs with
+// an exact H on the target turned into CZ.  Same packed format in and out, same amplitudes (up to the rounding of the 2x2
+// products); identities drop out.  out_capacity: ops the three output arrays have room for (2 * n_ops + n_qubits is always
+// enough); too small a buffer is an error and nothing is written.  need_tile (optional, two counts): the ops that need
+// their target inside the tile, before and after.  Host only, no device, deterministic, linear in n_ops.
+int qsim_rewrite_ops(int n_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, int32_t* out_nq,
+                     int32_t* out_qubits, double* out_mats, int out_capacity, int32_t* n_out, int32_t* need_tile) {
+  if (!n_out || out_capacity < 0 || (out_capacity && (!out_nq || !out_qubits || !out_mats)))
+    return fail(QSIM_ERR_INVALID, "qsim_rewrite_ops: bad arguments");
+  if (n_qubits < 1 || n_qubits > 63) return fail(QSIM_ERR_INVALID, "qsim_rewrite_ops: bad qubit count %d", n_qubits);
+  int rc = check_op_list(n_ops, nq, qubits, mats, n_qubits, kQubitOfState);
+  if (rc) return rc;
+  std::vector<RwOp> ops;
+  int need_in = 0, need_out = 0;
+  rewrite_op_list(n_qubits, n_ops, nq, qubits, mats, &ops, &need_in);
+  *n_out = (int32_t)ops.size();
+  if (ops.size() > (size_t)out_capacity) return fail(QSIM_ERR_INVALID, "qsim_rewrite_ops: output buffer too small (%d ops)", (int)ops.size());
+  for (size_t i = 0; i < ops.size(); ++i) {
+    out_nq[i] = ops[i].nq;
+    out_qubits[2 * i] = ops[i].q[0];
+    out_qubits[2 * i + 1] = ops[i].nq == 2 ? ops[i].q[1] : 0;
+    std::memcpy(out_mats + 32 * i, ops[i].U, sizeof ops[i].U);
+    need_out += rw_needs_tile(ops[i]);
+  }
+  if (need_tile) { need_tile[0] = need_in; need_tile[1] = need_out; }
+  return QSIM_OK;
+}
+
 // The NEXT fused pass of a partly executed op list on a partitioned state (the partition planner's view of the pass builder,
 // runner/partition_plan.py): qubits are index bits of the WHOLE state, the bits >= n_local_qubits are rank bits -- an op may
 // use them as controls or phase bits (the rank applies or skips it by its own bits) but an op that TARGETS one has to wait

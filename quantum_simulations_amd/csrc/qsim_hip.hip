@@ -48,6 +48,7 @@ typedef unsigned long long u64;
 #include "tile_kernel.h"
 #include "tile_planner.h"
 #include "tile_search.h"
+#include "op_rewrite.h"
 #include "misc_kernels.h"
 #include "dense_kernels.h"
 #include "expect_kernels.h"

@@ -1,5 +1,6 @@
 """The host planner of libqsim_hip.so in Python: what the pass builder would do with an op list, without a device
-(csrc/abi_plan.h: qsim_plan_ops, qsim_plan_ops_tiled, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass).
+(csrc/abi_plan.h: qsim_plan_ops, qsim_plan_ops_tiled, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass,
+qsim_rewrite_ops).
 
 A thin binding.  `ops` is [(qubits, U), ...] or the tuple `pack_ops` returns (`device.as_packed`).  Return codes become
 the exceptions of `_lib.check` and nothing else is read into them: what a caller makes of a list too short to plan is
@@ -80,6 +81,23 @@ def search_tiles(n: int, ops, beam: int = 0) -> np.ndarray:
     out = np.zeros(len(nq), dtype=np.uint64)
     _lib.check(_lib.load().qsim_plan_search(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), beam, ptr(out), len(out), C.byref(count)))
     return out[:count.value].copy()
+
+
+def rewrite_ops(n: int, ops, stats: dict = None) -> list:
+    """`ops` rewritten for planning (qsim_rewrite_ops, csrc/op_rewrite.h): X / Y gates pushed into their neighbours, CNOTs
+    with an exact H on the target turned into CZ -- the same amplitudes from fewer ops that need their target inside a
+    tile.  Returns [(qubits, U), ...]; `stats`, when given, receives ops_in, ops_out, need_tile_in, need_tile_out."""
+    nq, qubits, mats = as_packed(ops)
+    room = 2 * len(nq) + n
+    out_nq, out_q = np.zeros(room, dtype=np.int32), np.zeros(2 * room, dtype=np.int32)
+    out_m = np.zeros((room, 16), dtype=np.complex128)
+    count, need = C.c_int32(), np.zeros(2, dtype=np.int32)
+    _lib.check(_lib.load().qsim_rewrite_ops(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), ptr(out_nq), ptr(out_q), ptr(out_m),
+                                            room, C.byref(count), ptr(need)))
+    if stats is not None:
+        stats.update(ops_in=len(nq), ops_out=int(count.value), need_tile_in=int(need[0]), need_tile_out=int(need[1]))
+    return [([int(out_q[2 * i])], out_m[i, :4].reshape(2, 2).copy()) if out_nq[i] == 1 else
+            ([int(out_q[2 * i]), int(out_q[2 * i + 1])], out_m[i].reshape(4, 4).copy()) for i in range(count.value)]
 
 
 def count_layouts(n: int, ops, layouts, threads: int) -> np.ndarray:
