@@ -68,10 +68,6 @@ static bool rw_make_phase2(int a, int b, double2 p, RwOp* o) {   // diag(1, 1, 1
   return classify_op(2, o->q, o->U, &o->f);
 }
 static void rw_1q_matrix(const RwOp& o, double2 g[4]) { op_1q_matrix(o.f, g); }
-static void rw_mul2(const double2* a, const double2* b, double2* out) {   // out = a b
-  for (int r = 0; r < 2; ++r)
-    for (int c = 0; c < 2; ++c) out[2 * r + c] = cadd(cmul(a[2 * r], b[c]), cmul(a[2 * r + 1], b[2 + c]));
-}
 // exactly the Hadamard matrix (1/sqrt(2) to the last bit, either rounding of it)
 static bool rw_is_h(const RwOp& o) {
   if (rw_class(o) != RW_DENSE1) return false;
@@ -137,7 +133,7 @@ static void rw_h_conversion(const std::vector<RwOp>& list, std::vector<RwOp>* re
         double2 g[4], hm[4], prod[4];
         rw_1q_matrix(in[(size_t)j], g);
         rw_1q_matrix(h, hm);
-        rw_mul2(g, hm, prod);
+        mul2x2(g, hm, prod);
         if (!rw_make_1q(t, prod, &in[(size_t)j])) in_dead[(size_t)j] = 1;
       } else {
         push(h);
@@ -152,7 +148,7 @@ static void rw_h_conversion(const std::vector<RwOp>& list, std::vector<RwOp>* re
         double2 g[4], hm[4], prod[4];
         rw_1q_matrix(out[(size_t)p], g);
         rw_1q_matrix(h, hm);
-        rw_mul2(hm, g, prod);
+        mul2x2(hm, g, prod);
         RwOp fused;
         if (rw_make_1q(t, prod, &fused)) { fused.f.absorbed = 0; out[(size_t)p] = fused; }
         else drop_last_1q(t);

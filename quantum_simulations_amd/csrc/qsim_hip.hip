@@ -46,9 +46,13 @@ typedef unsigned long long u64;
 #include "gate_kernels.h"
 #include "gate_plan.h"
 #include "tile_kernel.h"
+// the host planner of the fused passes (no device call in any of these), then what launches its passes
+#include "tile_ops.h"
+#include "tile_groups.h"
 #include "tile_planner.h"
 #include "tile_search.h"
 #include "op_rewrite.h"
+#include "tile_launch.h"
 #include "misc_kernels.h"
 #include "dense_kernels.h"
 #include "expect_kernels.h"

@@ -1,0 +1,377 @@
+// tile_launch.h -- a planned pass on its way to the device: the launch of k_tile, the re-layout fused into the ends of an
+// op list, the plan cache and run_fused.  Everything of the fused passes that touches the device lives here.
+// Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
+// Tile order of a launch (k_tile).  Gate-less passes depend strongly on it (profiles/r02f_tile_order_probe.txt:
+// 2.38 -> 1.58 ms for tile bits {3,4,5,6,18,19,20,21} with bit-reversed order, 1.90 -> 1.70 ms averaged over ten
+// tile-bit sets with a bits-above-18 rule), but passes that carry their gates do not: per pass the best of the
+// three orders is within 2 % of consecutive tiles on the bench circuit (profiles/r02i_pass_times_by_order.txt),
+// so the product launches consecutive tiles; the other orders stay reachable in the probe build.
+static int tile_order_for(const TileArgs&, int) {
+#ifdef QSIM_PROBES
+  if (tuning().tile_order >= 0) return tuning().tile_order;
+#endif
+  return 0;
+}
+
+// physical bit of logical index bit b under a slab layout (host mirror of k_tile's slab_base)
+static uint8_t slab_position(const TileSlab& t, int b) {
+  for (int j = 0; j < 3; ++j) if (t.bit[j] == b) return (uint8_t)(t.top + j);
+  for (int i = 0; i < 4; ++i) if ((t.field[i] >> b) & 1) return (uint8_t)(b - i);
+  return (uint8_t)b;
+}
+
+// ---- probes of a launch (tools/): empty in the product library -------------------------------------------------------
+// memory probe (WRONG results): QSIM_DEBUG_OUT_OF_PLACE: tiles are stored into a second buffer
+static void probe_out_of_place(TileArgs* args, const qsim_chunk* c) {
+#ifdef QSIM_PROBES
+  if (getenv("QSIM_DEBUG_OUT_OF_PLACE")) {
+    static double2* other = nullptr;
+    static size_t other_bytes = 0;
+    const size_t need = sizeof(double2) << c->k;
+    if (other_bytes < need) { if (other) (void)hipFree(other); (void)hipMalloc((void**)&other, need); other_bytes = need; }
+    args->amp_out = other;
+  }
+#endif
+}
+// in-kernel stamps: QSIM_DEBUG_STAMPS=<file> dumps entry / loaded / engine / stored cycle stamps of every 64th workgroup
+static void probe_stamps_arm(TileArgs* args, u64 ntiles, hipStream_t stream) {
+#ifdef QSIM_PROBES
+  static unsigned long long* dbuf = nullptr;
+  static const char* path = getenv("QSIM_DEBUG_STAMPS");
+  if (path && !dbuf) (void)hipMalloc((void**)&dbuf, sizeof(unsigned long long) * 4 * ((1u << 22)));
+  unsigned long long* p = path ? dbuf : nullptr;
+  std::memcpy(reinterpret_cast<unsigned char*>(args) + kTileArgBytes - 8, &p, 8);
+  if (p) (void)hipMemsetAsync(p, 0, sizeof(unsigned long long) * 4 * (ntiles / 64 + 1), stream);
+#endif
+}
+static void probe_stamps_dump(const TileArgs& args, int nrec, u64 ntiles, hipStream_t stream) {
+#ifdef QSIM_PROBES
+  if (const char* path = getenv("QSIM_DEBUG_STAMPS")) {
+    unsigned long long* p = nullptr;
+    std::memcpy(&p, reinterpret_cast<const unsigned char*>(&args) + kTileArgBytes - 8, 8);
+    std::vector<unsigned long long> host(4 * (ntiles / 64 + 1));
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpy(host.data(), p, host.size() * 8, hipMemcpyDeviceToHost);
+    if (FILE* f = std::fopen(path, "a")) {
+      std::fprintf(f, "# pass nrec %d ntiles %llu\n", nrec, (u64)ntiles);
+      for (size_t i = 0; i + 3 < host.size(); i += 4)
+        if (host[i]) std::fprintf(f, "%llu %llu %llu %llu\n", host[i], host[i + 1], host[i + 2], host[i + 3]);
+      std::fclose(f);
+    }
+  }
+#endif
+}
+
+#ifndef QSIM_TILES_PER_WG
+#define QSIM_TILES_PER_WG 2
+#endif
+// the runtime cache policy and offset width as template arguments of k_tile<T, NT, WIDE, TPW, PART>
+template <int T, int TPW, bool PART>
+static void launch_k_tile(bool nt, bool wide, unsigned grid, hipStream_t stream, const TileArgs& args) {
+  if (nt && wide) hipLaunchKernelGGL((k_tile<T, true, true, TPW, PART>), dim3(grid), dim3(kTileThreads), 0, stream, args);
+  else if (nt) hipLaunchKernelGGL((k_tile<T, true, false, TPW, PART>), dim3(grid), dim3(kTileThreads), 0, stream, args);
+  else if (wide) hipLaunchKernelGGL((k_tile<T, false, true, TPW, PART>), dim3(grid), dim3(kTileThreads), 0, stream, args);
+  else hipLaunchKernelGGL((k_tile<T, false, false, TPW, PART>), dim3(grid), dim3(kTileThreads), 0, stream, args);
+}
+
+template <int T>
+static int launch_tile(const TileArgs& a, const qsim_chunk* c, hipStream_t stream, double alg_bytes) {
+  if constexpr (T > kTileBitsMax || T < kTileThreadBits) {
+    return fail(QSIM_ERR_INVALID, "internal: tile size %d not built", T);
+  } else {
+  if (a.nfix && (T != kTileBitsMax || a.nfix > 3 || c->k - T < a.nfix)) return fail(QSIM_ERR_INVALID, "internal: partial launch of a %d-bit tile", T);
+  const u64 ntiles = 1ull << (c->k - T - a.nfix);       // (a.nfix: the tiles of one destination slab of a fused re-layout)
+  if (ntiles > 0xFFFFFFFFull) return fail(QSIM_ERR_INVALID, "internal: too many tiles");
+  TileArgs args = a;
+  args.ntiles = (uint32_t)ntiles;
+  args.order = (uint8_t)((a.order & ~kTileOrderMask) | (tile_order_for(a, T) & kTileOrderMask));
+  args.nbits = (uint8_t)c->k;
+  if (!args.amp_out) args.amp_out = args.amp;
+  // a pass that reads / writes a re-laid-out buffer: the thread layouts become physical bit positions
+  for (int i = 0; i < T - kTileLow; ++i) {
+    if (args.perm & kTilePermIn) args.lay_in[i] = slab_position(args.slab_in, args.lay_in[i]);
+    if (args.perm & kTilePermOut) args.lay_out[i] = slab_position(args.slab_out, args.lay_out[i]);
+  }
+  probe_out_of_place(&args, c);
+  probe_stamps_arm(&args, ntiles, stream);
+  // thread part of an element offset: the first min(5, NH) bits of the load / store layouts: 32-bit addressing when
+  // all are < 28
+  bool wide = false;
+  for (int i = 0; i < kTileThreadBits - kTileLow && i < T - kTileLow; ++i) wide = wide || args.lay_in[i] >= 28 || args.lay_out[i] >= 28;
+  bool nt = c->span_bytes > tuning().mall_bytes;       // cache policy by state size (gate_plan.h)
+  if (tuning().force_nt >= 0) nt = tuning().force_nt != 0;
+  ProfileScope prof(6, alg_bytes, stream, nt, 32.0 * (double)(ntiles << T));
+  // Two tiles per workgroup, the second one's loads in flight while the first is computed on
+  // (profiles/r02r_ab_prefetch_before_engine.txt: -3.9 % per pass; 4 or 8 tiles per workgroup lose it again,
+  // profiles/r02z_ab_paired_stores.txt).  Also for the 64-bit-offset form (110 VGPRs: the 32 KiB of LDS admit four
+  // workgroups per CU, so 128 are there); not for small grids.
+  constexpr int TPW = QSIM_TILES_PER_WG;
+  const bool two = TPW > 1 && ntiles >= (u64)TPW * 4096;
+  const unsigned grid = (unsigned)(two ? ntiles / TPW : ntiles);
+  bool part = false;                                       // one destination slab: the PART instantiations (full tiles only)
+  if constexpr (T == kTileBitsMax) {
+    part = args.nfix != 0;
+    if (part && two) launch_k_tile<T, TPW, true>(nt, wide, grid, stream, args);
+    else if (part) launch_k_tile<T, 1, true>(nt, wide, grid, stream, args);
+  }
+  if (!part && two) launch_k_tile<T, TPW, false>(nt, wide, grid, stream, args);
+  else if (!part) launch_k_tile<T, 1, false>(nt, wide, grid, stream, args);
+  prof.done(stream);
+  HIP_TRY(hipGetLastError());
+  if (!part) probe_stamps_dump(args, a.nrec, ntiles, stream);
+  return QSIM_OK;
+  }
+}
+
+static int launch_tile_any(const TileArgs& a, int T, const qsim_chunk* c, hipStream_t stream, double alg_bytes) {
+  switch (T) {
+    case 8: return launch_tile<8>(a, c, stream, alg_bytes);
+    case 9: return launch_tile<9>(a, c, stream, alg_bytes);
+    case 10: return launch_tile<10>(a, c, stream, alg_bytes);
+    case 11: return launch_tile<11>(a, c, stream, alg_bytes);
+    case 12: return launch_tile<12>(a, c, stream, alg_bytes);
+  }
+  return fail(QSIM_ERR_INVALID, "internal: tile size %d", T);
+}
+
+// ---- re-layout fused into the first / last pass of an op list (qsim_apply_ops_io) -------------------------------
+// Slab layout of an all-to-all re-layout over the local bits `bits` (qsim_pack_all): amplitude i of the chunk sits at
+//   d * 2^(k - m) + (i with the m bits removed),   d = sum_j bit(i, bits[j]) << j
+// of the buffer, i.e. logical index bit bits[j] is physical bit k - m + j and the others close ranks.
+struct SlabLayout {
+  int m = 0;
+  int bits[3] = {0, 0, 0};
+};
+static void slab_descriptor(int k, const SlabLayout& L, TileSlab* t) {
+  int sorted[3] = {64, 64, 64};
+  for (int j = 0; j < L.m; ++j) sorted[j] = L.bits[j];
+  std::sort(sorted, sorted + L.m);
+  auto below = [](int b) -> u64 { return b >= 64 ? ~0ull : ((1ull << b) - 1); };
+  t->field[0] = below(sorted[0]);
+  for (int i = 1; i < 4; ++i) {
+    const int lo = sorted[i - 1], hi = i < 3 ? sorted[i] : 64;
+    t->field[i] = lo >= 64 ? 0 : (below(hi) & ~below(lo + 1));
+  }
+  for (int j = 0; j < 3; ++j) t->bit[j] = (uint8_t)(j < L.m ? L.bits[j] : 63);
+  t->top = (uint8_t)(k - L.m);
+  std::memset(t->pad, 0, sizeof t->pad);
+}
+struct FusedIo {
+  const qsim_chunk* src = nullptr;   // first pass reads this buffer (slab layout `in`) instead of the chunk
+  SlabLayout in;
+  qsim_chunk* dst = nullptr;         // last pass stores into this buffer in slab layout `out` ...
+  SlabLayout out;
+  qsim_chunk* dst_own = nullptr;     // ... except slab `own_pattern`, which goes to this one (same layout)
+  int own_pattern = -1;
+  bool parts = false;                // the slab-storing pass is not launched here: it is left pending in the chunk and
+                                     // launched slab by slab (qsim_apply_ops_io_part), so each slab's exchange can start early
+  bool fused_in = false, fused_out = false;   // results
+  bool own_in_chunk = false;         // result: the own slab went into the chunk itself (dst_own == src and ONE pass does it all)
+};
+
+// The slab-storing pass of an op list whose caller asked for the split form (qsim_ops_io::dst_parts): planned, not yet
+// launched.  The slabs are stored PIECE by piece: piece j = the j-th of 2^nb equal contiguous sub-ranges of EVERY slab
+// (the top nb index bits that are not slab bits have the value j), so the exchange of piece j uses all links at once
+// while the pieces behind it are still being computed.  The cut depends ONLY on (k, m, pieces asked for): every rank of a
+// multi-GPU run cuts alike whatever its own pass plan looks like (ranks plan different op lists: rank-bit phases,
+// controlled gates with a global control) -- the k-th transfer between two ranks always has the same size on both sides.
+// What a rank's plan decides is only how early its pieces are ready: kTile -- the top `nb_free` <= nb piece bits are not
+// tile bits of the pass, which then runs as 2^nb_free partial launches (a launch stores 2^(nb - nb_free) pieces at once;
+// nb_free = 0: one launch, everything ready with the first piece); kPack (nothing fusable: the state is final in the
+// chunk): one qsim_pack_all piece per call; kDone: stored already (passes that cannot be launched in part).
+struct PendingLast {
+  enum Mode { kNone = 0, kStashed, kTile, kPack, kDone };   // kStashed: launch_planned has put the pass here, the caller's slab description is still missing
+  int mode = kNone;
+  TileArgs a;
+  int T = 0;
+  double alg_bytes = 0;
+  int m = 0;
+  int32_t bits[3] = {0, 0, 0};
+  qsim_chunk* dst = nullptr;
+  qsim_chunk* dst_own = nullptr;
+  int own_pattern = -1;
+  int nb = 0;                        // piece bits: 2^nb pieces
+  int piece_bit[3] = {0, 0, 0};      // the top nb non-slab index bits, ascending (piece j: bit i of j <-> piece_bit[i])
+  int nb_free = 0;                   // kTile: how many of them, from the top, are no tile bits of the pass
+  unsigned stored = 0;               // bit j: piece j has been handed out
+  unsigned launched = 0;             // kTile: bit g: partial launch g (the top nb_free bits of the piece number) is queued
+};
+
+// 2^nb pieces for a request of `want` (1, 2, 4, 8): as many as asked for while a piece keeps >= 2^min_piece_bits amplitudes.
+static int piece_bits_for(int k, int m, int want, int min_piece_bits) {
+  int nb = 0;
+  while (nb < 3 && (2 << nb) <= want && (k - m) - (nb + 1) >= min_piece_bits && (k - m) - (nb + 1) >= kTileLow) ++nb;
+  return nb;
+}
+
+// The top nb index bits of a k-bit index that are none of the m slab bits, ascending (the piece bits of the split form).
+static void top_free_bits(int k, int m, const int32_t* slab_bits, int nb, int* out) {
+  for (int b = k - 1, found = 0; b >= 0 && found < nb; --b) {
+    bool slab = false;
+    for (int i = 0; i < m; ++i) slab = slab || slab_bits[i] == b;
+    if (!slab) out[nb - 1 - found++] = b;
+  }
+}
+
+static void plan_parts(PendingLast* p, int k, int want, const uint8_t* tile_high, int n_tile_high, int min_piece_bits) {
+  auto is_tile = [&](int b) { for (int j = 0; j < n_tile_high; ++j) if (tile_high[j] == b) return true; return false; };
+  p->nb = piece_bits_for(k, p->m, want, min_piece_bits);
+  top_free_bits(k, p->m, p->bits, p->nb, p->piece_bit);
+  p->nb_free = 0;
+  while (p->nb_free < p->nb && !is_tile(p->piece_bit[p->nb - 1 - p->nb_free])) ++p->nb_free;    // from the top
+  p->stored = p->launched = 0;
+}
+
+// One planned pass on its way to the device: buffers and the re-layout of the op list's ends (prepare_planned), then the
+// launch -- or, for the slab-storing pass of a split call, the stash (dispatch_planned).
+static void prepare_planned(qsim_chunk* c, TileArgs& a, int T, bool first, bool last, FusedIo* io) {
+  a.amp = c->amp;
+  a.amp_out = c->amp;
+  a.amp_out_own = nullptr;
+  a.perm = 0;
+  if (io && first && io->src) {
+    a.amp = io->src->amp;
+    a.perm |= kTilePermIn;
+    slab_descriptor(c->k, io->in, &a.slab_in);
+    io->fused_in = true;
+  }
+  if (io && last && io->dst) {
+    // the slab that stays is chosen per tile from the tile's base: its bits must lie outside the tile
+    bool clash = false;
+    for (int j = 0; j < T - kTileLow; ++j)
+      for (int i = 0; i < io->out.m; ++i) clash = clash || a.h[j] == io->out.bits[i];
+    if (!clash || io->own_pattern < 0) {
+      a.amp_out = io->dst->amp;
+      a.perm |= kTilePermOut;
+      slab_descriptor(c->k, io->out, &a.slab_out);
+      if (io->own_pattern >= 0) {
+        a.perm |= kTileOwnOut;
+        a.amp_out_own = io->dst_own->amp;
+        if (first && io->src && io->dst_own->amp == io->src->amp) {
+          // ONE pass reads the source buffer and stores the slabs, and the caller named the source as the place of the
+          // slab that stays (three shard-sized buffers per rank instead of four): a tile of that slab must not overwrite
+          // source lines other tiles still read -- it goes into the chunk itself, whose contents nobody needs now
+          a.amp_out_own = c->amp;
+          io->own_in_chunk = true;
+        }
+        a.own_mask = a.own_value = 0;
+        for (int i = 0; i < io->out.m; ++i) {
+          a.own_mask |= 1ull << io->out.bits[i];
+          if ((io->own_pattern >> i) & 1) a.own_value |= 1ull << io->out.bits[i];
+        }
+      }
+      io->fused_out = true;
+    }
+  }
+}
+
+static int dispatch_planned(qsim_chunk* c, TileArgs& a, int T, double alg_bytes, bool last, FusedIo* io) {
+  if (io && last && io->dst && io->parts && io->fused_out && T == kTileBitsMax) {
+    PendingLast* p = c->pending ? c->pending : (c->pending = new PendingLast());
+    p->mode = PendingLast::kStashed; p->a = a; p->T = T; p->alg_bytes = alg_bytes; p->launched = 0;
+    return QSIM_OK;                  // (qsim_apply_ops_io fills in the slab description and keeps it pending)
+  }
+  if (tuning().debug_stats < 2) return launch_tile_any(a, T, c, c->stream, alg_bytes);
+  // QSIM_DEBUG_STATS=2: time every pass synchronously and print its shape (profiling aid)
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+  (void)hipEventRecord(e0, c->stream);
+  const int rc = launch_tile_any(a, T, c, c->stream, alg_bytes);
+  (void)hipEventRecord(e1, c->stream);
+  (void)hipEventSynchronize(e1);
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  std::fprintf(stderr, "[qsim] timed pass: %.3f ms, %d records, high bits", ms, a.nrec);
+  for (int j = 0; j < T - kTileLow; ++j) std::fprintf(stderr, " %d", a.h[j]);
+  std::fprintf(stderr, "\n");
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  return rc;
+}
+
+static int launch_planned(qsim_chunk* c, TileArgs& a, int T, double alg_bytes, bool first, bool last, FusedIo* io) {
+  prepare_planned(c, a, T, first, last, io);
+  return dispatch_planned(c, a, T, alg_bytes, last, io);
+}
+
+// ---- plan cache ---------------------------------------------------------------------------------------------------
+// Runners execute the same op list again and again (a planned circuit repeated, one plan per chunk of a chunked run):
+// the pass images of the last few op lists are kept, keyed by the exact bytes of the call (local qubits, arities,
+// qubits, matrices), and launched again without planning.  Planning overlaps with the device for large states (the
+// images of pass p + 1 are made while pass p runs), so this matters where passes are short: 13 % of a step at 22
+// qubits, nothing at 28.  Images are stored without buffers or layouts: those are put in at
+// launch time (launch_planned), so one entry serves every chunk of its size and every re-layout.
+struct CachedPass { TileArgs a; int T; double alg_bytes; };
+struct CachedPlan {
+  int k = 0;
+  u64 hash = 0;
+  std::vector<unsigned char> key;        // nq | qubits | mats of the call
+  std::vector<CachedPass> passes;
+};
+constexpr size_t kPlanCacheEntries = 8;
+constexpr size_t kPlanCacheMaxKeyBytes = 4u << 20;      // longer op lists are planned every time
+static std::list<CachedPlan> g_plan_cache;             // most recently used first
+static std::mutex g_plan_cache_mu;
+
+// `defer` (an op list whose source arrives in pieces, qsim_ops_io::src_parts): the passes are planned and prepared (buffers
+// in) but not launched; the caller launches them when the source is complete.
+static int run_fused(qsim_chunk* c, const std::vector<FusedOp>& ops, int* n_passes, FusedIo* io = nullptr,
+                     int n_ops = 0, const int32_t* nq = nullptr, const int32_t* qubits = nullptr, const double* mats = nullptr,
+                     std::vector<CachedPass>* defer = nullptr, const TileHint* hint = nullptr) {
+  // key of the call (only when the caller handed the raw op list over)
+  std::vector<unsigned char> key;
+  u64 hash = 0;
+  const size_t hint_bytes = hint ? sizeof(uint64_t) * (size_t)hint->n : 0;
+  const size_t key_bytes = (size_t)n_ops * (sizeof(int32_t) * 3 + sizeof(double) * 32) + hint_bytes;
+  const bool cacheable = nq && qubits && mats && n_ops > 0 && key_bytes <= kPlanCacheMaxKeyBytes && tuning().debug_stats == 0 &&
+                         tuning().debug_skip_gates == 0;     // (probe passes take their tile bits from the environment at plan time)
+  if (cacheable) {
+    key.resize(key_bytes);
+    unsigned char* w = key.data();
+    std::memcpy(w, nq, sizeof(int32_t) * (size_t)n_ops); w += sizeof(int32_t) * (size_t)n_ops;
+    std::memcpy(w, qubits, sizeof(int32_t) * 2 * (size_t)n_ops); w += sizeof(int32_t) * 2 * (size_t)n_ops;
+    std::memcpy(w, mats, sizeof(double) * 32 * (size_t)n_ops); w += sizeof(double) * 32 * (size_t)n_ops;
+    if (hint_bytes) std::memcpy(w, hint->masks, hint_bytes);
+    hash = fnv1a(key.data(), key.size(), 1469598103934665603ull ^ (u64)c->k);
+    std::vector<CachedPass> hit;
+    {
+      std::lock_guard<std::mutex> lock(g_plan_cache_mu);
+      for (auto it = g_plan_cache.begin(); it != g_plan_cache.end(); ++it)
+        if (it->hash == hash && it->k == c->k && it->key == key) {
+          g_plan_cache.splice(g_plan_cache.begin(), g_plan_cache, it);
+          hit = g_plan_cache.front().passes;
+          break;
+        }
+    }
+    if (!hit.empty()) {
+      for (size_t p = 0; p < hit.size(); ++p) {
+        if (defer) {
+          prepare_planned(c, hit[p].a, hit[p].T, p == 0, p + 1 == hit.size(), io);
+          defer->push_back(hit[p]);
+          continue;
+        }
+        const int rc = launch_planned(c, hit[p].a, hit[p].T, hit[p].alg_bytes, p == 0, p + 1 == hit.size(), io);
+        if (rc) return rc;
+      }
+      *n_passes = (int)hit.size();
+      return QSIM_OK;
+    }
+  }
+  std::vector<CachedPass> made;
+  const int rc = plan_fused(c->k, ops, n_passes, [&](TileArgs& a, int T, double alg_bytes, bool first, bool last) {
+    if (cacheable) made.push_back(CachedPass{a, T, alg_bytes});      // (before buffers and layouts go in)
+    if (defer) {
+      prepare_planned(c, a, T, first, last, io);
+      defer->push_back(CachedPass{a, T, alg_bytes});
+      return (int)QSIM_OK;
+    }
+    return launch_planned(c, a, T, alg_bytes, first, last, io);
+  }, hint);
+  if (rc == QSIM_OK && cacheable && !made.empty()) {
+    std::lock_guard<std::mutex> lock(g_plan_cache_mu);
+    g_plan_cache.emplace_front();
+    CachedPlan& e = g_plan_cache.front();
+    e.k = c->k; e.hash = hash; e.key.swap(key); e.passes.swap(made);
+    while (g_plan_cache.size() > kPlanCacheEntries) g_plan_cache.pop_back();
+  }
+  return rc;
+}

@@ -75,19 +75,16 @@ static int plan_search(int k, const std::vector<FusedOp>& ops_in, int beam, std:
       // tile grown around its targets -- the tiles a first-come scan never starts from.
       pb.candidates(&cands, (size_t)pb.cap, 1, s.mask, true);
       {
-        u64 bt = 0, bd = 0, bx = 0;
+        PassBuilder::Blocked blocked{pb};           // (every op scanned blocks what follows it, admitted or not)
         int seen = 0;
         seeds.clear();
         for (size_t i = pb.first; i < n_ops; ++i) {
           if (pb.done[i]) continue;
           if (++seen > pb.scan_window) break;
-          if (pb.admissible3(i, bt, bd, bx) && pb.need[i] && __builtin_popcountll(pb.need[i]) <= pb.cap &&
+          if (blocked.admits(i) && pb.need[i] && __builtin_popcountll(pb.need[i]) <= pb.cap &&
               std::find(seeds.begin(), seeds.end(), pb.need[i]) == seeds.end())
             seeds.push_back(pb.need[i]);
-          bt |= pb.tm[i] & ~pb.xm[i];
-          bx |= pb.xm[i];
-          bd |= pb.qm[i] & ~pb.tm[i];
-          if (bt == pb.all_qubits) break;
+          if (blocked.add(i)) break;
         }
         for (u64 seed : seeds) cands.push_back(pb.grow(seed));
         // ... and around the targets of every two of the first kSearchPairSeeds of them (one op's targets leave most of a

@@ -13,11 +13,11 @@ that makes the planner emit exactly that (`directed_lists`), reads back what a p
 time in extended precision (`reference`).  tests/test_engine_case_ledger.py proves the coverage on the CPU;
 tests/test_gpu_engine_cases.py runs every list on the device.
 
-How a list is aimed (csrc/tile_planner.h).  The lists are short and every target is an index bit below 11, so a
+How a list is aimed (csrc/tile_planner.h, csrc/tile_groups.h).  The lists are short and every target is an index bit below 11, so a
 chunk of n qubits is planned as ONE pass whose tile bits are the index bits 0..T-1, T = min(n, 11) (plan_fused fills
 the tile "with the lowest unused bits"); tile position = qubit.  Qubits >= 11 of a 14-qubit chunk lie outside the
 tile.  The ops of a list target at most three distinct bits, so the pass has one register group: the targeted bits,
-padded "with the highest unused tile bits" (emit_group).  Two layouts are used:
+padded "with the highest unused tile bits" (GroupEmitter::write_group).  Two layouts are used:
   * HI : registers (r0, r1, r2) = tile bits (T-3, T-2, T-1) -- every target is one of them;
   * LOW: registers = tile bits (0, T-2, T-1) -- one op targets bit 0.  A full tile whose last group lies above the
     line bits is stored without a write-back, where serialize_pass turns OPC_ASWAP1 back into OPC_SWAP1, so the FULL
@@ -44,7 +44,7 @@ _1Q_CONTROLLED = ("DENSE1", "SWAP1", "ANTI1", "REAL1", "YLIKE1", "ASWAP1")   # f
 _ZERO_FAMILIES = ("DENSE1", "REAL1", "ANTI1", "YLIKE1")
 _PHASES = ("PHASE", "PHASE_NEG", "PHASE_I", "PHASE_NI")
 
-# Entries of the table the planner never emits: (family, variant, the line of csrc/tile_planner.h that rules it out, why).
+# Entries of the table the planner never emits: (family, variant, the line of csrc/tile_ops.h / tile_groups.h that rules it out, why).
 _L_DENSE2 = "d.opcode = (uint8_t)(OPC_DENSE2 + 3 * reg_pos(tile_pos(o.target[0])) + reg_pos(tile_pos(o.target[1])));"
 _W_DENSE2 = "the two targets of an op are distinct qubits, hence distinct registers: JA != JB, never 3 * J + J"
 _L_HAD1 = "if (sp && tuning().tile_had && o.control < 0 && o.m[0].y == 0 && o.m[1].y == 0 && o.m[2].y == 0 && o.m[3].y == 0 &&"
@@ -66,7 +66,7 @@ def table() -> set:
 
 def possible_forms(text: str, family: str, variant: int) -> tuple:
     """Predicate forms the planner can give an entry in one engine text.  Outer forms need index bits outside the
-    tile: FULL only.  Reasons (csrc/tile_planner.h, emit_group):
+    tile: FULL only.  Reasons (csrc/tile_groups.h, GroupEmitter::describe and mux_pairs):
       * a 1q gate has ONE control (FusedOp::control): on a register it selects variants 3..8 (no predicate left), else it
         is a lane OR an outer predicate -- never both;
       * OPC_PRED_OUTER_ZERO is the control = 0 half of the tile_mux pair, whose U satisfies is_plain_1q (kind TG_DENSE1

@@ -476,7 +476,7 @@ def _streaming_counts(entries):
 
 
 def test_streaming_policy_on_small_views_of_a_large_allocation(hip):
-    """The cache policy follows the ALLOCATION a chunk lives in (gate_plan.h group_resident, tile_planner.h
+    """The cache policy follows the ALLOCATION a chunk lives in (gate_plan.h group_resident, tile_launch.h
     launch_tile): a 2^5..2^16 view of a parent larger than the 256 MiB Infinity Cache runs the non-temporal
     (streaming) instantiations of k_gate / k_gate_shuffle / k_tile, which the stand-alone small-state tests of this
     module never reach -- product-reachable through the chunked runner (views of one big state).  Every 1q target,
@@ -702,7 +702,7 @@ def test_interleaved_fused_passes_gate_kernels_and_reductions_on_one_stream(hip)
 
 
 def test_plan_cache_reuses_plans_and_tells_op_lists_apart(hip):
-    """qsim_apply_ops keeps the pass images of the last op lists (csrc/tile_planner.h, plan cache): an identical call
+    """qsim_apply_ops keeps the pass images of the last op lists (csrc/tile_launch.h, plan cache): an identical call
     launches them again without planning -- on another chunk, inside a re-layout -- and anything that differs in a
     single matrix entry, qubit or size is planned afresh.  Every result against the oracle."""
     n = 14

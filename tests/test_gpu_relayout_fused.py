@@ -270,6 +270,34 @@ def test_split_form_stores_the_slabs_piece_by_piece(k):
         c.close()
 
 
+def test_split_form_partial_launches_with_two_tiles_per_workgroup():
+    """The partial launches of the split form at k = 25: the smallest chunk whose partial launch (one piece bit fixed)
+    still has 2^13 tiles, the threshold of the two-tiles-per-workgroup form of the PART instantiations of k_tile
+    (csrc/tile_launch.h launch_tile; the sizes above stay below it), and 512 MiB, so their streaming forms.  The ops lie
+    on qubits 0..11, so a 4096-amplitude window of the state is closed under them and the host oracle needs only the
+    window; 1e-13: 40 ops on amplitudes of 2^-12.5 round at 1e-18."""
+    from quantum_simulations_amd.kernel.device import DeviceChunk
+    k, bit, w = 25, 20, 1 << 12
+    state, buf = DeviceChunk.empty(k), DeviceChunk.empty(k)
+    state.init_random(2500)
+    ops = _random_ops(12, 40, 2501)
+    rng = np.random.default_rng(2502)
+    windows = [0, (1 << k) - w] + [int(o) * w for o in rng.integers(0, 1 << (k - 12), size=6)]
+    want = {}
+    for o in windows:
+        want[o] = state.download(o, w)
+        orc.apply_ops(want[o], ops)
+    state.apply_ops_io(ops, dst=(buf, [bit], None, -1), parts=-2)
+    assert len(state.pending_parts()) == 2 and state.last_split_launches == 2      # the top bit is no tile bit: one launch per piece
+    for j in (1, 0):
+        state.store_part(j)
+    for o in windows:                                         # slab layout: bit 20 moves to the top, the bits above it close ranks
+        at = (((o >> bit) & 1) << (k - 1)) | ((o >> (bit + 1)) << bit) | (o & ((1 << bit) - 1))
+        np.testing.assert_allclose(buf.download(at, w), want[o], rtol=0, atol=1e-13, err_msg=f"window {o}")
+    for c in (state, buf):
+        c.close()
+
+
 @pytest.mark.parametrize("k", [7, 14, 17, 21])
 def test_split_source_consumes_the_pieces_as_they_arrive(k):
     """qsim_ops_io::src_parts (the receive side of a fused re-layout): the call plans and launches nothing; every

@@ -97,7 +97,7 @@ def test_two_qubit_heavy_lists_plan_and_run():
 def test_outer_controlled_gate_merges_with_the_1q_gate_on_its_target():
     """A controlled gate whose control lies outside the tile, next to a plain 1q gate U on its target, is written as
     two predicated 2x2 records (control = 1: U V or V U; control = 0: U under OPC_PRED_OUTER_ZERO) instead of V + U
-    (csrc/tile_planner.h, emit_groups peephole).  Both orders, CNOT and CY, a gate in between on another qubit, and
+    (csrc/tile_groups.h, GroupEmitter::mux_pairs).  Both orders, CNOT and CY, a gate in between on another qubit, and
     the cases that must NOT pair (a gate on the target in between; a control inside the tile)."""
     n = 13
     H, X, RY, T, Y = (orc.gate_matrix(g, {"theta": 0.7}) for g in ("H", "X", "RY", "T", "Y"))
@@ -145,7 +145,7 @@ def test_phase_runs_are_merged_and_ordered():
 
 
 def test_commuting_1q_gates_are_fused():
-    """Library-side fusion of 1q gates across ops they commute with (csrc/tile_planner.h commute_fuse_1q): X through
+    """Library-side fusion of 1q gates across ops they commute with (csrc/tile_ops.h commute_fuse_1q): X through
     CNOT targets, Z / S / T through controls and CZ / CR; H must NOT pass a CNOT.  Fewer records, same state."""
     if os.environ.get("QSIM_TILE_COMMUTE_FUSE") != "2":
         # off by default (measured neutral); the knob is read once per process: run this test alone in a child

@@ -24,7 +24,7 @@ LOW = 3
 
 
 def classify(qs, U):
-    """(all qubits, general targets, X-type targets) as the pass builder sees an op (csrc/tile_planner.h classify_op)"""
+    """(all qubits, general targets, X-type targets) as the pass builder sees an op (csrc/tile_ops.h classify_op)"""
     U = np.asarray(U)
     if len(qs) == 1:
         diag = U[0, 1] == 0 and U[1, 0] == 0
