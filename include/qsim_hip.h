@@ -359,6 +359,15 @@ int qsim_norm2(qsim_chunk* c, double* out);               /* sum |amp|^2        
  * workgroup order on the device, no atomics); only the 2^r doubles cross to the host.  Qubits >= log2(chunk) fail with
  * QSIM_ERR_NONLOCAL.  Dynamic circuits (mid-circuit measurement, reset) sample their outcomes from it. */
 int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out);
+/* Reduced density matrix of r qubits (1 <= r <= 6), unnormalised:
+ *   rho[a][b] = sum over e of psi(e, a) * conj(psi(e, b)),   a, b < 2^r,
+ * bit j of a (and of b) <-> index bit qubits[j] (any order, as in qsim_probabilities / qsim_apply_fused_k);
+ * e runs over the other k - r index bits.  out: 2 * 4^r doubles, row-major, (re, im) interleaved.  trace = sum |amp|^2.
+ * One read-only pass over the chunk (any qubit set: one partial matrix per workgroup, summed in workgroup order on the
+ * device, no atomics): two calls give the same bits.  One triangle is computed and mirrored, so out is exactly
+ * Hermitian and its diagonal exactly real.  Only the 2 * 4^r doubles cross to the host; blocks until out is written.
+ * A repeated qubit fails with QSIM_ERR_INVALID, a qubit >= log2(chunk) with QSIM_ERR_NONLOCAL. */
+int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, double* out);
 /* Expectation values of Pauli strings, unnormalised: out[t] = <psi|P_t|psi> for t < n_terms.  P_t is two masks of
  * physical local index bits: x_masks[t] = the bits that carry X or Y, z_masks[t] = the bits that carry Z or Y; with
  * ny = popcount(x & z) (Y = i X Z), P|i> = i^ny (-1)^popcount(i & z) |i ^ x> and

@@ -109,6 +109,7 @@ SIGNATURES = {
     "qsim_sync": (C.c_int, [_P]),
     "qsim_norm2": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "qsim_probabilities": (C.c_int, [_P, C.c_int, _P, _P]),
+    "qsim_reduced_density_matrix": (C.c_int, [_P, C.c_int, _P, _P]),
     "qsim_expectation_pauli": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_plan_expectation": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_sample": (C.c_int, [_P, C.c_uint64, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int)]),

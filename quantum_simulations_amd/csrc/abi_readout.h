@@ -226,6 +226,96 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
   return QSIM_OK;
 }
 
+// Reduced density matrix (rdm_kernels.h): one read-only pass (k_rdm_small for r <= 3, k_rdm_mfma for r = 4..6), one
+// partial matrix of 4^r doubles per workgroup, k_hist_sum over them in workgroup order; the triangle is mirrored on the
+// host.  The scratch is the expectation buffer (ensure_expect): at most (kRdmMaxWg + 1) * 4^r doubles, that is 32 MiB +
+// 32 KiB at r = 6, 8 MiB at r = 5, 2 MiB at r = 4, 512 KiB at r = 3 (and grid + 1 matrices for chunks of fewer tiles).
+int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, double* out) {
+  int rc = check_chunk(c, "qsim_reduced_density_matrix");
+  if (rc) return rc;
+  if (!qubits || !out) return fail(QSIM_ERR_INVALID, "qsim_reduced_density_matrix: null argument");
+  if (r < 1 || r > kRdmMaxQubits) return fail(QSIM_ERR_INVALID, "qsim_reduced_density_matrix: 1 <= r <= 6 qubits expected, got %d", r);
+  if ((rc = require_no_parts(c, "qsim_reduced_density_matrix"))) return rc;
+  u64 sel = 0;
+  for (int i = 0; i < r; ++i) {
+    if ((rc = check_local_qubit(c, qubits[i]))) return rc;
+    for (int j = 0; j < i; ++j) if (qubits[j] == qubits[i]) return fail(QSIM_ERR_INVALID, "qsim_reduced_density_matrix: repeated qubit %d", qubits[i]);
+    sel |= 1ull << qubits[i];
+  }
+  const int k = c->k, tb = std::min(k, kRdmTileBits), eb = tb - r;
+  const u64 all = (1ull << k) - 1;
+  u64 T = sel | ((1ull << std::min(k, kExpLineBits)) - 1);
+  for (int b = 0; b < k && __builtin_popcountll(T) < tb; ++b) T |= 1ull << b;
+  RdmArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.amp = c->amp;
+  a.tb = tb;
+  a.outer_mask = all & ~T;
+  a.n_tiles = 1ull << (k - tb);
+  int n_env = 0;                                    // tile bits outside the qubits: the e' bits, ascending
+  for (int b = 0, j = 0; b < k; ++b) {
+    if (!((T >> b) & 1)) continue;
+    a.phys_bit[j] = b;
+    if ((sel >> b) & 1) {
+      for (int q = 0; q < r; ++q) if (qubits[q] == b) a.lds_pos[j] = eb + q;
+    } else {
+      a.lds_pos[j] = n_env++;
+    }
+    ++j;
+  }
+  // r <= 3: a qubit on a line bit XORs one of the e' bits 0..2 that the remaining line bits leave free (rdm_kernels.h)
+  int free_bit = 0;
+  for (int b = 0; b < std::min(k, kExpLineBits); ++b) free_bit += !((sel >> b) & 1);
+  for (int q = 0; q < r; ++q)
+    if (qubits[q] < kExpLineBits && free_bit < std::min(eb, kExpLineBits)) a.swz[q] = 1 << free_bit++;
+  const int dd = 1 << (2 * r), dim = 1 << r;
+  const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, kRdmMaxWg);
+  if ((rc = ensure_expect(c, sizeof(double) * ((u64)grid + 1) * (u64)dd))) return rc;
+  a.partial = static_cast<double*>(c->expect);
+  double* dev_out = a.partial + (u64)grid * dd;
+  HIP_TRY(hipSetDevice(c->device));
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  {
+    ProfileScope prof(11, 16.0 * (double)amps(c), c->stream, nt);
+#define QSIM_RDM_LAUNCH(KERNEL, R)                                                                      \
+    if (nt) hipLaunchKernelGGL((KERNEL<R, true>), dim3(grid), dim3(kBlock), 0, c->stream, a);           \
+    else hipLaunchKernelGGL((KERNEL<R, false>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+#ifdef QSIM_PROBES
+    if (tuning().rdm_form == 1 && r >= 4) {
+      if (r == 4) { QSIM_RDM_LAUNCH(k_rdm_block, 4) } else if (r == 5) { QSIM_RDM_LAUNCH(k_rdm_block, 5) } else { QSIM_RDM_LAUNCH(k_rdm_block, 6) }
+    } else
+#endif
+    switch (r) {
+      case 1: QSIM_RDM_LAUNCH(k_rdm_small, 1) break;
+      case 2: QSIM_RDM_LAUNCH(k_rdm_small, 2) break;
+      case 3: QSIM_RDM_LAUNCH(k_rdm_small, 3) break;
+      case 4: QSIM_RDM_LAUNCH(k_rdm_mfma, 4) break;
+      case 5: QSIM_RDM_LAUNCH(k_rdm_mfma, 5) break;
+      default: QSIM_RDM_LAUNCH(k_rdm_mfma, 6) break;
+    }
+#undef QSIM_RDM_LAUNCH
+    HIP_TRY(hipGetLastError());
+    prof.done(c->stream);
+  }
+  hipLaunchKernelGGL(k_hist_sum, dim3(dd), dim3(kBlock), 0, c->stream, (const double*)a.partial, (int)grid, dd, dev_out);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> tri((size_t)dd);
+  HIP_TRY(hipMemcpyAsync(tri.data(), dev_out, sizeof(double) * (u64)dd, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int x = 0; x < dim; ++x) {                   // the triangle and its mirror image: exactly Hermitian
+    out[2 * (x * dim + x)] = tri[(size_t)(x * dim + x)];
+    out[2 * (x * dim + x) + 1] = 0.0;
+    for (int y = 0; y < x; ++y) {
+      const double re = tri[(size_t)(x * dim + y)], im = tri[(size_t)(y * dim + x)];
+      out[2 * (x * dim + y)] = re;
+      out[2 * (x * dim + y) + 1] = im;
+      out[2 * (y * dim + x)] = re;
+      out[2 * (y * dim + x) + 1] = -im;
+    }
+  }
+  return QSIM_OK;
+}
+
 // Shot sampling (sample_kernels.h): pass A (block sums), the block prefix and the shots' blocks on the host, the shots
 // grouped by block, pass B (one workgroup per hit block), the indices back in the order of randnums.
 int qsim_sample_block_bits(void) { return kSampleBlockBits; }

@@ -61,6 +61,7 @@ struct Tuning {
   int dense_wgs = 0;         // (probe build) resident workgroups per CU the k = 5 grid asks for (product: 4); QSIM_DENSE_WGS
   int dense_consec = 0;      // (probe build) k <= 4: a wave's column groups are consecutive (else strided through its XCD's region); QSIM_DENSE_CONSEC
   long long dense_skew = 0;  // (probe build) XCD x starts x * skew column groups into its region; QSIM_DENSE_SKEW
+  int rdm_form = 0;          // (probe build) qsim_reduced_density_matrix, r = 4..6: 0 = k_rdm_mfma, 1 = the vector-ALU k_rdm_block; QSIM_RDM_FORM
   int dense_mfma = 3;        // qsim_apply_fused_k: bit 0: k = 3, bit 1: k = 4 on the matrix cores (k_dense_mfma; else the vector-ALU k_dense; probe knob QSIM_DENSE_MFMA)
   int debug_skip_gates = 0;  // probe build only: QSIM_DEBUG_SKIP_GATES=1: tile passes move data but apply nothing (WRONG results)
   int tile_order = -1;       // probe build only: QSIM_TILE_ORDER=0/1/2 forces the tile order of k_tile
@@ -91,6 +92,7 @@ struct Tuning {
     if (const char* e = getenv("QSIM_PLAN_SCAN_WINDOW")) plan_scan_window = std::max(1, atoi(e));
     if (const char* e = getenv("QSIM_DENSE_MFMA")) dense_mfma = atoi(e);
     if (const char* e = getenv("QSIM_DENSE_FORM")) dense_form = atoi(e);
+    if (const char* e = getenv("QSIM_RDM_FORM")) rdm_form = atoi(e);
     if (const char* e = getenv("QSIM_DENSE_PF")) dense_pf = atoi(e);
     if (const char* e = getenv("QSIM_DENSE_GROUPS")) dense_groups = atoi(e);
     if (const char* e = getenv("QSIM_DENSE_WGS")) dense_wgs = atoi(e);
@@ -140,8 +142,9 @@ static const char* const kClassNames[] = {
     "k_gate<1> scale (diagonal subset)", "k_gate<2> 2x2 butterfly", "k_gate<4> 4x4 butterfly",
     "k_gate_shuffle<1,1> lane 1q", "k_gate_shuffle<1,2> lane 2q", "k_gate_shuffle<2,1> lane+reg 2q",
     "k_tile fused pass", "k_dense dense k-qubit block", "k_hist outcome probabilities",
-    "k_sample_block_sums shot sampling, pass A", "k_sample_resolve shot sampling, pass B"};
-constexpr int kNumClasses = 11;
+    "k_sample_block_sums shot sampling, pass A", "k_sample_resolve shot sampling, pass B",
+    "k_rdm reduced density matrix"};
+constexpr int kNumClasses = 12;
 
 static hipEvent_t prof_event_locked() {
   if (!g_prof_pool.empty()) {

@@ -56,6 +56,7 @@ typedef unsigned long long u64;
 #include "misc_kernels.h"
 #include "dense_kernels.h"
 #include "expect_kernels.h"
+#include "rdm_kernels.h"
 #include "sample_kernels.h"
 #include "comm_rccl.h"
 

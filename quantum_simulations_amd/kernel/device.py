@@ -288,6 +288,19 @@ class DeviceChunk:
         _lib.check(_lib.load().qsim_probabilities(self._h, len(q), _lib.ptr(q), _lib.ptr(out)))
         return out
 
+    def reduced_density_matrix(self, qubits) -> np.ndarray:
+        """Reduced density matrix of `qubits` (1 to 6 PHYSICAL index bits of this chunk, any order), unnormalised:
+        complex128 of shape (2^r, 2^r), entry [a, b] = sum over the other bits e of psi(e, a) conj(psi(e, b)) with bit j
+        of a and b on index bit qubits[j]; its trace is sum |amp|^2 (qsim_reduced_density_matrix: one read-only pass on
+        the device, a fixed summation order -- two calls give the same bits; exactly Hermitian).  `density` has purity,
+        entropy and fidelity of the result."""
+        q = np.ascontiguousarray(qubits, dtype=np.int32).reshape(-1)
+        if not 1 <= len(q) <= 6:
+            raise ValueError(f"reduced_density_matrix: 1 to 6 qubits expected, got {len(q)}")
+        out = np.empty((1 << len(q), 1 << len(q)), dtype=np.complex128)
+        _lib.check(_lib.load().qsim_reduced_density_matrix(self._h, len(q), _lib.ptr(q), _lib.ptr(out)))
+        return out
+
     def expectation_pauli(self, x_masks, z_masks) -> np.ndarray:
         """<psi|P_t|psi> of Pauli strings given as masks of PHYSICAL index bits of this chunk (x: X or Y, z: Z or Y),
         unnormalised (qsim_expectation_pauli: read-only passes on the device, a fixed summation order -- two calls give

@@ -93,6 +93,12 @@ class SingleGpuEngine:
         evaluated on the device through the current layout; the state does not move."""
         return self.state.expectation(obs, l2p=self.l2p if self.l2p is not None else list(range(self.n)))
 
+    def reduced_density_matrix(self, qubits) -> np.ndarray:
+        """Reduced density matrix (unnormalised, complex128 (2^r, 2^r)) of 1 to 6 LOGICAL qubits, bit j of a row or
+        column index = qubit qubits[j], evaluated on the device through the current layout; the state does not move."""
+        l2p = self.l2p if self.l2p is not None else list(range(self.n))
+        return self.state.reduced_density_matrix([l2p[int(q)] for q in qubits])
+
     def sample(self, shots: int, seed: int = 0, qubits=None) -> np.ndarray:
         """`shots` samples of the register, drawn on the device through the current layout (the state does not move;
         `sampling.draw(shots, seed)` gives the uniforms): LOGICAL basis-state indices as uint64, or with `qubits` the

@@ -310,6 +310,14 @@ def expectation(buf: HbmStateBuffer, obs) -> float:
     return buf.state.expectation(obs, l2p=l2p)
 
 
+def reduced_density_matrix(buf: HbmStateBuffer, qubits) -> np.ndarray:
+    """Reduced density matrix (unnormalised, complex128 (2^r, 2^r)) of 1 to 6 LOGICAL qubits of the final state of `run`,
+    bit j of a row or column index = qubit qubits[j], evaluated on the device through the staging layout
+    `buf.log_to_phys` (nothing is downloaded or permuted)."""
+    l2p = getattr(buf, "log_to_phys", None) or list(range(buf.n_qubits))
+    return buf.state.reduced_density_matrix([l2p[int(q)] for q in qubits])
+
+
 def sample(buf: HbmStateBuffer, shots: int, seed: int = 0, qubits=None) -> np.ndarray:
     """`shots` samples of the final state of `run`, drawn on the device through the staging layout `buf.log_to_phys`
     (nothing is downloaded or permuted; `sampling.draw(shots, seed)` gives the uniforms): LOGICAL basis-state indices as
