@@ -163,6 +163,13 @@ int qsim_apply_ops_io_source_parts(const qsim_chunk* c, int32_t* n_parts, uint64
 int qsim_apply_ops_io_parts(const qsim_chunk* c, int32_t* n_parts, uint64_t* piece_amps, int32_t* n_launches);
 int qsim_apply_ops_io_part(qsim_chunk* c, int part);
 int qsim_split_piece_count(int n_local_qubits, int m, int dst_parts);   /* the piece rule as a pure function */
+/* The launch rule of a fused pass as a pure function (no GPU): the tiles ONE workgroup takes when a pass of 2^tile_bits-
+ * amplitude tiles runs over a chunk of n_local_qubits with n_fixed_bits index bits fixed (0: all tiles; 1..3: a partial
+ * launch of the split form) -- 1, or the library's QSIM_TILES_PER_WG (2) from 4096 workgroups of that many tiles on: the
+ * second tile's loads then fly while the gate engine works on the first.  The launch itself calls it.  Arguments the
+ * launch refuses (a tile size that is not built, more tile or fixed bits than the chunk has, fixed bits with a partial
+ * tile, 2^32 tiles or more) fail with QSIM_ERR_INVALID. */
+int qsim_tiles_per_workgroup(int n_local_qubits, int tile_bits, int n_fixed_bits);
 /* The host planner of the fused passes WITHOUT a device (used by the CPU tests): plans the op list
  * for a 2^n_local_qubits chunk and writes one QSIM_PASS_IMAGE_BYTES pass image per planned pass to `out`
  * (layout = the kernel-argument block of k_tile, csrc/tile_kernel.h: record count, tile size T, tile high

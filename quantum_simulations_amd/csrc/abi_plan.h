@@ -276,4 +276,9 @@ int qsim_split_piece_count(int n_local_qubits, int m, int dst_parts) {
   if (m < 1 || m > 3 || m > n_local_qubits || dst_parts == 0) return 1;
   return 1 << piece_bits_for(n_local_qubits, m, dst_parts < 0 ? -dst_parts : dst_parts, dst_parts < 0 ? kTileLow : 20);
 }
+
+// (k, T, fixed bits of a partial launch) -> tiles one workgroup of the fused pass takes: launch_tile's own rule
+int qsim_tiles_per_workgroup(int n_local_qubits, int tile_bits, int n_fixed_bits) {
+  return tiles_per_workgroup(n_local_qubits, tile_bits, n_fixed_bits);
+}
 }  // extern "C"

@@ -74,14 +74,31 @@ static void launch_k_tile(bool nt, bool wide, unsigned grid, hipStream_t stream,
   else hipLaunchKernelGGL((k_tile<T, false, false, TPW, PART>), dim3(grid), dim3(kTileThreads), 0, stream, args);
 }
 
+// Tiles per workgroup of a launch of T-bit tiles over a chunk of k qubits with nfix index bits fixed (a partial launch):
+// the launch rule as a pure function (qsim_tiles_per_workgroup), 1 or QSIM_TILES_PER_WG; what launch_tile refuses is an
+// error here.  Two tiles per workgroup, the second one's loads in flight while the first is computed on
+// (profiles/r02r_ab_prefetch_before_engine.txt: -3.9 % per pass; 4 or 8 tiles per workgroup lose it again,
+// profiles/r02z_ab_paired_stores.txt).  Also for the 64-bit-offset form (110 VGPRs: the 32 KiB of LDS admit four
+// workgroups per CU, so 128 are there); not for small grids.
+static int tiles_per_workgroup(int k, int T, int nfix) {
+  if (T > kTileBitsMax || T < kTileThreadBits) return fail(QSIM_ERR_INVALID, "internal: tile size %d not built", T);
+  if (k < T) return fail(QSIM_ERR_INVALID, "internal: a %d-bit tile on a chunk of %d qubits", T, k);
+  if (nfix < 0 || (nfix && (T != kTileBitsMax || nfix > 3 || k - T < nfix)))
+    return fail(QSIM_ERR_INVALID, "internal: partial launch of a %d-bit tile", T);
+  if (k - T - nfix >= 32) return fail(QSIM_ERR_INVALID, "internal: too many tiles");
+  const u64 ntiles = 1ull << (k - T - nfix);            // (nfix: the tiles of one destination slab of a fused re-layout)
+  constexpr int TPW = QSIM_TILES_PER_WG;
+  return TPW > 1 && ntiles >= (u64)TPW * 4096 ? TPW : 1;
+}
+
 template <int T>
 static int launch_tile(const TileArgs& a, const qsim_chunk* c, hipStream_t stream, double alg_bytes) {
   if constexpr (T > kTileBitsMax || T < kTileThreadBits) {
     return fail(QSIM_ERR_INVALID, "internal: tile size %d not built", T);
   } else {
-  if (a.nfix && (T != kTileBitsMax || a.nfix > 3 || c->k - T < a.nfix)) return fail(QSIM_ERR_INVALID, "internal: partial launch of a %d-bit tile", T);
-  const u64 ntiles = 1ull << (c->k - T - a.nfix);       // (a.nfix: the tiles of one destination slab of a fused re-layout)
-  if (ntiles > 0xFFFFFFFFull) return fail(QSIM_ERR_INVALID, "internal: too many tiles");
+  const int per_wg = tiles_per_workgroup(c->k, T, a.nfix);
+  if (per_wg < 0) return per_wg;
+  const u64 ntiles = 1ull << (c->k - T - a.nfix);
   TileArgs args = a;
   args.ntiles = (uint32_t)ntiles;
   args.order = (uint8_t)((a.order & ~kTileOrderMask) | (tile_order_for(a, T) & kTileOrderMask));
@@ -101,12 +118,8 @@ static int launch_tile(const TileArgs& a, const qsim_chunk* c, hipStream_t strea
   bool nt = c->span_bytes > tuning().mall_bytes;       // cache policy by state size (gate_plan.h)
   if (tuning().force_nt >= 0) nt = tuning().force_nt != 0;
   ProfileScope prof(6, alg_bytes, stream, nt, 32.0 * (double)(ntiles << T));
-  // Two tiles per workgroup, the second one's loads in flight while the first is computed on
-  // (profiles/r02r_ab_prefetch_before_engine.txt: -3.9 % per pass; 4 or 8 tiles per workgroup lose it again,
-  // profiles/r02z_ab_paired_stores.txt).  Also for the 64-bit-offset form (110 VGPRs: the 32 KiB of LDS admit four
-  // workgroups per CU, so 128 are there); not for small grids.
   constexpr int TPW = QSIM_TILES_PER_WG;
-  const bool two = TPW > 1 && ntiles >= (u64)TPW * 4096;
+  const bool two = per_wg > 1;                             // (tiles_per_workgroup: the rule)
   const unsigned grid = (unsigned)(two ? ntiles / TPW : ntiles);
   bool part = false;                                       // one destination slab: the PART instantiations (full tiles only)
   if constexpr (T == kTileBitsMax) {

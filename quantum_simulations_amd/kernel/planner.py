@@ -1,6 +1,6 @@
 """The host planner of libqsim_hip.so in Python: what the pass builder would do with an op list, without a device
 (csrc/abi_plan.h: qsim_plan_ops, qsim_plan_ops_tiled, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass,
-qsim_rewrite_ops).
+qsim_rewrite_ops; csrc/tile_launch.h: qsim_tiles_per_workgroup).
 
 A thin binding.  `ops` is [(qubits, U), ...] or the tuple `pack_ops` returns (`device.as_packed`).  Return codes become
 the exceptions of `_lib.check` and nothing else is read into them: what a caller makes of a list too short to plan is
@@ -71,6 +71,16 @@ def pass_count(n: int, ops, tiles=None) -> int:
     rc, count = _plan(n, ops, tiles, None)
     _lib.check(rc)
     return count
+
+
+def tiles_per_workgroup(n: int, tile_bits: int, fixed_bits: int = 0) -> int:
+    """Tiles one workgroup of a fused pass takes on a chunk of n qubits (qsim_tiles_per_workgroup: the rule the launch
+    itself applies, a pure function): 1, or 2 from 2 x 4096 tiles on; `fixed_bits`: those a partial launch of the split
+    form fixes.  What the launch would refuse raises ValueError."""
+    rc = int(_lib.load().qsim_tiles_per_workgroup(int(n), int(tile_bits), int(fixed_bits)))
+    if rc < 0:
+        _lib.check(rc)
+    return rc
 
 
 def search_tiles(n: int, ops, beam: int = 0) -> np.ndarray:

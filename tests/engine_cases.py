@@ -11,7 +11,8 @@ This module builds, for every (engine text, family, variant, predicate form) the
 that makes the planner emit exactly that (`directed_lists`), reads back what a planned list really contains
 (`ledger`), names what the planner can never emit (`UNREACHABLE`, `possible_forms`) and states the operation a second
 time in extended precision (`reference`).  tests/test_engine_case_ledger.py proves the coverage on the CPU;
-tests/test_gpu_engine_cases.py runs every list on the device.
+tests/test_gpu_engine_cases.py runs every list on the device.  `paired_lists` are the FULL lists once more at 24 qubits,
+where a workgroup takes two tiles (tests/test_gpu_engine_cases_paired.py).
 
 How a list is aimed (csrc/tile_planner.h, csrc/tile_groups.h).  The lists are short and every target is an index bit below 11, so a
 chunk of n qubits is planned as ONE pass whose tile bits are the index bits 0..T-1, T = min(n, 11) (plan_fused fills
@@ -158,14 +159,16 @@ def variant_registers(variant: int):
 
 
 class _Geometry:
-    def __init__(self, n: int):
+    def __init__(self, n: int, outer=None):
         self.n = n
         self.T = min(n, 11)
         self.text = FULL if self.T == 11 else PARTIAL
         self.hi = (self.T - 3, self.T - 2, self.T - 1)
         self.low = (0, self.T - 2, self.T - 1)
         self.lane = (3, 4)                                  # tile bits that are no register bits (T - 3 >= 5)
-        self.outer = (12, 13) if n >= 14 else None          # index bits outside the tile
+        # index bits outside the tile (a pair; which of the two a list uses follows its variant)
+        self.outer = tuple(outer) if outer is not None else (12, 13) if n >= 14 else None
+        assert self.outer is None or (len(set(self.outer)) == 2 and all(self.T <= b < n for b in self.outer))
 
 
 def _lists_1q(g: _Geometry, family: str):
@@ -282,28 +285,75 @@ def _lists_layout(g: _Geometry):
     yield Case(g.text, g.n, "REAL1", 0, "none", [([0], M_REAL), ([a], M_DENSE), ([b], M_DENSE_B), ([c], M_ANTI)], "direct-out")
 
 
+def _lists_of(g: _Geometry) -> list:
+    out = []
+    for family in FAMILIES:
+        if family in _1Q_CONTROLLED or family == "HAD1":
+            out += list(_lists_1q(g, family))
+        elif family in _PHASES:
+            out += list(_lists_phase(g, family))
+        elif family == "DIAGR":
+            out += list(_lists_diagr(g))
+        elif family == "DENSE2":
+            out += list(_lists_dense2(g))
+        else:
+            out += list(_lists_scale(g))
+    if g.text == FULL:
+        out += list(_lists_layout(g))
+    return out
+
+
 def directed_lists() -> list:
     """Every directed list, in a fixed order: [Case(text, n, family, variant, form, ops, note)].  A case is AIMED at its
     (family, variant, form); `ledger` tells what its plan really holds."""
     out = []
     for n in PARTIAL_SIZES + FULL_SIZES:
-        g = _Geometry(n)
-        for family in FAMILIES:
-            if family in _1Q_CONTROLLED or family == "HAD1":
-                out += list(_lists_1q(g, family))
-            elif family in _PHASES:
-                out += list(_lists_phase(g, family))
-            elif family == "DIAGR":
-                out += list(_lists_diagr(g))
-            elif family == "DENSE2":
-                out += list(_lists_dense2(g))
-            else:
-                out += list(_lists_scale(g))
-        if g.text == FULL:
-            out += list(_lists_layout(g))
+        out += _lists_of(_Geometry(n))
     ids = [case_id(c) for c in out]
     assert len(set(ids)) == len(ids)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The FULL lists once more where a workgroup of k_tile takes TWO tiles (csrc/tile_launch.h: from 2 x 4096 tiles on, i.e.
+# 24 qubits with 11-bit tiles; planner.tiles_per_workgroup).  The tile is still index bits 0..10, so the tile number is
+# index >> 11 and the two tiles of a workgroup (tile numbers 2w, 2w + 1) differ in index bit 11 alone.  The outer pair is
+# (11, 23): an outer predicate on bit 11 differs INSIDE a tile pair (the engine's `baseh` has to be the one of the tile it
+# works on), one on bit 23 differs across the grid.  Which of the pair a list uses follows its variant, so the lists with
+# an outer predicate are built with both orders of the pair: each sees its predicate at either place.
+PAIRED_N = 24
+PAIRED_OUTER = (11, 23)
+PAIRED_ACTIVE = 13             # the lists touch index bits 0..11 and 23 only: 13 "active" qubits, bits 12..22 look on
+
+
+def outer_bits(c: Case) -> tuple:
+    """Index bits outside the (11-bit) tile a list touches, in the order of their first appearance."""
+    seen = []
+    for qubits, _ in c.ops:
+        seen += [q for q in qubits if q >= 11 and q not in seen]
+    return tuple(seen)
+
+
+def paired_lists() -> list:
+    """The FULL directed lists at PAIRED_N qubits, in a fixed order: all of them with the outer pair (11, 23), then those
+    whose form has an outer predicate with (23, 11).  The note of a list that touches a bit outside the tile ends in
+    o<bits>, e.g. o11, o23 or o23.11 (in order of appearance): the ids are unique and name the placement."""
+    def tagged(g, keep):
+        for c in _lists_of(g):
+            if keep(c):
+                bits = ".".join(str(b) for b in outer_bits(c))
+                yield c._replace(note="-".join(x for x in (c.note, "o" + bits if bits else "") if x))
+    out = list(tagged(_Geometry(PAIRED_N, PAIRED_OUTER), lambda c: True))
+    out += list(tagged(_Geometry(PAIRED_N, PAIRED_OUTER[::-1]), lambda c: "outer" in c.form))
+    ids = [case_id(c) for c in out]
+    assert len(set(ids)) == len(ids)
+    return out
+
+
+def to_active(ops) -> list:
+    """A paired list on its 13-qubit active register: index bit 23 relabelled 12 (bits 12..22 are untouched)."""
+    assert all(q <= 11 or q == 23 for qubits, _ in ops for q in qubits)
+    return [([12 if q == 23 else q for q in qubits], U) for qubits, U in ops]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -325,6 +375,20 @@ def ledger_of_images(images) -> set:
 
 def ledger(n_qubits: int, ops) -> set:
     return ledger_of_images(ti.plan(n_qubits, ops))
+
+
+def outer_masks_of_images(images) -> set:
+    """{(family, variant, predicate form, outer mask)} of the predicated gate records with index bits outside the tile:
+    the mask holds the absolute index bits that must be 1 (for outer-zero: that must be 0)."""
+    seen = set()
+    for img in images:
+        for rec in ti.records(img):
+            if rec[0] == "gate" and rec[3]:
+                _, case, blk, outer = rec[:4]
+                family = ti.fam_of(case)
+                form = "lane+outer" if blk else "outer-zero" if outer < 0 else "outer"
+                seen.add((family, case - ti.OPC[family], form, abs(outer)))
+    return seen
 
 
 def direct_flags(images) -> set:

@@ -1,17 +1,22 @@
 """The directed op lists of tests/engine_cases.py reach every branch-table entry of the fused-pass gate engine that
 the planner can emit -- proven on the CPU: `qsim_plan_ops` plans each list without a device and the record streams
 are read back (tests/tile_interpreter.py).  tests/test_gpu_engine_cases.py runs the same lists on the device, so
-this file is what says WHICH case each of those device tests executes.  Needs the built library, no GPU."""
+this file is what says WHICH case each of those device tests executes.  The same for the paired lists (the FULL lists
+at 24 qubits, where a workgroup of k_tile takes two tiles; tests/test_gpu_engine_cases_paired.py).  Needs the built
+library, no GPU."""
 import os
 
 import numpy as np
 import pytest
 
 from tests import engine_cases as ec
+from quantum_simulations_amd.kernel import planner
 from tests import tile_interpreter as ti
+from tests.test_gpu_engine_cases_paired import multi_group_lists, product_state
 from tests.test_gpu_kernels import _random_ops
 
 CASES = ec.directed_lists()
+PAIRED = ec.paired_lists()
 
 
 @pytest.fixture(scope="module")
@@ -118,3 +123,154 @@ def test_reference_conventions():
     out = ec.reference(psi, [([0], np.array([[1, 2], [3, 4]]))])
     assert out[0] == 2 and out[1] == 4
     assert out.dtype == np.clongdouble
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the paired lists: two tiles per workgroup
+@pytest.fixture(scope="module")
+def planned_paired():
+    """case id -> (case, planned images)"""
+    return {ec.case_id(c): (c, ti.plan(c.n, c.ops)) for c in PAIRED}
+
+
+def test_two_tiles_per_workgroup_from_8192_tiles_on():
+    """The launch rule (qsim_tiles_per_workgroup, which launch_tile itself calls): with 11-bit tiles the paired lists'
+    24 qubits are the first size with two tiles per workgroup."""
+    assert planner.tiles_per_workgroup(ec.PAIRED_N, 11, 0) == 2
+    assert planner.tiles_per_workgroup(ec.PAIRED_N - 1, 11, 0) == 1
+    for k in range(11, 36):                          # 2^(k - 11) tiles: two from 2 x 4096 on
+        assert planner.tiles_per_workgroup(k, 11) == (2 if k - 11 >= 13 else 1), k
+    for T in (8, 9, 10):
+        assert planner.tiles_per_workgroup(T, T) == 1
+    # a partial launch of the split form: the tiles of the launch count, not those of the chunk
+    assert [planner.tiles_per_workgroup(25, 11, f) for f in (0, 1, 2, 3)] == [2, 2, 1, 1]
+    # what the launch refuses: tile sizes that are not built, a tile larger than the chunk, fixed bits with a partial
+    # tile / more than three / more than the chunk has left, 2^32 tiles or more
+    for bad in ((24, 12, 0), (24, 7, 0), (10, 11, 0), (24, 10, 1), (24, 11, 4), (13, 11, 3), (24, 11, -1), (43, 11, 0)):
+        with pytest.raises(ValueError):
+            planner.tiles_per_workgroup(*bad)
+    assert planner.tiles_per_workgroup(42, 11, 0) == 2
+
+
+def test_paired_lists_are_the_full_lists_on_other_outer_bits():
+    """All 195 FULL lists of 14 qubits with the outer pair (12, 13) relabelled (11, 23), then the 58 with an outer
+    predicate relabelled (23, 11); directed_lists() itself is what it was (the device tests seed by its order)."""
+    full = [c for c in CASES if c.text == ec.FULL and c.n == 14]
+    with_outer = [c for c in full if "outer" in c.form]
+    assert (len(CASES), len(full), len(with_outer), len(PAIRED)) == (737, 195, 58, 195 + 58)
+    assert [ec.case_id(c) for c in CASES[:2]] == ["PARTIAL-n8-DENSE1+0-none", "PARTIAL-n8-DENSE1+0-lane"]
+    for moved, sources in ((PAIRED[:195], ({12: 11, 13: 23}, full)), (PAIRED[195:], ({12: 23, 13: 11}, with_outer))):
+        relabel, source = sources
+        assert len(moved) == len(source)
+        for c, c14 in zip(moved, source):
+            assert (c.text, c.n, c.family, c.variant, c.form) == (ec.FULL, ec.PAIRED_N, c14.family, c14.variant, c14.form)
+            assert len(c.ops) == len(c14.ops)
+            for (q, U), (q14, U14) in zip(c.ops, c14.ops):
+                assert list(q) == [relabel.get(b, b) for b in q14] and np.array_equal(U, U14), ec.case_id(c)
+            # the id names the placement: the bits outside the tile the list touches
+            bits = ec.outer_bits(c)
+            assert set(bits) <= {11, 23}
+            assert c.note == "-".join(x for x in (c14.note, "o" + ".".join(map(str, bits)) if bits else "") if x), ec.case_id(c)
+    assert all(("outer" in c.form) == bool(ec.outer_bits(c)) for c in PAIRED)
+
+
+def test_every_paired_list_is_planned_as_aimed(planned_paired):
+    """One pass whose tile is index bits 0..10 -- so tile number = index >> 11 and the two tiles of a workgroup differ in
+    index bit 11 -- that holds the (family, variant, form) of the id and nothing the planner cannot emit."""
+    for cid, (c, images) in planned_paired.items():
+        assert 2 <= len(c.ops) <= 8, cid
+        assert len(images) == 1, cid
+        assert int(images[0]["T"]) == 11, cid
+        assert [int(b) for b in images[0]["h"][:8]] == list(range(3, 11)), cid
+        held = ec.ledger_of_images(images)
+        assert (c.text, c.family, c.variant, c.form) in held, (cid, sorted(held))
+        for text, f, v, form in held:
+            assert text == ec.FULL and form in ec.possible_forms(text, f, v), (cid, f, v, form)
+        assert max(float(np.max(np.abs(U))) for _, U in c.ops) <= 1.0, cid
+        assert all(q <= 11 or q == 23 for qubits, _ in c.ops for q in qubits), cid
+        if "outer" in c.form:     # the aimed record carries exactly the outer bits the id names
+            mask = sum(1 << b for b in ec.outer_bits(c))
+            assert (c.family, c.variant, c.form, mask) in ec.outer_masks_of_images(images), cid
+
+
+def test_paired_lists_cover_the_table_with_the_predicate_in_and_across_tile_pairs(planned_paired):
+    seen, masks, flags = set(), set(), set()
+    for c, images in planned_paired.values():
+        seen |= {e[1:] for e in ec.ledger_of_images(images)}
+        masks |= ec.outer_masks_of_images(images)
+        flags |= ec.direct_flags(images)
+    assert seen == ec.required(ec.FULL)
+    assert {(c.family, c.variant, c.form) for c in PAIRED} == ec.required(ec.FULL)
+    # every entry with an outer predicate: once with the bit that differs INSIDE a tile pair, once with the one that
+    # differs across the grid
+    outer_entries = {e for e in ec.required(ec.FULL) if "outer" in e[2]}
+    assert {m[:3] for m in masks} == outer_entries
+    for e in outer_entries:
+        assert {m[3] for m in masks if m[:3] == e} >= {1 << 11, 1 << 23}, e
+    assert {m[3] for m in masks} == {1 << 11, 1 << 23, (1 << 11) | (1 << 23)}
+    for bit in ec.PAIRED_OUTER:
+        assert any(c.form == "lane+outer" and ec.outer_bits(c) == (bit,) for c in PAIRED), bit
+    assert flags == {(False, False), (False, True), (True, False), (True, True)}
+    for c, images in planned_paired.values():
+        if c.family == "ASWAP1":
+            assert ec.direct_flags(images) == {(False, False)}, ec.case_id(c)
+
+
+def _records_plain(img, move):
+    """The record stream of an image as comparable values; `move` relabels the bits of the outer masks."""
+    out = []
+    for rec in ti.records(img):
+        if rec[0] == "group":
+            out.append(("group", tuple(rec[1])))
+            continue
+        _, case, blk, outer, dbl, _, size = rec
+        mask = sum(1 << move.get(b, b) for b in range(64) if (abs(outer) >> b) & 1)
+        out.append(("gate", case, blk, mask if outer >= 0 else -mask, size, dbl(0, (size - 16) // 8).tobytes()))
+    return out
+
+
+def test_paired_interpreter_equals_the_longdouble_reference_on_the_active_register(planned_paired):
+    """The lists touch index bits 0..11 and 23 only.  On the 13-qubit active register (23 relabelled 12) the planner
+    emits the same records as at 24 qubits but for that bit of the outer masks, and their numpy walk == the
+    extended-precision reference to 1e-13: lists, records and reference agree where the device test takes them from."""
+    for seed, (cid, (c, images)) in enumerate(planned_paired.items()):
+        ops = ec.to_active(c.ops)
+        small = ti.plan(ec.PAIRED_ACTIVE, ops)
+        assert len(small) == 1 and int(small[0]["order"]) == int(images[0]["order"]), cid
+        assert _records_plain(small[0], {}) == _records_plain(images[0], {23: 12}), cid
+        psi = ec.random_state(ec.PAIRED_ACTIVE, 3000 + seed)
+        want = ec.reference(psi, ops)
+        ti.run(psi, small)
+        assert float(np.max(np.abs(psi - want))) <= 1e-13, cid
+
+
+def test_multi_group_lists_of_the_paired_device_test():
+    """What the three random lists of tests/test_gpu_engine_cases_paired.py bring into a second tile: 2 or 3 passes, two of
+    them with 3 to 8 register groups (LDS traffic between them), tiles that hold bit 23 and leave lower bits out, every
+    predicate form between them, and only records the planner is known to emit."""
+    families, forms = set(), set()
+    for ops in multi_group_lists():
+        assert len(ops) == 90 and all(q <= 11 or q == 23 for qubits, _ in ops for q in qubits)
+        images = ti.plan(ec.PAIRED_N, ops)
+        assert 2 <= len(images) <= 3
+        assert all(int(img["T"]) == 11 for img in images)
+        assert any(23 in planner.tile_bits(img) and planner.tile_bits(img) != list(range(3, 10)) + [23] for img in images)
+        groups = [sum(1 for rec in ti.records(img) if rec[0] == "group") for img in images]
+        assert max(groups) >= 5 and sum(g >= 3 for g in groups) >= 2, groups
+        for text, f, v, form in ec.ledger_of_images(images):
+            assert form in ec.possible_forms(text, f, v), (f, v, form)
+            families.add(f)
+            forms.add(form)
+    assert forms == set(ec.FORMS) and len(families) >= 11, (forms, families)
+
+
+def test_product_state_of_the_paired_device_test():
+    """The device test's input and expected state on a small analogue: active qubits on index bits 0..3 and 7, spectators
+    on bits 4..6; the reference on the active register times the spectator vector == the reference on the whole index."""
+    rng = np.random.default_rng(5)
+    chi, phi = ec.random_state(5, 1), rng.standard_normal(8) + 1j * rng.standard_normal(8)
+    psi = product_state(chi, phi)
+    assert psi.dtype == np.complex128 and abs(psi[(1 << 7) | (5 << 4) | 9] - chi[16 | 9] * phi[5]) < 1e-16
+    ops = [ec.controlled(7, 1, ec.M_DENSE, True), ([3], ec.M_REAL), ec.cphase(2, 7, ec.P_GENERIC), ec.controlled(7, 0, ec.M_ANTI, False)]
+    small = ec.reference(chi, [([4 if q == 7 else q for q in qubits], U) for qubits, U in ops])
+    assert float(np.max(np.abs(ec.reference(psi, ops) - product_state(small, phi)))) < 1e-16

@@ -658,7 +658,7 @@ def test_fused_phase_runs_keep_their_order(hip, n):
 
 def test_interleaved_fused_passes_gate_kernels_and_reductions_on_one_stream(hip):
     """The shape of the code that exposed round 2's END_DIRECT bug: several chunks of ONE
-    allocation on ONE stream, fused passes (direct-in / direct-out ends, 2 tiles per workgroup) alternating with
+    allocation on ONE stream, fused passes (direct-in / direct-out ends; 512 tiles each, so one tile per workgroup) alternating with
     per-gate kernels, partner-chunk butterflies and reductions, nothing synchronised in between except where a
     result is read -- the compiler-visible registers around the engine's asm statement are reused differently by
     every neighbour.  Every amplitude of every chunk against the oracle."""
