@@ -63,9 +63,7 @@ int qsim_destroy(qsim_chunk* c) {
   (void)hipSetDevice(c->device);
   if (c->have_events) { (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1); }
   if (c->scratch) (void)hipFree(c->scratch);
-  if (c->hist) (void)hipFree(c->hist);
-  if (c->expect) (void)hipFree(c->expect);
-  if (c->sample) (void)hipFree(c->sample);
+  if (c->work) (void)hipFree(c->work);
   delete c->pending;
   delete c->deferred;
   if (c->owns_memory && c->amp) {
@@ -166,8 +164,7 @@ static int launch_copy(qsim_chunk* dst, const qsim_chunk* src, bool nt) {
   constexpr int kItems = 2;
   u64 blocks = (amps(dst) + (u64)kBlock * kItems - 1) / ((u64)kBlock * kItems);
   blocks = (blocks + 7) & ~7ull;                     // whole octets: logical_block<true> deals blocks over the 8 XCDs
-  if (nt) hipLaunchKernelGGL((k_copy<true, kItems>), grid_for(blocks), dim3(kBlock), 0, dst->stream, dst->amp, src->amp, amps(dst));
-  else hipLaunchKernelGGL((k_copy<false, kItems>), grid_for(blocks), dim3(kBlock), 0, dst->stream, dst->amp, src->amp, amps(dst));
+  QSIM_WITH_NT(hipLaunchKernelGGL((k_copy<NT, kItems>), grid_for(blocks), dim3(kBlock), 0, dst->stream, dst->amp, src->amp, amps(dst)));
   HIP_TRY(hipGetLastError());
   return QSIM_OK;
 }

@@ -394,7 +394,7 @@ int qsim_apply_2q_quad_remote(qsim_comm* cm, qsim_chunk* shard, qsim_chunk* buf,
     for (int j = 0; j < 4; ++j) {
       view[j] = *shard;                                     // device, stream, cache policy of the shard's allocation
       view[j].k = shard->k - 2;
-      view[j].owns_memory = false; view[j].scratch = nullptr; view[j].have_events = false; view[j].pending = nullptr;
+      view[j].owns_memory = false; view[j].scratch = nullptr; view[j].work = nullptr; view[j].work_bytes = 0; view[j].have_events = false; view[j].pending = nullptr;
       view[j].amp = j == my_index ? shard->amp + (u64)q * Q : (active[j] ? buf->amp + slot_of(q, j) * Q : nullptr);
     }
     if (n_act == 4) {

@@ -1,6 +1,23 @@
 // abi_readout.h -- C ABI: what is read off a chunk without changing it: norm, outcome probabilities, Pauli-sum
 // expectation values, sparse export, the closed-form checkers and the fingerprint.
 // Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
+
+// The r distinct local qubits of a readout call, as the mask *sel: null arguments, the range of r, pending parts, then
+// qubit by qubit (range, locality, repetition).
+static int check_qubit_list(qsim_chunk* c, int r, const int32_t* qubits, const void* out, int max_r, const char* what, u64* sel) {
+  if (!qubits || !out) return fail(QSIM_ERR_INVALID, "%s: null argument", what);
+  if (r < 1 || r > max_r) return fail(QSIM_ERR_INVALID, "%s: 1 <= r <= %d qubits expected, got %d", what, max_r, r);
+  int rc = require_no_parts(c, what);
+  if (rc) return rc;
+  *sel = 0;
+  for (int i = 0; i < r; ++i) {
+    if ((rc = check_local_qubit(c, qubits[i]))) return rc;
+    for (int j = 0; j < i; ++j) if (qubits[j] == qubits[i]) return fail(QSIM_ERR_INVALID, "%s: repeated qubit %d", what, qubits[i]);
+    *sel |= 1ull << qubits[i];
+  }
+  return QSIM_OK;
+}
+
 extern "C" {
 int qsim_norm2(qsim_chunk* c, double* out) {
   int rc = check_chunk(c, "qsim_norm2");
@@ -11,13 +28,7 @@ int qsim_norm2(qsim_chunk* c, double* out) {
   const unsigned grid = std::min<unsigned>(stream_grid(amps(c)), kReduceBlocks);
   hipLaunchKernelGGL(k_norm2_partial, dim3(grid), dim3(kBlock), 0, c->stream, c->amp, amps(c), c->scratch);
   HIP_TRY(hipGetLastError());
-  std::vector<double> host(grid);
-  HIP_TRY(hipMemcpyAsync(host.data(), c->scratch, sizeof(double) * grid, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  long double total = 0;
-  for (double v : host) total += v;
-  *out = (double)total;
-  return QSIM_OK;
+  return reduce_partials(c, grid, 1, false, out);
 }
 
 // Joint outcome probabilities of r measured qubits: k_hist (one read-only pass, partial histograms per workgroup) and
@@ -26,16 +37,10 @@ int qsim_norm2(qsim_chunk* c, double* out) {
 int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out) {
   int rc = check_chunk(c, "qsim_probabilities");
   if (rc) return rc;
-  if (!qubits || !out) return fail(QSIM_ERR_INVALID, "qsim_probabilities: null argument");
-  if (r < 1 || r > 8) return fail(QSIM_ERR_INVALID, "qsim_probabilities: 1 <= r <= 8 qubits expected, got %d", r);
-  if ((rc = require_no_parts(c, "qsim_probabilities"))) return rc;
-  u64 sel = 0;
-  for (int i = 0; i < r; ++i) {
-    if ((rc = check_local_qubit(c, qubits[i]))) return rc;
-    for (int j = 0; j < i; ++j) if (qubits[j] == qubits[i]) return fail(QSIM_ERR_INVALID, "qsim_probabilities: repeated qubit %d", qubits[i]);
-    sel |= 1ull << qubits[i];
-  }
-  if ((rc = ensure_hist(c))) return rc;
+  u64 sel;
+  if ((rc = check_qubit_list(c, r, qubits, out, 8, "qsim_probabilities", &sel))) return rc;
+  if ((rc = ensure_work(c, sizeof(double) * kHistDoubles))) return rc;
+  double* const partial = static_cast<double*>(c->work);
   HIP_TRY(hipSetDevice(c->device));
   const int k = c->k;
   const int above = std::max(0, k - 8);
@@ -63,31 +68,24 @@ int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out)
   a.n_wg_bits = n_wg;
   const u64 all_hi = k > 8 ? (((1ull << k) - 1) & ~255ull) : 0;
   a.loop_mask = all_hi & ~used;
-  a.partial = c->hist;
+  a.partial = partial;
   const int nbins = 1 << r;
   const unsigned grid = 1u << n_wg;
-  double* dev_out = c->hist + ((u64)grid << 8);
+  double* dev_out = partial + ((u64)grid << 8);
   const bool nt = c->span_bytes > tuning().mall_bytes;
   {
     ProfileScope prof(8, 16.0 * (double)amps(c), c->stream, nt);
-#define QSIM_HIST_LAUNCH(IB)                                                                                     \
-    if (nt) hipLaunchKernelGGL((k_hist<IB, true>), dim3(grid), dim3(kBlock), 0, c->stream, a);                    \
-    else hipLaunchKernelGGL((k_hist<IB, false>), dim3(grid), dim3(kBlock), 0, c->stream, a);
     switch (n_item) {
-      case 0: QSIM_HIST_LAUNCH(0) break;
-      case 1: QSIM_HIST_LAUNCH(1) break;
-      case 2: QSIM_HIST_LAUNCH(2) break;
-      default: QSIM_HIST_LAUNCH(3) break;
+      case 0: QSIM_WITH_NT(hipLaunchKernelGGL((k_hist<0, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a)); break;
+      case 1: QSIM_WITH_NT(hipLaunchKernelGGL((k_hist<1, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a)); break;
+      case 2: QSIM_WITH_NT(hipLaunchKernelGGL((k_hist<2, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a)); break;
+      default: QSIM_WITH_NT(hipLaunchKernelGGL((k_hist<3, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a)); break;
     }
-#undef QSIM_HIST_LAUNCH
     HIP_TRY(hipGetLastError());
     prof.done(c->stream);
   }
-  hipLaunchKernelGGL(k_hist_sum, dim3(nbins), dim3(kBlock), 0, c->stream, (const double*)c->hist, (int)grid, nbins, dev_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, dev_out, sizeof(double) * nbins, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QSIM_OK;
+  if ((rc = sum_rows(c, partial, grid, nbins, dev_out))) return rc;
+  return fetch_doubles(c, dev_out, (u64)nbins, out);
 }
 
 // Pauli-sum expectation values (expect_kernels.h): the pass plan on the host, then per pass k_expect_tile (or
@@ -102,20 +100,6 @@ int qsim_plan_expectation(int n_local_qubits, int n_terms, const uint64_t* x_mas
   for (int t = 0; t < n_terms; ++t) pass_of_term[t] = p.pass_of[(size_t)t];
   for (size_t q = 0; q < p.tile.size(); ++q) tile_masks[q] = p.tile[q];
   *n_passes = (int)p.tile.size();
-  return QSIM_OK;
-}
-
-static int ensure_expect(qsim_chunk* c, u64 bytes) {
-  if (c->expect_bytes >= bytes) return QSIM_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  if (c->expect) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipFree(c->expect));
-    c->expect = nullptr;
-    c->expect_bytes = 0;
-  }
-  HIP_TRY(hipMalloc(&c->expect, bytes));
-  c->expect_bytes = bytes;
   return QSIM_OK;
 }
 
@@ -165,8 +149,8 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
   for (int q = 0; q < np; ++q) max_count = std::max(max_count, p.count[q]);
   const u64 partial_bytes = sizeof(double) * (u64)kExpMaxWg * (u64)max_count;
   const u64 table_off = partial_bytes, out_off = table_off + sizeof(ExpTerm) * (u64)n_terms;
-  if ((rc = ensure_expect(c, out_off + sizeof(double) * (u64)n_terms))) return rc;
-  char* base = static_cast<char*>(c->expect);
+  if ((rc = ensure_work(c, out_off + sizeof(double) * (u64)n_terms))) return rc;
+  char* base = static_cast<char*>(c->work);
   double* partial = reinterpret_cast<double*>(base);
   ExpTerm* dev_table = reinterpret_cast<ExpTerm*>(base + table_off);
   double* dev_out = reinterpret_cast<double*>(base + out_off);
@@ -188,12 +172,9 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
       w.cr = table[(size_t)first[q]].cr;
       w.ci = table[(size_t)first[q]].ci;
       const unsigned grid = (unsigned)std::min<u64>(std::max<u64>(w.half / kBlock, 1), kExpMaxWg);
-      if (nt) hipLaunchKernelGGL((k_expect_wide<true>), dim3(grid), dim3(kBlock), 0, c->stream, w);
-      else hipLaunchKernelGGL((k_expect_wide<false>), dim3(grid), dim3(kBlock), 0, c->stream, w);
+      QSIM_WITH_NT(hipLaunchKernelGGL((k_expect_wide<NT>), dim3(grid), dim3(kBlock), 0, c->stream, w));
       HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_hist_sum, dim3(1), dim3(kBlock), 0, c->stream, (const double*)partial, (int)grid, 1,
-                         dev_out + first[q]);
-      HIP_TRY(hipGetLastError());
+      if ((rc = sum_rows(c, partial, grid, 1, dev_out + first[q]))) return rc;
       continue;
     }
     ExpArgs a;
@@ -211,16 +192,12 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
     while (slices * 2 * a.n_terms <= kBlock) slices *= 2;
     a.slices = slices;
     const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, grid_tile);
-    if (nt) hipLaunchKernelGGL((k_expect_tile<true>), dim3(grid), dim3(kBlock), 0, c->stream, a);
-    else hipLaunchKernelGGL((k_expect_tile<false>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+    QSIM_WITH_NT(hipLaunchKernelGGL((k_expect_tile<NT>), dim3(grid), dim3(kBlock), 0, c->stream, a));
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_hist_sum, dim3(a.n_terms), dim3(kBlock), 0, c->stream, (const double*)partial, (int)grid,
-                       a.n_terms, dev_out + first[q]);
-    HIP_TRY(hipGetLastError());
+    if ((rc = sum_rows(c, partial, grid, a.n_terms, dev_out + first[q]))) return rc;
   }
   std::vector<double> res((size_t)n_terms);
-  HIP_TRY(hipMemcpyAsync(res.data(), dev_out, sizeof(double) * (u64)n_terms, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((rc = fetch_doubles(c, dev_out, (u64)n_terms, res.data()))) return rc;
   for (int t = 0; t < n_terms; ++t) out[t] = res[(size_t)order[(size_t)t]];
   *n_passes = np;
   return QSIM_OK;
@@ -228,20 +205,13 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
 
 // Reduced density matrix (rdm_kernels.h): one read-only pass (k_rdm_small for r <= 3, k_rdm_mfma for r = 4..6), one
 // partial matrix of 4^r doubles per workgroup, k_hist_sum over them in workgroup order; the triangle is mirrored on the
-// host.  The scratch is the expectation buffer (ensure_expect): at most (kRdmMaxWg + 1) * 4^r doubles, that is 32 MiB +
+// host.  In the workspace (ensure_work): at most (kRdmMaxWg + 1) * 4^r doubles, that is 32 MiB +
 // 32 KiB at r = 6, 8 MiB at r = 5, 2 MiB at r = 4, 512 KiB at r = 3 (and grid + 1 matrices for chunks of fewer tiles).
 int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, double* out) {
   int rc = check_chunk(c, "qsim_reduced_density_matrix");
   if (rc) return rc;
-  if (!qubits || !out) return fail(QSIM_ERR_INVALID, "qsim_reduced_density_matrix: null argument");
-  if (r < 1 || r > kRdmMaxQubits) return fail(QSIM_ERR_INVALID, "qsim_reduced_density_matrix: 1 <= r <= 6 qubits expected, got %d", r);
-  if ((rc = require_no_parts(c, "qsim_reduced_density_matrix"))) return rc;
-  u64 sel = 0;
-  for (int i = 0; i < r; ++i) {
-    if ((rc = check_local_qubit(c, qubits[i]))) return rc;
-    for (int j = 0; j < i; ++j) if (qubits[j] == qubits[i]) return fail(QSIM_ERR_INVALID, "qsim_reduced_density_matrix: repeated qubit %d", qubits[i]);
-    sel |= 1ull << qubits[i];
-  }
+  u64 sel;
+  if ((rc = check_qubit_list(c, r, qubits, out, kRdmMaxQubits, "qsim_reduced_density_matrix", &sel))) return rc;
   const int k = c->k, tb = std::min(k, kRdmTileBits), eb = tb - r;
   const u64 all = (1ull << k) - 1;
   u64 T = sel | ((1ull << std::min(k, kExpLineBits)) - 1);
@@ -270,16 +240,14 @@ int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, dou
     if (qubits[q] < kExpLineBits && free_bit < std::min(eb, kExpLineBits)) a.swz[q] = 1 << free_bit++;
   const int dd = 1 << (2 * r), dim = 1 << r;
   const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, kRdmMaxWg);
-  if ((rc = ensure_expect(c, sizeof(double) * ((u64)grid + 1) * (u64)dd))) return rc;
-  a.partial = static_cast<double*>(c->expect);
+  if ((rc = ensure_work(c, sizeof(double) * ((u64)grid + 1) * (u64)dd))) return rc;
+  a.partial = static_cast<double*>(c->work);
   double* dev_out = a.partial + (u64)grid * dd;
   HIP_TRY(hipSetDevice(c->device));
   const bool nt = c->span_bytes > tuning().mall_bytes;
   {
     ProfileScope prof(11, 16.0 * (double)amps(c), c->stream, nt);
-#define QSIM_RDM_LAUNCH(KERNEL, R)                                                                      \
-    if (nt) hipLaunchKernelGGL((KERNEL<R, true>), dim3(grid), dim3(kBlock), 0, c->stream, a);           \
-    else hipLaunchKernelGGL((KERNEL<R, false>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+#define QSIM_RDM_LAUNCH(KERNEL, R) QSIM_WITH_NT(hipLaunchKernelGGL((KERNEL<R, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a));
 #ifdef QSIM_PROBES
     if (tuning().rdm_form == 1 && r >= 4) {
       if (r == 4) { QSIM_RDM_LAUNCH(k_rdm_block, 4) } else if (r == 5) { QSIM_RDM_LAUNCH(k_rdm_block, 5) } else { QSIM_RDM_LAUNCH(k_rdm_block, 6) }
@@ -297,11 +265,9 @@ int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, dou
     HIP_TRY(hipGetLastError());
     prof.done(c->stream);
   }
-  hipLaunchKernelGGL(k_hist_sum, dim3(dd), dim3(kBlock), 0, c->stream, (const double*)a.partial, (int)grid, dd, dev_out);
-  HIP_TRY(hipGetLastError());
+  if ((rc = sum_rows(c, a.partial, grid, dd, dev_out))) return rc;
   std::vector<double> tri((size_t)dd);
-  HIP_TRY(hipMemcpyAsync(tri.data(), dev_out, sizeof(double) * (u64)dd, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((rc = fetch_doubles(c, dev_out, (u64)dd, tri.data()))) return rc;
   for (int x = 0; x < dim; ++x) {                   // the triangle and its mirror image: exactly Hermitian
     out[2 * (x * dim + x)] = tri[(size_t)(x * dim + x)];
     out[2 * (x * dim + x) + 1] = 0.0;
@@ -349,8 +315,8 @@ int qsim_sample(qsim_chunk* c, uint64_t n_shots, const double* randnums, uint64_
   // device scratch: block sums | shot slots | hit blocks | first shot of every hit block (+ 1)
   const u64 slot_off = sizeof(double) * n_blocks, hit_off = slot_off + sizeof(u64) * n_shots;
   const u64 first_off = hit_off + sizeof(u64) * n_shots;
-  if ((rc = ensure_sample(c, first_off + sizeof(unsigned) * (n_shots + 1)))) return rc;
-  char* base = static_cast<char*>(c->sample);
+  if ((rc = ensure_work(c, first_off + sizeof(unsigned) * (n_shots + 1)))) return rc;
+  char* base = static_cast<char*>(c->work);
   double* dev_sums = reinterpret_cast<double*>(base);
   u64* dev_slot = reinterpret_cast<u64*>(base + slot_off);
   u64* dev_hit = reinterpret_cast<u64*>(base + hit_off);
@@ -359,14 +325,12 @@ int qsim_sample(qsim_chunk* c, uint64_t n_shots, const double* randnums, uint64_
   const bool nt = c->span_bytes > tuning().mall_bytes;
   {
     ProfileScope prof(9, 16.0 * (double)n, c->stream, nt);
-    if (nt) hipLaunchKernelGGL((k_sample_block_sums<true>), grid_for(n_blocks), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, dev_sums);
-    else hipLaunchKernelGGL((k_sample_block_sums<false>), grid_for(n_blocks), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, dev_sums);
+    QSIM_WITH_NT(hipLaunchKernelGGL((k_sample_block_sums<NT>), grid_for(n_blocks), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, dev_sums));
     HIP_TRY(hipGetLastError());
     prof.done(c->stream);
   }
   std::vector<double> cdf(n_blocks);
-  HIP_TRY(hipMemcpyAsync(cdf.data(), dev_sums, sizeof(double) * n_blocks, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((rc = fetch_doubles(c, dev_sums, n_blocks, cdf.data()))) return rc;
   *n_passes = 1;
   long double run = 0;                               // the block prefix, in block order (rounding to double keeps it monotone)
   for (u64 b = 0; b < n_blocks; ++b) { run += cdf[b]; cdf[b] = (double)run; }
@@ -392,8 +356,7 @@ int qsim_sample(qsim_chunk* c, uint64_t n_shots, const double* randnums, uint64_
   HIP_TRY(hipMemcpyAsync(dev_first, first.data(), sizeof(unsigned) * (n_hit + 1), hipMemcpyHostToDevice, c->stream));
   {
     ProfileScope prof(10, 16.0 * (double)std::min<u64>(n, n_hit << kSampleBlockBits), c->stream, nt);
-    if (nt) hipLaunchKernelGGL((k_sample_resolve<true>), grid_for(n_hit), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, (const u64*)dev_hit, (const unsigned*)dev_first, n_hit, dev_slot);
-    else hipLaunchKernelGGL((k_sample_resolve<false>), grid_for(n_hit), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, (const u64*)dev_hit, (const unsigned*)dev_first, n_hit, dev_slot);
+    QSIM_WITH_NT(hipLaunchKernelGGL((k_sample_resolve<NT>), grid_for(n_hit), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, (const u64*)dev_hit, (const unsigned*)dev_first, n_hit, dev_slot));
     HIP_TRY(hipGetLastError());
     prof.done(c->stream);
   }
@@ -495,13 +458,7 @@ int qsim_max_abs_err_closed_form_perm(qsim_chunk* c, int kind, int n_total_qubit
   hipLaunchKernelGGL(k_closed_form_err, dim3(grid), dim3(kBlock), 0, c->stream, c->amp, amps(c), kind,
                      n_total_qubits, (u64)base_index, c->scratch, perm);
   HIP_TRY(hipGetLastError());
-  std::vector<double> host(grid);
-  HIP_TRY(hipMemcpyAsync(host.data(), c->scratch, sizeof(double) * grid, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  double worst = 0;
-  for (double v : host) worst = std::max(worst, v);
-  *out = worst;
-  return QSIM_OK;
+  return reduce_partials(c, grid, 1, true, out);
 }
 
 // sum over the chunk's amplitudes whose logical index passes the filter of amp * w(logical index): see k_fingerprint
@@ -521,13 +478,6 @@ int qsim_fingerprint(qsim_chunk* c, int n_total_qubits, uint64_t base_index, con
   hipLaunchKernelGGL(k_fingerprint, dim3(grid), dim3(kBlock), 0, c->stream, c->amp, amps(c), n_total_qubits, (u64)base_index,
                      fp_mix((u64)seed), (u64)sel_mask, (u64)sel_value, c->scratch, perm);
   HIP_TRY(hipGetLastError());
-  std::vector<double> host(2 * (size_t)grid);
-  HIP_TRY(hipMemcpyAsync(host.data(), c->scratch, sizeof(double) * host.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  long double re = 0, im = 0;
-  for (unsigned b = 0; b < grid; ++b) { re += host[2 * b]; im += host[2 * b + 1]; }
-  out[0] = (double)re;
-  out[1] = (double)im;
-  return QSIM_OK;
+  return reduce_partials(c, grid, 2, false, out);
 }
 }  // extern "C"

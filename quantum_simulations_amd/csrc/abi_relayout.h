@@ -1,6 +1,7 @@
 // abi_relayout.h -- C ABI: slab packing (the two ends of an all-to-all re-layout), the in-place swap between chunks of one
 // device, and qsim_apply_ops_io: an op list with the re-layout fused into its ends, whole or in pieces (_part / _load).
 // Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
+#include "slab_kernels.h"
 
 // The m (local bit, rank bit) pairs of a re-layout: in range and distinct (`what`, `shards`, `index_bit`: the caller's words).
 static int check_swapped_bits(int k, int g_bits, int m, const int32_t* local_bits, const int32_t* global_bits, const char* what,

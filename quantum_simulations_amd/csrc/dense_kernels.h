@@ -316,12 +316,7 @@ __global__ __launch_bounds__(64) void k_dense_small(const DenseSmallArgs a) {
 }
 
 // The launcher: what qsim_apply_fused_k does with a checked block of k = 3 .. 6 distinct local qubits (the matrix goes to the
-// chunk's scratch).  QSIM_DENSE_NT: `nt` (run time) -> the kernels' NT template argument, the statement once for each value.
-#define QSIM_DENSE_NT(...)                              \
-  do {                                                  \
-    if (nt) { constexpr bool NT = true; __VA_ARGS__; }  \
-    else { constexpr bool NT = false; __VA_ARGS__; }    \
-  } while (0)
+// chunk's scratch).
 static int apply_dense_block(qsim_chunk* c, int k, const int32_t* qubits, const double* M) {
   HIP_TRY(hipSetDevice(c->device));
   const int rc = ensure_scratch(c);
@@ -350,13 +345,13 @@ static int apply_dense_block(qsim_chunk* c, int k, const int32_t* qubits, const 
       const u64 waves = (d.col_blocks + kDenseMfmaColBlocksPerWave - 1) / kDenseMfmaColBlocksPerWave;
       u64 wgs = (waves + kBlock / 64 - 1) / (kBlock / 64);
       wgs = (wgs + 7) & ~7ull;
-      if (k == 3) QSIM_DENSE_NT(hipLaunchKernelGGL((k_dense_mfma<3, NT>), grid_for(wgs), dim3(kBlock), 0, c->stream, d));
-      else QSIM_DENSE_NT(hipLaunchKernelGGL((k_dense_mfma<4, NT>), grid_for(wgs), dim3(kBlock), 0, c->stream, d));
+      if (k == 3) QSIM_WITH_NT(hipLaunchKernelGGL((k_dense_mfma<3, NT>), grid_for(wgs), dim3(kBlock), 0, c->stream, d));
+      else QSIM_WITH_NT(hipLaunchKernelGGL((k_dense_mfma<4, NT>), grid_for(wgs), dim3(kBlock), 0, c->stream, d));
     } else {
       u64 blocks = (a.count + kBlock - 1) / kBlock;
       blocks = (blocks + 7) & ~7ull;
-      if (k == 3) QSIM_DENSE_NT(hipLaunchKernelGGL((k_dense<3, NT>), grid_for(blocks), dim3(kBlock), 0, c->stream, a));
-      else QSIM_DENSE_NT(hipLaunchKernelGGL((k_dense<4, NT>), grid_for(blocks), dim3(kBlock), 0, c->stream, a));
+      if (k == 3) QSIM_WITH_NT(hipLaunchKernelGGL((k_dense<3, NT>), grid_for(blocks), dim3(kBlock), 0, c->stream, a));
+      else QSIM_WITH_NT(hipLaunchKernelGGL((k_dense<4, NT>), grid_for(blocks), dim3(kBlock), 0, c->stream, a));
     }
     prof.done(c->stream);
     HIP_TRY(hipGetLastError());
@@ -395,14 +390,14 @@ static int apply_dense_block(qsim_chunk* c, int k, const int32_t* qubits, const 
     if (k <= 4) {
       const u64 waves = (d.col_blocks + groups - 1) / groups;
       const unsigned grid = (unsigned)std::min<u64>(((std::max<u64>((waves + 3) / 4, 1) + 7) & ~7ull), 1u << 20);   // (whole octets: one region per XCD)
-      if (k == 3) QSIM_DENSE_NT(launch_dense_mfma2<3, NT, 256>(d, grid, c->stream, pf));
-      else QSIM_DENSE_NT(launch_dense_mfma2<4, NT, 256>(d, grid, c->stream, pf));
+      if (k == 3) QSIM_WITH_NT(launch_dense_mfma2<3, NT, 256>(d, grid, c->stream, pf));
+      else QSIM_WITH_NT(launch_dense_mfma2<4, NT, 256>(d, grid, c->stream, pf));
     } else if (k == 5) {
       const unsigned grid = (unsigned)std::min<u64>((std::max<u64>((d.col_blocks + 3) / 4, 1) + 7) & ~7ull, (u64)cus * wgs_per_cu);
-      QSIM_DENSE_NT(launch_dense_mfma2<5, NT, 256>(d, grid, c->stream, pf));
+      QSIM_WITH_NT(launch_dense_mfma2<5, NT, 256>(d, grid, c->stream, pf));
     } else {
       const unsigned grid = (unsigned)std::min<u64>((std::max<u64>((d.col_blocks + 7) / 8, 1) + 7) & ~7ull, (u64)cus);
-      QSIM_DENSE_NT(launch_dense_mfma2<6, NT, 512>(d, grid, c->stream, pf));
+      QSIM_WITH_NT(launch_dense_mfma2<6, NT, 512>(d, grid, c->stream, pf));
     }
   } else {
     DenseSmallArgs a;
@@ -416,4 +411,3 @@ static int apply_dense_block(qsim_chunk* c, int k, const int32_t* qubits, const 
   HIP_TRY(hipGetLastError());
   return QSIM_OK;
 }
-#undef QSIM_DENSE_NT

@@ -1,5 +1,5 @@
 // expect_kernels.h -- expectation values of Pauli sums (qsim_plan_expectation, qsim_expectation_pauli).
-// Part of the single translation unit qsim_hip.hip (included there after misc_kernels.h; not a standalone header).
+// Part of the single translation unit qsim_hip.hip (included there after readout_kernels.h; not a standalone header).
 //
 // A Pauli string is two masks of physical index bits: x = the bits that carry X or Y, z = the bits that carry Z or Y.
 // With ny = popcount(x & z) (Y = i X Z):   <psi|P|psi> = sum_i (-1)^popcount(i & z) Re(i^ny conj(psi_{i ^ x}) psi_i).

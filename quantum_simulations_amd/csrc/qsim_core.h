@@ -1,4 +1,4 @@
-// qsim_core.h -- error plumbing and the chunk handle.
+// qsim_core.h -- error plumbing, the chunk handle and its argument checks.
 // Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
 // ------------------------------------------------------------------ error plumbing
 static thread_local std::string g_err;
@@ -31,12 +31,9 @@ struct qsim_chunk {
   qsim_chunk* parent;    // for views (keeps nothing alive; caller orders destruction)
   hipEvent_t ev0, ev1;   // timing
   bool have_events;
-  double* scratch;       // reduction workspace (lazily allocated, owned)
-  double* hist;          // qsim_probabilities: partial histograms (lazily allocated, owned)
-  void* expect;          // qsim_expectation_pauli: partial rows, term tables, results (grown on demand, owned)
-  u64 expect_bytes;
-  void* sample;          // qsim_sample: block sums, hit-block lists, shot slots (grown on demand, owned)
-  u64 sample_bytes;
+  double* scratch;       // reduction partials and the dense block's matrix: 64 KiB (lazily allocated, owned)
+  void* work;            // the readout workspace: what the last readout call laid out in it (ensure_work: grown on demand, owned)
+  u64 work_bytes;
   int last_passes;       // HBM passes of the last qsim_apply_ops
   u64 span_bytes;        // size of the allocation the chunk lives in (cache-policy choice)
   struct PendingLast* pending;   // split form of qsim_apply_ops_io: the slab-storing pass, planned but not yet launched (owned)
@@ -62,3 +59,38 @@ static int device_stream(int device, hipStream_t* out) {
 }
 
 static inline u64 amps(const qsim_chunk* c) { return 1ull << c->k; }
+
+// `nt` (run time) -> the kernels' NT template argument: the statement once for each value.
+#define QSIM_WITH_NT(...)                               \
+  do {                                                  \
+    if (nt) { constexpr bool NT = true; __VA_ARGS__; }  \
+    else { constexpr bool NT = false; __VA_ARGS__; }    \
+  } while (0)
+
+// ------------------------------------------------------------------ argument checks
+static int check_chunk(const qsim_chunk* c, const char* what) {
+  if (!c || !c->amp) return fail(QSIM_ERR_INVALID, "%s: null chunk", what);
+  return QSIM_OK;
+}
+
+static int check_local_qubit(const qsim_chunk* c, int q) {
+  if (q < 0) return fail(QSIM_ERR_INVALID, "qubit %d is negative", q);
+  if (q >= c->k)
+    return fail(QSIM_ERR_NONLOCAL,
+                "qubit %d >= log2(chunk_size)=%d: non-local gate requires layout/collect step",
+                q, c->k);
+  return QSIM_OK;
+}
+
+static int check_group(qsim_chunk* const* cs, int n, const char* what) {
+  for (int i = 0; i < n; ++i) {
+    int rc = check_chunk(cs[i], what);
+    if (rc) return rc;
+    if (cs[i]->k != cs[0]->k) return fail(QSIM_ERR_INVALID, "%s: chunks differ in size", what);
+    if (cs[i]->device != cs[0]->device)
+      return fail(QSIM_ERR_INVALID, "%s: chunks live on different devices", what);
+    for (int j = 0; j < i; ++j)
+      if (cs[i]->amp == cs[j]->amp) return fail(QSIM_ERR_INVALID, "%s: the same chunk twice", what);
+  }
+  return QSIM_OK;
+}

@@ -53,7 +53,8 @@ typedef unsigned long long u64;
 #include "tile_search.h"
 #include "op_rewrite.h"
 #include "tile_launch.h"
-#include "misc_kernels.h"
+#include "state_kernels.h"
+#include "readout_kernels.h"
 #include "dense_kernels.h"
 #include "expect_kernels.h"
 #include "rdm_kernels.h"

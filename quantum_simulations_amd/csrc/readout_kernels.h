@@ -1,157 +1,7 @@
-// misc_kernels.h -- argument checks and the non-gate kernels (fill, norm, pack, closed-form checkers); the dense block: dense_kernels.h.
+// readout_kernels.h -- what every read-only pass over a chunk shares: the block reductions, the norm, the histogram and
+// its row sum, the sparse export, the closed-form checker, the fingerprint, the chunk's device buffers and the finish of
+// a call.
 // Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
-// ------------------------------------------------------------------ argument checks
-static int check_chunk(const qsim_chunk* c, const char* what) {
-  if (!c || !c->amp) return fail(QSIM_ERR_INVALID, "%s: null chunk", what);
-  return QSIM_OK;
-}
-
-static int check_local_qubit(const qsim_chunk* c, int q) {
-  if (q < 0) return fail(QSIM_ERR_INVALID, "qubit %d is negative", q);
-  if (q >= c->k)
-    return fail(QSIM_ERR_NONLOCAL,
-                "qubit %d >= log2(chunk_size)=%d: non-local gate requires layout/collect step",
-                q, c->k);
-  return QSIM_OK;
-}
-
-static int check_group(qsim_chunk* const* cs, int n, const char* what) {
-  for (int i = 0; i < n; ++i) {
-    int rc = check_chunk(cs[i], what);
-    if (rc) return rc;
-    if (cs[i]->k != cs[0]->k) return fail(QSIM_ERR_INVALID, "%s: chunks differ in size", what);
-    if (cs[i]->device != cs[0]->device)
-      return fail(QSIM_ERR_INVALID, "%s: chunks live on different devices", what);
-    for (int j = 0; j < i; ++j)
-      if (cs[i]->amp == cs[j]->amp) return fail(QSIM_ERR_INVALID, "%s: the same chunk twice", what);
-  }
-  return QSIM_OK;
-}
-
-// ------------------------------------------------------------------ misc kernels
-__global__ void k_fill_zero(double2* p, u64 n, int set0) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    p[i] = make_double2((i == 0 && set0) ? 1.0 : 0.0, 0.0);
-}
-
-__device__ __forceinline__ u64 splitmix64(u64 x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-// amplitude i = (u(2i), u(2i+1)), u(j) = (splitmix64(seed + j) >> 11) * 2^-52 - 1 in [-1, 1)
-__global__ void k_fill_random(double2* p, u64 n, u64 seed) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double re = (double)(splitmix64(seed + 2 * i) >> 11) * (1.0 / 4503599627370496.0) - 1.0;
-    const double im = (double)(splitmix64(seed + 2 * i + 1) >> 11) * (1.0 / 4503599627370496.0) - 1.0;
-    p[i] = make_double2(re, im);
-  }
-}
-
-__global__ void k_scale(double2* p, u64 n, double s) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    double2 v = p[i];
-    p[i] = make_double2(v.x * s, v.y * s);
-  }
-}
-
-// NT: streaming (non-temporal) accesses for copies larger than the Infinity Cache -- the same cache
-// policy the gate kernels use; this copy is also bench.py's same-run device-to-device ceiling.
-// One-shot grid, ITEMS 16-byte elements per thread, XCD-contiguous block order (the shape of the gate
-// kernels: grid-stride loops are 5-8 % slower, tools/bw_probe.hip).
-template <bool NT, int ITEMS>
-__global__ __launch_bounds__(kBlock) void k_copy(double2* __restrict__ dst, const double2* __restrict__ src, u64 n) {
-  const u64 first = (logical_block<true>() * ITEMS) * kBlock + threadIdx.x;
-  double2 v[ITEMS];
-#pragma unroll
-  for (int r = 0; r < ITEMS; ++r) if (first + (u64)r * kBlock < n) v[r] = ld_amp<NT>(src + first + (u64)r * kBlock);
-#pragma unroll
-  for (int r = 0; r < ITEMS; ++r) if (first + (u64)r * kBlock < n) st_amp<NT>(dst + first + (u64)r * kBlock, v[r]);
-}
-
-// dst[j] = src[insert(j, bit, value)]  /  inverse
-__global__ void k_pack_half(double2* __restrict__ dst, const double2* __restrict__ src, u64 n_half,
-                            int bit, u64 value_off) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n_half; j += stride) {
-    const u64 i = (((j >> bit) << (bit + 1)) | (j & ((1ull << bit) - 1))) | value_off;
-    dst[j] = src[i];
-  }
-}
-__global__ void k_unpack_half(double2* __restrict__ dst, const double2* __restrict__ src, u64 n_half,
-                              int bit, u64 value_off) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n_half; j += stride) {
-    const u64 i = (((j >> bit) << (bit + 1)) | (j & ((1ull << bit) - 1))) | value_off;
-    dst[i] = src[j];
-  }
-}
-
-// slab gather / scatter for the all-to-all re-layout: j runs over the 2^(k-m) amplitudes whose
-// bits `pos` equal the pattern folded into value_off
-__global__ void k_pack_bits(double2* __restrict__ dst, const double2* __restrict__ src, u64 n_slab,
-                            int npos, int p0, int p1, int p2, u64 value_off) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n_slab; j += stride)
-    dst[j] = ld_amp<true>(src + (expand_index(j, npos, p0, p1, p2) | value_off));
-}
-__global__ void k_unpack_bits(double2* __restrict__ dst, const double2* __restrict__ src, u64 n_slab,
-                              int npos, int p0, int p1, int p2, u64 value_off) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n_slab; j += stride)
-    dst[expand_index(j, npos, p0, p1, p2) | value_off] = ld_amp<true>(src + j);
-}
-
-// All slabs in one pass: amplitude i goes to slab pattern(i) at its compressed index (and back).
-// Consecutive lanes read consecutive amplitudes, and the <= 8 slabs a wave feeds each receive a
-// contiguous run, so reads and writes are whole 128-B lines for ANY choice of bits -- the
-// per-pattern kernels above touch 16 B of every line when a selected bit is below 3
-// (tools/relayout_probe.py: 0.7-1.0 TB/s instead of 4.5-5; the gather side of unpack with lanes of
-// one line 8 apart still runs at 2.6-3.5 TB/s).  `skip` = the pattern that stays.
-__device__ __forceinline__ u64 drop_bit(u64 x, int p) { return ((x >> (p + 1)) << p) | (x & ((1ull << p) - 1)); }
-template <bool PACK>
-__global__ void k_slabs_all(double2* __restrict__ state, double2* __restrict__ buf, u64 n, int m,
-                            int b0, int b1, int b2, int s_hi, int s_mid, int s_lo, int slab_bits, int skip,
-                            int n_piece_bits, int pb0, int pb1, int pb2, int piece) {
-  // A piece = the amplitudes whose top `n_piece_bits` non-selected index bits equal `piece`: the
-  // same contiguous sub-range of every slab, so the exchange can be pipelined piece by piece.
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) {
-    u64 i = t;
-    if (n_piece_bits > 0) i = (((i >> pb0) << (pb0 + 1)) | (i & ((1ull << pb0) - 1))) | ((u64)(piece & 1) << pb0);
-    if (n_piece_bits > 1) i = (((i >> pb1) << (pb1 + 1)) | (i & ((1ull << pb1) - 1))) | ((u64)((piece >> 1) & 1) << pb1);
-    if (n_piece_bits > 2) i = (((i >> pb2) << (pb2 + 1)) | (i & ((1ull << pb2) - 1))) | ((u64)((piece >> 2) & 1) << pb2);
-    int p = (int)((i >> b0) & 1);
-    if (m > 1) p |= (int)((i >> b1) & 1) << 1;
-    if (m > 2) p |= (int)((i >> b2) & 1) << 2;
-    if (p == skip) continue;
-    u64 j = i;
-    if (m > 2) j = drop_bit(j, s_hi);
-    if (m > 1) j = drop_bit(j, s_mid);
-    j = drop_bit(j, s_lo);
-    double2* const slot = buf + (((u64)p << slab_bits) | j);
-    if (PACK) st_amp<true>(slot, ld_amp<true>(state + i));
-    else st_amp<true>(state + i, ld_amp<true>(slot));
-  }
-}
-
-// exchange slab (bits pos == a_off pattern) of chunk A with slab (bits pos == b_off pattern) of chunk B
-__global__ void k_swap_slabs(double2* __restrict__ a, double2* __restrict__ b, u64 n_slab,
-                             int npos, int p0, int p1, int p2, u64 a_off, u64 b_off) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < n_slab; j += stride) {
-    const u64 e = expand_index(j, npos, p0, p1, p2);
-    const double2 x = a[e | a_off], y = b[e | b_off];
-    a[e | a_off] = y;
-    b[e | b_off] = x;
-  }
-}
-
 constexpr int kReduceBlocks = 2048;
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -273,24 +123,6 @@ __global__ __launch_bounds__(kBlock) void k_hist_sum(const double* partial, int 
   block_reduce_store<false>(v, out);
 }
 
-// ---- complex64 <-> complex128 on the device: the reference's chunk files are complex64 (storage/block_store.py:11),
-// so an export rounds on the GPU and moves 8 B per amplitude over PCIe instead of 16 (round to nearest even, what
-// numpy's astype(complex64) does)
-__global__ __launch_bounds__(kBlock) void k_to_c64(float2* __restrict__ dst, const double2* __restrict__ src, u64 n) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double2 v = src[i];
-    dst[i] = make_float2(__double2float_rn(v.x), __double2float_rn(v.y));
-  }
-}
-__global__ __launch_bounds__(kBlock) void k_from_c64(double2* __restrict__ dst, const float2* __restrict__ src, u64 n) {
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float2 v = src[i];
-    dst[i] = make_double2((double)v.x, (double)v.y);
-  }
-}
-
 // ---- sparse view of the state: the v3 worker's rows (idx, re, im) with its pruning rule |re| > eps or |im| > eps
 // (parallel_gate_applicator.py:372-374, state_manager.py:95-106), made on the device: a GHZ state of 30 qubits has two
 // rows, not 16 GiB.  One pass counts, a second one appends the kept amplitudes (one atomic per wave reserves the slots;
@@ -364,16 +196,10 @@ __global__ __launch_bounds__(kBlock) void k_closed_form_err(const double2* p, u6
 
 // ---- layout-aware fingerprint of a (partitioned, staged) state: sum_i amp_i * w(y_i) over the chunk's amplitudes whose
 // LOGICAL index y_i passes the filter (y & sel_mask) == sel_value, with counter-based pseudo-random complex weights of y
-// (two rounds of splitmix64 over y ^ mix(seed); real and imaginary part uniform in [-1, 1), exactly representable).
+// (two rounds of fp_mix, state_kernels.h, over y ^ mix(seed); real and imaginary part uniform in [-1, 1), exactly representable).
 // A state that is right up to rounding gives the same value wherever its amplitudes live: a shard of a multi-GPU run in
 // its staged layout, or the same index set of a one-GPU run (ref_dense.simulate semantics, ref_dense.py:44-57; layout
 // permute_state, staging.py:639-658).  Slabs that trade places, a wrong permutation or a lost phase change it at O(1).
-__host__ __device__ __forceinline__ u64 fp_mix(u64 x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 __global__ __launch_bounds__(kBlock) void k_fingerprint(const double2* p, u64 n, int n_total, u64 base, u64 seed_mix,
                                                         u64 sel_mask, u64 sel_value, double* partial, const BitPerm perm) {
   const u64 stride = (u64)gridDim.x * blockDim.x;
@@ -405,6 +231,7 @@ __global__ __launch_bounds__(kBlock) void k_fingerprint(const double2* p, u64 n,
   }
 }
 
+// ---- the chunk's device buffers
 constexpr int kScratchDoubles = 8192;      // >= kReduceBlocks reduction partials, and a 64 x 64 complex matrix (dense blocks)
 static_assert(kScratchDoubles >= kReduceBlocks, "the scratch holds the reduction partials");
 static int ensure_scratch(qsim_chunk* c) {
@@ -415,17 +242,54 @@ static int ensure_scratch(qsim_chunk* c) {
   return QSIM_OK;
 }
 
-constexpr int kHistWgBits = 11;            // qsim_probabilities: at most 2^11 workgroups (8 per CU)
-constexpr u64 kHistDoubles = (256ull << kHistWgBits) + 256;   // partial histograms + the summed one
-static int ensure_hist(qsim_chunk* c) {
-  if (!c->hist) {
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMalloc((void**)&c->hist, sizeof(double) * kHistDoubles));
+// The readout workspace: one buffer per chunk, grown on demand, laid out by whichever readout call runs (every call ends
+// with the stream synchronised, so no two layouts are alive at once).  A chunk holds the largest need so far, not the sum.
+static int ensure_work(qsim_chunk* c, u64 bytes) {
+  if (c->work_bytes >= bytes) return QSIM_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->work) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipFree(c->work));
+    c->work = nullptr;
+    c->work_bytes = 0;
+  }
+  HIP_TRY(hipMalloc(&c->work, bytes));
+  c->work_bytes = bytes;
+  return QSIM_OK;
+}
+
+// ---- the finish of a call
+// rows x n partials (one row per workgroup) -> n sums in a device slot, the rows in row order
+static int sum_rows(qsim_chunk* c, const double* partial, unsigned rows, int n, double* dev_out) {
+  hipLaunchKernelGGL(k_hist_sum, dim3(n), dim3(kBlock), 0, c->stream, partial, (int)rows, n, dev_out);
+  HIP_TRY(hipGetLastError());
+  return QSIM_OK;
+}
+
+// n doubles of the device on the host when it returns
+static int fetch_doubles(qsim_chunk* c, const double* dev, u64 n, double* host) {
+  HIP_TRY(hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return QSIM_OK;
+}
+
+// the scratch's `grid` block partials of `width` interleaved values -> out[width]: long double sums in block order, or maxima
+static int reduce_partials(qsim_chunk* c, unsigned grid, int width, bool max, double* out) {
+  std::vector<double> host((size_t)width * grid);
+  const int rc = fetch_doubles(c, c->scratch, host.size(), host.data());
+  if (rc) return rc;
+  for (int w = 0; w < width; ++w) {
+    long double total = 0;
+    double worst = 0;
+    for (unsigned b = 0; b < grid; ++b) {
+      const double v = host[(size_t)width * b + w];
+      if (max) worst = std::max(worst, v);
+      else total += v;
+    }
+    out[w] = max ? worst : (double)total;
   }
   return QSIM_OK;
 }
 
-static unsigned stream_grid(u64 n) {
-  const u64 want = (n + kBlock - 1) / kBlock;
-  return (unsigned)std::min<u64>(std::max<u64>(want, 1), 8192);
-}
+constexpr int kHistWgBits = 11;            // qsim_probabilities: at most 2^11 workgroups (8 per CU)
+constexpr u64 kHistDoubles = (256ull << kHistWgBits) + 256;   // partial histograms + the summed one

@@ -139,17 +139,3 @@ static void sample_locate(u64 n_blocks, const double* cdf, u64 n_shots, const do
     out_local[s] = b ? t - cdf[b - 1] : t;
   }
 }
-
-static int ensure_sample(qsim_chunk* c, u64 bytes) {
-  if (c->sample_bytes >= bytes) return QSIM_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  if (c->sample) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipFree(c->sample));
-    c->sample = nullptr;
-    c->sample_bytes = 0;
-  }
-  HIP_TRY(hipMalloc(&c->sample, bytes));
-  c->sample_bytes = bytes;
-  return QSIM_OK;
-}

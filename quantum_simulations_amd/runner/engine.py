@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from quantum_simulations_amd import readout
 from quantum_simulations_amd.circuit.fusion import batch_levels
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.kernel import gates as gate_table, planner
@@ -91,21 +92,18 @@ class SingleGpuEngine:
     def expectation(self, obs) -> float:
         """<psi|H|psi> (unnormalised) of a Pauli sum over LOGICAL qubits (observable.PauliSum or what it accepts),
         evaluated on the device through the current layout; the state does not move."""
-        return self.state.expectation(obs, l2p=self.l2p if self.l2p is not None else list(range(self.n)))
+        return readout.expectation(self.state, self.l2p, obs)
 
     def reduced_density_matrix(self, qubits) -> np.ndarray:
         """Reduced density matrix (unnormalised, complex128 (2^r, 2^r)) of 1 to 6 LOGICAL qubits, bit j of a row or
         column index = qubit qubits[j], evaluated on the device through the current layout; the state does not move."""
-        l2p = self.l2p if self.l2p is not None else list(range(self.n))
-        return self.state.reduced_density_matrix([l2p[int(q)] for q in qubits])
+        return readout.reduced_density_matrix(self.state, self.l2p, qubits)
 
     def sample(self, shots: int, seed: int = 0, qubits=None) -> np.ndarray:
         """`shots` samples of the register, drawn on the device through the current layout (the state does not move;
         `sampling.draw(shots, seed)` gives the uniforms): LOGICAL basis-state indices as uint64, or with `qubits` the
         marginal values (bit j = qubit qubits[j]).  `sampling.counts` turns them into {bitstring: count}."""
-        from quantum_simulations_amd import sampling
-        values = sampling.to_logical(self.state.sample(sampling.draw(shots, seed)), self.l2p)
-        return values if qubits is None else sampling.marginal(values, qubits)
+        return readout.sample(self.state, self.l2p, shots, seed, qubits)
 
     def logical_index(self, offset: int, count: int) -> np.ndarray:
         """Logical amplitude indices of the physical range [offset, offset + count) of the state in its current layout."""

@@ -23,6 +23,7 @@ from pathlib import Path
 
 import numpy as np
 
+from quantum_simulations_amd import readout
 from quantum_simulations_amd.circuit.fusion import batch_levels, split_by_locality
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.circuit.staging import atlas_stages, permute_state
@@ -306,26 +307,21 @@ def _apply_nonlocal(data: dict, qs: list[int], U: np.ndarray, k: int) -> None:
 def expectation(buf: HbmStateBuffer, obs) -> float:
     """<psi|H|psi> (unnormalised) of a Pauli sum over LOGICAL qubits on the final state of `run`, evaluated on the
     device through the staging layout `buf.log_to_phys` (nothing is downloaded or permuted)."""
-    l2p = getattr(buf, "log_to_phys", None) or list(range(buf.n_qubits))
-    return buf.state.expectation(obs, l2p=l2p)
+    return readout.expectation(buf.state, getattr(buf, "log_to_phys", None) or None, obs)
 
 
 def reduced_density_matrix(buf: HbmStateBuffer, qubits) -> np.ndarray:
     """Reduced density matrix (unnormalised, complex128 (2^r, 2^r)) of 1 to 6 LOGICAL qubits of the final state of `run`,
     bit j of a row or column index = qubit qubits[j], evaluated on the device through the staging layout
     `buf.log_to_phys` (nothing is downloaded or permuted)."""
-    l2p = getattr(buf, "log_to_phys", None) or list(range(buf.n_qubits))
-    return buf.state.reduced_density_matrix([l2p[int(q)] for q in qubits])
+    return readout.reduced_density_matrix(buf.state, getattr(buf, "log_to_phys", None) or None, qubits)
 
 
 def sample(buf: HbmStateBuffer, shots: int, seed: int = 0, qubits=None) -> np.ndarray:
     """`shots` samples of the final state of `run`, drawn on the device through the staging layout `buf.log_to_phys`
     (nothing is downloaded or permuted; `sampling.draw(shots, seed)` gives the uniforms): LOGICAL basis-state indices as
     uint64, or with `qubits` the marginal values (bit j = qubit qubits[j])."""
-    from quantum_simulations_amd import sampling
-    l2p = getattr(buf, "log_to_phys", None) or None
-    values = sampling.to_logical(buf.state.sample(sampling.draw(shots, seed)), l2p)
-    return values if qubits is None else sampling.marginal(values, qubits)
+    return readout.sample(buf.state, getattr(buf, "log_to_phys", None) or None, shots, seed, qubits)
 
 
 def collect_state(buf: HbmStateBuffer, apply_permutation: bool = False,

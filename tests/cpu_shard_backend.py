@@ -13,7 +13,7 @@ _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 def _fp_mix(x: np.ndarray) -> np.ndarray:
-    """one splitmix64 round on uint64 arrays (csrc/misc_kernels.h fp_mix)"""
+    """one splitmix64 round on uint64 arrays (csrc/state_kernels.h fp_mix)"""
     with np.errstate(over="ignore"):
         x = (x + np.uint64(0x9E3779B97F4A7C15)) & _M64
         x = ((x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)) & _M64
