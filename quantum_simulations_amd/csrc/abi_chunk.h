@@ -64,8 +64,7 @@ int qsim_destroy(qsim_chunk* c) {
   if (c->have_events) { (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1); }
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->work) (void)hipFree(c->work);
-  delete c->pending;
-  delete c->deferred;
+  delete c->split;
   if (c->owns_memory && c->amp) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(c->amp);

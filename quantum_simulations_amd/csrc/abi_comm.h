@@ -143,7 +143,7 @@ static int relayout_plan(int rank, int world, int k, int m, const int32_t* local
   const int rc = check_swapped_bits(k, g_bits, m, local_bits, global_bits, "re-layout", "shards", "rank bit");
   if (rc) return rc;
   if (n_pieces != 1 && n_pieces != 2 && n_pieces != 4 && n_pieces != 8) return fail(QSIM_ERR_INVALID, "re-layout: n_pieces must be 1, 2, 4 or 8");
-  n_pieces = 1 << piece_bits_for(k, m, n_pieces, 20);       // pieces stay >= 2^20 amplitudes: the rule of the split form
+  n_pieces = PieceCut::cut(k, m, local_bits, n_pieces).n_parts();      // pieces stay >= 2^20 amplitudes: the rule of the split form
   p->n_pieces = n_pieces;
   p->own = 0;
   for (int i = 0; i < m; ++i) p->own |= ((rank >> global_bits[i]) & 1) << i;
@@ -394,7 +394,7 @@ int qsim_apply_2q_quad_remote(qsim_comm* cm, qsim_chunk* shard, qsim_chunk* buf,
     for (int j = 0; j < 4; ++j) {
       view[j] = *shard;                                     // device, stream, cache policy of the shard's allocation
       view[j].k = shard->k - 2;
-      view[j].owns_memory = false; view[j].scratch = nullptr; view[j].work = nullptr; view[j].work_bytes = 0; view[j].have_events = false; view[j].pending = nullptr;
+      view[j].owns_memory = false; view[j].scratch = nullptr; view[j].work = nullptr; view[j].work_bytes = 0; view[j].have_events = false; view[j].split = nullptr;
       view[j].amp = j == my_index ? shard->amp + (u64)q * Q : (active[j] ? buf->amp + slot_of(q, j) * Q : nullptr);
     }
     if (n_act == 4) {

@@ -88,7 +88,8 @@ static int apply_ops_fused(qsim_chunk* c, int n_ops, const int32_t* nq, const in
   classify_ops(n_ops, nq, qubits, mats, &ops);
   int passes = 0;
   const TileHint hint = {tile_masks, n_tiles};
-  rc = run_fused(c, ops, &passes, nullptr, n_ops, nq, qubits, mats, nullptr, n_tiles ? &hint : nullptr);
+  rc = run_fused(c, ops, RawOps{n_ops, nq, qubits, mats}, n_tiles ? &hint : nullptr, nullptr, &passes,
+                 [&](TileArgs& a, int T, double alg_bytes, bool) { return dispatch_planned(c, a, T, alg_bytes); });
   c->last_passes = passes;
   return rc;
 }

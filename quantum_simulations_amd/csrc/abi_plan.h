@@ -274,7 +274,7 @@ int qsim_choose_layout(int n_local_qubits, int n_tiles, const uint64_t* tile_mas
 // (k, m, pieces asked for) -> pieces made: the rule of the split form as a pure function (schedulers, dry runs, tests)
 int qsim_split_piece_count(int n_local_qubits, int m, int dst_parts) {
   if (m < 1 || m > 3 || m > n_local_qubits || dst_parts == 0) return 1;
-  return 1 << piece_bits_for(n_local_qubits, m, dst_parts < 0 ? -dst_parts : dst_parts, dst_parts < 0 ? kTileLow : 20);
+  return PieceCut::cut(n_local_qubits, m, nullptr, dst_parts).n_parts();
 }
 
 // (k, T, fixed bits of a partial launch) -> tiles one workgroup of the fused pass takes: launch_tile's own rule

@@ -14,6 +14,16 @@ static int check_swapped_bits(int k, int g_bits, int m, const int32_t* local_bit
   }
   return QSIM_OK;
 }
+// The first of m slab bits that lies outside [0, k) or (*repeated) repeats an earlier one, in list order; -1: none does.
+static int bad_slab_bit(int k, int m, const int32_t* bits, bool* repeated) {
+  for (int i = 0; i < m; ++i) {
+    *repeated = false;
+    if (bits[i] < 0 || bits[i] >= k) return i;
+    *repeated = true;
+    for (int j = 0; j < i; ++j) if (bits[j] == bits[i]) return i;
+  }
+  return -1;
+}
 // The rank (chunk index) that differs from `rank` in having pattern d on the swapped index bits.
 static int peer_of(int rank, int m, const int32_t* global_bits, int d) {
   for (int i = 0; i < m; ++i) rank = (rank & ~(1 << global_bits[i])) | (((d >> i) & 1) << global_bits[i]);
@@ -33,6 +43,15 @@ static int partial_launch_args(const TileArgs& planned, int T, int k, const int*
     if ((g >> i) & 1) out->fix_or |= 1ull << bit;
     if (bit >= k || bit < kTileLow) return fail(QSIM_ERR_INVALID, "internal: piece bit %d", bit);
   }
+  return QSIM_OK;
+}
+// Partial launch g of a kept pass, unless it is queued already: the tiles whose top cut.nb_free piece bits have the value g.
+static int launch_group(qsim_chunk* c, const CachedPass& p, PieceCut& cut, int g) {
+  if ((cut.launched >> g) & 1) return QSIM_OK;
+  TileArgs a;
+  int rc = partial_launch_args(p.a, p.T, c->k, cut.piece_bit + (cut.nb - cut.nb_free), cut.nb_free, g, &a);
+  if (rc || (rc = launch_tile_any(a, p.T, c, c->stream, p.alg_bytes / (double)(1 << cut.nb_free)))) return rc;
+  cut.launched |= 1u << g;
   return QSIM_OK;
 }
 
@@ -64,10 +83,10 @@ static int slab_args(const qsim_chunk* c, int m, const int32_t* bits, int patter
   if (pattern < 0 || pattern >= (1 << m)) return fail(QSIM_ERR_INVALID, "slab: pattern out of range");
   int sorted[3] = {0, 0, 0};
   *value_off = 0;
+  bool repeated;
+  if (const int i = bad_slab_bit(c->k, m, bits, &repeated); i >= 0)
+    return repeated ? fail(QSIM_ERR_INVALID, "slab: repeated bit %d", bits[i]) : fail(QSIM_ERR_INVALID, "slab: bit %d out of range", bits[i]);
   for (int i = 0; i < m; ++i) {
-    if (bits[i] < 0 || bits[i] >= c->k) return fail(QSIM_ERR_INVALID, "slab: bit %d out of range", bits[i]);
-    for (int j = 0; j < i; ++j)
-      if (bits[j] == bits[i]) return fail(QSIM_ERR_INVALID, "slab: repeated bit %d", bits[i]);
     sorted[i] = bits[i];
     if ((pattern >> i) & 1) *value_off |= 1ull << bits[i];
   }
@@ -180,22 +199,21 @@ int qsim_swap_global_local(qsim_chunk* const* chunks, int n_chunks, const int32_
   return QSIM_OK;
 }
 
-// The slab-storing end of an op list whose tile passes (all but a stashed last one) have been queued: the split form's
-// bookkeeping (the pieces are stored by qsim_apply_ops_io_part), or the pack passes of a list that could not fuse them.
-static int finish_out_side(qsim_chunk* c, const qsim_ops_io* io, FusedIo& fio) {
+// The slab-storing end of an op list whose tile passes (all but a kept last one) have been queued: the out side of the split
+// form (the pieces are stored by qsim_apply_ops_io_part), or the pack passes of a list that could not fuse them.
+static int finish_out_side(qsim_chunk* c, const qsim_ops_io* io, const FusedIo& fio, const CachedPass* kept) {
   int rc = QSIM_OK;
   if (io->dst && io->dst_parts != 0) {
-    // split form: the slabs are stored piece by piece by qsim_apply_ops_io_part -- partial launches of the planned last
-    // pass, or (nothing fusable) qsim_pack_all pieces of the final state, or nothing (stored already)
-    PendingLast* p = c->pending ? c->pending : (c->pending = new PendingLast());
-    const bool stashed = p->mode == PendingLast::kStashed;
-    p->mode = stashed ? PendingLast::kTile : (fio.fused_out ? PendingLast::kDone : PendingLast::kPack);
-    p->m = io->dst_m;
-    for (int i = 0; i < io->dst_m; ++i) p->bits[i] = io->dst_bits[i];
-    p->dst = io->dst; p->dst_own = io->dst_own; p->own_pattern = io->own_pattern;
-    const int min_piece_bits = io->dst_parts < 0 ? kTileLow : 20;        // (negative: tests cut small shards too)
-    const int want = io->dst_parts < 0 ? -io->dst_parts : io->dst_parts;
-    plan_parts(p, c->k, want, p->mode == PendingLast::kTile ? p->a.h : nullptr, p->mode == PendingLast::kTile ? p->T - kTileLow : 0, min_piece_bits);
+    // split form: partial launches of the kept last pass, or (nothing fusable) qsim_pack_all pieces of the final state, or
+    // nothing (stored already)
+    SplitIo::Out& o = split_record(c)->out;
+    o = SplitIo::Out();
+    o.mode = kept ? SplitIo::Out::kTile : (fio.fused_out ? SplitIo::Out::kDone : SplitIo::Out::kPack);
+    o.m = io->dst_m;
+    for (int i = 0; i < io->dst_m; ++i) o.bits[i] = io->dst_bits[i];
+    o.dst = io->dst; o.dst_own = io->dst_own; o.own_pattern = io->own_pattern;
+    o.cut = PieceCut::cut(c->k, io->dst_m, io->dst_bits, io->dst_parts);
+    if (kept) { o.pass = *kept; o.cut.free_above(kept->a.h, kept->T - kTileLow); }
   } else if (io->dst && !fio.fused_out) {     // not fused: pack passes
     if ((rc = slabs_all(c, io->dst_m, io->dst_bits, io->dst, io->own_pattern, 0, 1, true, "qsim_apply_ops_io"))) return rc;
     if (io->own_pattern >= 0) {
@@ -206,56 +224,14 @@ static int finish_out_side(qsim_chunk* c, const qsim_ops_io* io, FusedIo& fio) {
   return QSIM_OK;
 }
 
-// qsim_ops_io::src_parts: plan now, launch as the source pieces are announced (qsim_apply_ops_io_load)
-static int apply_ops_io_deferred(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
-                                 const qsim_ops_io* io, const FusedIo& fio_in, const std::vector<FusedOp>& ops, bool tiles, int* n_passes) {
-  DeferredIo* d = c->deferred ? c->deferred : (c->deferred = new DeferredIo());
-  *d = DeferredIo();
-  d->tiles = tiles;
-  d->n_ops = n_ops;
-  d->io = *io;
-  d->fio = fio_in;
-  const int want = io->src_parts < 0 ? -io->src_parts : io->src_parts;
-  d->nb = piece_bits_for(c->k, io->src_m, want, io->src_parts < 0 ? kTileLow : 20);
-  top_free_bits(c->k, io->src_m, io->src_bits, d->nb, d->piece_bit);
-  int passes = 0, rc = QSIM_OK;
-  if (io->src && !d->fio.src) ++passes;                     // the source cannot be read by a tile pass: unpack pieces
-  if (tiles) {
-    int p = 0;
-    const TileHint hint = {io->tile_masks, io->n_tiles};
-    if ((rc = run_fused(c, ops, &p, &d->fio, n_ops, nq, qubits, mats, &d->passes, io->n_tiles ? &hint : nullptr))) return rc;
-    d->io.tile_masks = nullptr;                               // (the caller's array: used by the plan above only)
-    d->io.n_tiles = 0;
-    passes += p;
-    c->own_in_chunk = d->fio.own_in_chunk;
-    if (d->fio.src && !d->fio.fused_in) return fail(QSIM_ERR_INVALID, "internal: the first pass did not take the source buffer");
-    // the first pass in partial launches: when it reads the source itself, is not also the slab-storing pass of a split
-    // / fused destination, and the top piece bits are no tile bits of it
-    const bool first_stores = d->passes.size() == 1 && io->dst != nullptr;
-    if (d->fio.src && !first_stores && !d->passes.empty() && d->passes[0].T == kTileBitsMax) {
-      auto is_tile = [&](int b) { for (int j = 0; j < kTileBitsMax - kTileLow; ++j) if (d->passes[0].a.h[j] == b) return true; return false; };
-      while (d->nb_free < d->nb && !is_tile(d->piece_bit[d->nb - 1 - d->nb_free])) ++d->nb_free;    // from the top
-    }
-  } else {
-    d->nq.assign(nq, nq + n_ops);
-    d->qubits.assign(qubits, qubits + 2 * (size_t)n_ops);
-    d->mats.assign(mats, mats + 32 * (size_t)n_ops);
-    passes += n_ops;
-  }
-  if (io->dst && !d->fio.fused_out) ++passes;
-  d->active = true;
-  c->last_passes = passes;
-  if (n_passes) *n_passes = passes;
-  return QSIM_OK;
-}
-
 // Op list with a re-layout fused into its ends (staging.py:136-152 SWAP lists): the FIRST fused pass reads
 // the state from io->src in the slab layout of qsim_pack_all over io->src_bits (what an all-to-all left in the receive
 // buffer) instead of a separate unpack pass, the LAST one stores it into io->dst in the slab layout over io->dst_bits
 // (slab io->own_pattern, which stays on this rank, into io->dst_own) instead of a separate pack pass.  Whatever cannot
 // be fused (bits inside a 128-B line, chunks too small for tile passes, an empty op list, a slab bit that is a tile
 // bit of the last pass) is done with the slab kernels, so the result is the same in every case; *n_passes counts the
-// HBM passes really made.
+// HBM passes really made.  io->src_parts: the same steps, but the prepared passes are held, not launched, until the source
+// pieces are announced (qsim_apply_ops_io_load).
 int qsim_apply_ops_io(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, const qsim_ops_io* io, int* n_passes) {
   int rc = validate_ops(c, n_ops, nq, qubits, mats);
   if (rc) return rc;
@@ -270,10 +246,10 @@ int qsim_apply_ops_io(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t
     if (b->k != c->k || b->device != c->device || b->amp == c->amp)
       return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io: the %s buffer must be a distinct chunk of the state's size and device", side);
     if (m < 1 || m > 3 || m > c->k) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io: %s: 1..3 slab bits expected, got %d", side, m);
-    for (int i = 0; i < m; ++i) {
-      if (bits[i] < 0 || bits[i] >= c->k) return fail(QSIM_ERR_NONLOCAL, "qsim_apply_ops_io: %s slab bit %d is non-local for 2^%d amplitudes", side, bits[i], c->k);
-      for (int j = 0; j < i; ++j) if (bits[j] == bits[i]) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io: %s: repeated slab bit %d", side, bits[i]);
-    }
+    bool repeated;
+    if (const int i = bad_slab_bit(c->k, m, bits, &repeated); i >= 0)
+      return repeated ? fail(QSIM_ERR_INVALID, "qsim_apply_ops_io: %s: repeated slab bit %d", side, bits[i])
+                      : fail(QSIM_ERR_NONLOCAL, "qsim_apply_ops_io: %s slab bit %d is non-local for 2^%d amplitudes", side, bits[i], c->k);
     return QSIM_OK;
   };
   if (io->src && (rc = check_side(io->src, io->src_m, io->src_bits, "source"))) return rc;
@@ -305,30 +281,58 @@ int qsim_apply_ops_io(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t
     fio.out.m = io->dst_m;
     for (int i = 0; i < io->dst_m; ++i) fio.out.bits[i] = io->dst_bits[i];
   }
-  const bool parts = io->dst && io->dst_parts != 0;
   c->own_in_chunk = false;
   if (parts_pending(c))
     return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io: pieces of an earlier split call are pending on this chunk (qsim_apply_ops_io_part / _load)");
-  fio.parts = parts;
-  if (io->src && io->src_parts != 0) return apply_ops_io_deferred(c, n_ops, nq, qubits, mats, io, fio, ops, tiles, n_passes);
+  fio.parts = io->dst && io->dst_parts != 0;
+  const bool defer = io->src && io->src_parts != 0;     // plan now, launch as the source pieces are announced
+  std::vector<CachedPass> held;                         // prepared, not launched: every pass (defer), or the last one (kept for _part)
   int passes = 0;
-  if (io->src && !fio.src) {           // not fusable: one unpack pass brings the state into the chunk
-    if ((rc = slabs_all(c, io->src_m, io->src_bits, const_cast<qsim_chunk*>(io->src), -1, 0, 1, false, "qsim_apply_ops_io"))) return rc;
+  if (io->src && !fio.src) {           // not fusable: one unpack pass brings the state into the chunk (defer: piece by piece)
+    if (!defer && (rc = slabs_all(c, io->src_m, io->src_bits, const_cast<qsim_chunk*>(io->src), -1, 0, 1, false, "qsim_apply_ops_io"))) return rc;
     ++passes;
   }
   if (tiles) {
     int p = 0;
     const TileHint hint = {io->tile_masks, io->n_tiles};
-    if ((rc = run_fused(c, ops, &p, &fio, n_ops, nq, qubits, mats, nullptr, io->n_tiles ? &hint : nullptr))) return rc;
+    rc = run_fused(c, ops, RawOps{n_ops, nq, qubits, mats}, io->n_tiles ? &hint : nullptr, &fio, &p,
+                   [&](TileArgs& a, int T, double alg_bytes, bool last) {
+                     if (!defer && !stays_for_parts(fio, T, last)) return dispatch_planned(c, a, T, alg_bytes);
+                     held.push_back(CachedPass{a, T, alg_bytes});
+                     return (int)QSIM_OK;
+                   });
+    if (rc) return rc;
     passes += p;
     c->own_in_chunk = fio.own_in_chunk;
     if (fio.src && !fio.fused_in) return fail(QSIM_ERR_INVALID, "internal: the first pass did not take the source buffer");
   } else {
-    if ((rc = qsim_apply_ops_unfused(c, n_ops, nq, qubits, mats))) return rc;
+    if (!defer && (rc = qsim_apply_ops_unfused(c, n_ops, nq, qubits, mats))) return rc;
     passes += n_ops;
   }
   if (io->dst && !fio.fused_out) ++passes;                 // a pack pass (whole, or piece by piece)
-  if ((rc = finish_out_side(c, io, fio))) return rc;
+  if (defer) {
+    SplitIo::In& in = split_record(c)->in;
+    in = SplitIo::In();
+    in.tiles = tiles;
+    in.io = *io;
+    in.io.tile_masks = nullptr;                             // (the caller's array: used by the plan above only)
+    in.io.n_tiles = 0;
+    in.fio = fio;
+    in.cut = PieceCut::cut(c->k, io->src_m, io->src_bits, io->src_parts);
+    // the first pass in partial launches: when it reads the source itself, is not also the slab-storing pass of a split
+    // / fused destination, and the top piece bits are no tile bits of it
+    const bool first_stores = held.size() == 1 && io->dst != nullptr;
+    if (fio.src && !first_stores && !held.empty() && held[0].T == kTileBitsMax) in.cut.free_above(held[0].a.h, kTileBitsMax - kTileLow);
+    in.passes.swap(held);
+    if (!tiles) {                                           // gate by gate, once the source is complete
+      in.nq.assign(nq, nq + n_ops);
+      in.qubits.assign(qubits, qubits + 2 * (size_t)n_ops);
+      in.mats.assign(mats, mats + 32 * (size_t)n_ops);
+    }
+    in.active = true;
+  } else if ((rc = finish_out_side(c, io, fio, held.empty() ? nullptr : &held[0]))) {
+    return rc;
+  }
   c->last_passes = passes;
   if (n_passes) *n_passes = passes;
   return QSIM_OK;
@@ -338,31 +342,25 @@ int qsim_apply_ops_io(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t
 int qsim_apply_ops_io_part(qsim_chunk* c, int part) {
   int rc = check_chunk(c, "qsim_apply_ops_io_part");
   if (rc) return rc;
-  PendingLast* p = c->pending;
-  if (!p || p->mode == PendingLast::kNone) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_part: no split op list is pending on this chunk");
-  const int n_parts = 1 << p->nb;
+  if (!c->split || c->split->out.mode == SplitIo::Out::kNone) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_part: no split op list is pending on this chunk");
+  SplitIo::Out& o = c->split->out;
+  const int n_parts = o.cut.n_parts();
   if (part < 0 || part >= n_parts) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_part: piece %d out of range", part);
-  if ((p->stored >> part) & 1) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_part: piece %d has been stored already", part);
+  if ((o.stored >> part) & 1) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_part: piece %d has been stored already", part);
   HIP_TRY(hipSetDevice(c->device));
-  if (p->mode == PendingLast::kTile) {
-    // the partial launch that holds this piece: the top nb_free piece bits select it, it stores 2^(nb - nb_free) pieces
-    const int g = part >> (p->nb - p->nb_free);
-    if (!((p->launched >> g) & 1)) {
-      TileArgs a;
-      if ((rc = partial_launch_args(p->a, p->T, c->k, p->piece_bit + (p->nb - p->nb_free), p->nb_free, g, &a))) return rc;
-      if ((rc = launch_tile_any(a, p->T, c, c->stream, p->alg_bytes / (double)(1 << p->nb_free)))) return rc;
-      p->launched |= 1u << g;
-    }
-  } else if (p->mode == PendingLast::kPack) {
+  if (o.mode == SplitIo::Out::kTile) {
+    // the partial launch that holds this piece: it stores 2^(nb - nb_free) pieces
+    if ((rc = launch_group(c, o.pass, o.cut, o.cut.group_of(part)))) return rc;
+  } else if (o.mode == SplitIo::Out::kPack) {
     // (the pieces of qsim_pack_all are the values of the top non-slab index bits: the same cut)
-    if ((rc = slabs_all(c, p->m, p->bits, p->dst, p->own_pattern, part, n_parts, true, "qsim_apply_ops_io_part"))) return rc;
-    if (p->own_pattern >= 0 && p->stored == 0) {            // the own slab goes to the receive buffer whole, with the first piece
-      const uint64_t slab = 1ull << (c->k - p->m);
-      if ((rc = qsim_pack_bits(c, p->m, p->bits, p->own_pattern, p->dst_own, (uint64_t)p->own_pattern * slab))) return rc;
+    if ((rc = slabs_all(c, o.m, o.bits, o.dst, o.own_pattern, part, n_parts, true, "qsim_apply_ops_io_part"))) return rc;
+    if (o.own_pattern >= 0 && o.stored == 0) {              // the own slab goes to the receive buffer whole, with the first piece
+      const uint64_t slab = 1ull << (c->k - o.m);
+      if ((rc = qsim_pack_bits(c, o.m, o.bits, o.own_pattern, o.dst_own, (uint64_t)o.own_pattern * slab))) return rc;
     }
   }
-  p->stored |= 1u << part;
-  if (p->stored == (1u << n_parts) - 1u) p->mode = PendingLast::kNone;
+  o.stored |= 1u << part;
+  if (o.stored == (1u << n_parts) - 1u) o.mode = SplitIo::Out::kNone;
   return QSIM_OK;
 }
 
@@ -372,42 +370,37 @@ int qsim_apply_ops_io_part(qsim_chunk* c, int part) {
 int qsim_apply_ops_io_load(qsim_chunk* c, int part) {
   int rc = check_chunk(c, "qsim_apply_ops_io_load");
   if (rc) return rc;
-  DeferredIo* d = c->deferred;
-  if (!d || !d->active) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_load: no op list with a split source is pending on this chunk");
-  const int n_parts = 1 << d->nb;
+  if (!c->split || !c->split->in.active) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_load: no op list with a split source is pending on this chunk");
+  SplitIo::In& in = c->split->in;
+  const int n_parts = in.cut.n_parts();
   if (part < 0 || part >= n_parts) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_load: piece %d out of range", part);
-  if ((d->announced >> part) & 1) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_load: piece %d has been announced already", part);
+  if ((in.announced >> part) & 1) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_load: piece %d has been announced already", part);
   HIP_TRY(hipSetDevice(c->device));
   PendingGuard guard{c, true};        // an error leaves nothing pending
-  d->announced |= 1u << part;
-  const qsim_ops_io* io = &d->io;
-  if (!d->fio.src) {                  // unpack mode: this piece goes home now
+  in.announced |= 1u << part;
+  const qsim_ops_io* io = &in.io;
+  if (!in.fio.src) {                  // unpack mode: this piece goes home now
     if ((rc = slabs_all(c, io->src_m, io->src_bits, const_cast<qsim_chunk*>(io->src), -1, part, n_parts, false, "qsim_apply_ops_io_load"))) return rc;
-  } else if (d->nb_free > 0) {        // partial launches of the first pass: group g = the top nb_free bits of the piece number
-    const int shift = d->nb - d->nb_free;
-    const int g = part >> shift;
+  } else if (in.cut.nb_free > 0) {    // partial launches of the first pass: a group runs once all its pieces are there
+    const int shift = in.cut.nb - in.cut.nb_free, g = in.cut.group_of(part);
     const unsigned group = ((1u << (1 << shift)) - 1u) << (g << shift);
-    if ((d->announced & group) == group && !((d->launched >> g) & 1)) {
-      CachedPass& p0 = d->passes[0];
-      TileArgs a;
-      if ((rc = partial_launch_args(p0.a, p0.T, c->k, d->piece_bit + shift, d->nb_free, g, &a))) return rc;
-      if ((rc = launch_tile_any(a, p0.T, c, c->stream, p0.alg_bytes / (double)(1 << d->nb_free)))) return rc;
-      d->launched |= 1u << g;
-    }
+    if ((in.announced & group) == group && (rc = launch_group(c, in.passes[0], in.cut, g))) return rc;
   }
-  if (d->announced != (n_parts >= 32 ? ~0u : (1u << n_parts) - 1u)) { guard.armed = false; return QSIM_OK; }
+  if (in.announced != (1u << n_parts) - 1u) { guard.armed = false; return QSIM_OK; }
   // the source is complete: the rest of the op list
-  d->active = false;
-  if (d->tiles) {
-    for (size_t i = 0; i < d->passes.size(); ++i) {
-      if (i == 0 && d->nb_free > 0) continue;               // ran in partial launches
-      CachedPass& p = d->passes[i];
-      if ((rc = dispatch_planned(c, p.a, p.T, p.alg_bytes, i + 1 == d->passes.size(), &d->fio))) return rc;
+  in.active = false;
+  const CachedPass* kept = nullptr;
+  if (in.tiles) {
+    for (size_t i = 0; i < in.passes.size(); ++i) {
+      if (i == 0 && in.cut.nb_free > 0) continue;           // ran in partial launches
+      CachedPass& p = in.passes[i];
+      if (stays_for_parts(in.fio, p.T, i + 1 == in.passes.size())) kept = &p;
+      else if ((rc = dispatch_planned(c, p.a, p.T, p.alg_bytes))) return rc;
     }
   } else {
-    if ((rc = qsim_apply_ops_unfused(c, d->n_ops, d->nq.data(), d->qubits.data(), d->mats.data()))) return rc;
+    if ((rc = qsim_apply_ops_unfused(c, (int)in.nq.size(), in.nq.data(), in.qubits.data(), in.mats.data()))) return rc;
   }
-  if ((rc = finish_out_side(c, io, d->fio))) return rc;
+  if ((rc = finish_out_side(c, io, in.fio, kept))) return rc;
   guard.armed = false;
   return QSIM_OK;
 }
@@ -420,25 +413,28 @@ int qsim_apply_ops_io_own_slab(const qsim_chunk* c, int32_t* in_chunk) {
   return QSIM_OK;
 }
 
+// The pieces of one side of the pending split op list (m slab bits) and the launches its pass takes.
+static int report_pieces(const qsim_chunk* c, const PieceCut& cut, int m, int launches, int32_t* n_parts, uint64_t* piece_amps, int32_t* n_launches) {
+  if (n_parts) *n_parts = cut.n_parts();
+  if (piece_amps) *piece_amps = cut.piece_amps(c->k, m);
+  if (n_launches) *n_launches = launches;
+  return QSIM_OK;
+}
+
 // Source pieces of the pending op list (qsim_ops_io::src_parts): how many, their size, and how many partial launches the
 // first pass takes (0: it runs whole after the last piece).
 int qsim_apply_ops_io_source_parts(const qsim_chunk* c, int32_t* n_parts, uint64_t* piece_amps, int32_t* n_launches) {
-  if (!c || !c->deferred || !c->deferred->active) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_source_parts: nothing pending on this chunk");
-  const DeferredIo* d = c->deferred;
-  if (n_parts) *n_parts = 1 << d->nb;
-  if (piece_amps) *piece_amps = (1ull << (c->k - d->io.src_m)) >> d->nb;
-  if (n_launches) *n_launches = d->nb_free > 0 ? (1 << d->nb_free) : 0;
-  return QSIM_OK;
+  if (!c || !c->split || !c->split->in.active) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_source_parts: nothing pending on this chunk");
+  const SplitIo::In& in = c->split->in;
+  return report_pieces(c, in.cut, in.io.src_m, in.cut.nb_free > 0 ? (1 << in.cut.nb_free) : 0, n_parts, piece_amps, n_launches);
 }
 
 // The pieces of the pending split op list: piece j of EVERY slab d is [d * 2^(k - m) + j * piece_amps, + piece_amps) of the
 // send / receive buffers.  n_parts depends only on (k, m, dst_parts): the same on every rank.
 int qsim_apply_ops_io_parts(const qsim_chunk* c, int32_t* n_parts, uint64_t* piece_amps, int32_t* n_launches) {
-  if (!c || !c->pending || c->pending->mode == PendingLast::kNone) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_parts: no split op list is pending on this chunk");
-  const PendingLast* p = c->pending;
-  if (n_parts) *n_parts = 1 << p->nb;
-  if (piece_amps) *piece_amps = (1ull << (c->k - p->m)) >> p->nb;
-  if (n_launches) *n_launches = p->mode == PendingLast::kTile ? (1 << p->nb_free) : (p->mode == PendingLast::kPack ? (1 << p->nb) : 0);
-  return QSIM_OK;
+  if (!c || !c->split || c->split->out.mode == SplitIo::Out::kNone) return fail(QSIM_ERR_INVALID, "qsim_apply_ops_io_parts: no split op list is pending on this chunk");
+  const SplitIo::Out& o = c->split->out;
+  const int launches = o.mode == SplitIo::Out::kTile ? (1 << o.cut.nb_free) : (o.mode == SplitIo::Out::kPack ? o.cut.n_parts() : 0);
+  return report_pieces(c, o.cut, o.m, launches, n_parts, piece_amps, n_launches);
 }
 }  // extern "C"

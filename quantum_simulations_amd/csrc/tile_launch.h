@@ -182,61 +182,8 @@ struct FusedIo {
   bool own_in_chunk = false;         // result: the own slab went into the chunk itself (dst_own == src and ONE pass does it all)
 };
 
-// The slab-storing pass of an op list whose caller asked for the split form (qsim_ops_io::dst_parts): planned, not yet
-// launched.  The slabs are stored PIECE by piece: piece j = the j-th of 2^nb equal contiguous sub-ranges of EVERY slab
-// (the top nb index bits that are not slab bits have the value j), so the exchange of piece j uses all links at once
-// while the pieces behind it are still being computed.  The cut depends ONLY on (k, m, pieces asked for): every rank of a
-// multi-GPU run cuts alike whatever its own pass plan looks like (ranks plan different op lists: rank-bit phases,
-// controlled gates with a global control) -- the k-th transfer between two ranks always has the same size on both sides.
-// What a rank's plan decides is only how early its pieces are ready: kTile -- the top `nb_free` <= nb piece bits are not
-// tile bits of the pass, which then runs as 2^nb_free partial launches (a launch stores 2^(nb - nb_free) pieces at once;
-// nb_free = 0: one launch, everything ready with the first piece); kPack (nothing fusable: the state is final in the
-// chunk): one qsim_pack_all piece per call; kDone: stored already (passes that cannot be launched in part).
-struct PendingLast {
-  enum Mode { kNone = 0, kStashed, kTile, kPack, kDone };   // kStashed: launch_planned has put the pass here, the caller's slab description is still missing
-  int mode = kNone;
-  TileArgs a;
-  int T = 0;
-  double alg_bytes = 0;
-  int m = 0;
-  int32_t bits[3] = {0, 0, 0};
-  qsim_chunk* dst = nullptr;
-  qsim_chunk* dst_own = nullptr;
-  int own_pattern = -1;
-  int nb = 0;                        // piece bits: 2^nb pieces
-  int piece_bit[3] = {0, 0, 0};      // the top nb non-slab index bits, ascending (piece j: bit i of j <-> piece_bit[i])
-  int nb_free = 0;                   // kTile: how many of them, from the top, are no tile bits of the pass
-  unsigned stored = 0;               // bit j: piece j has been handed out
-  unsigned launched = 0;             // kTile: bit g: partial launch g (the top nb_free bits of the piece number) is queued
-};
-
-// 2^nb pieces for a request of `want` (1, 2, 4, 8): as many as asked for while a piece keeps >= 2^min_piece_bits amplitudes.
-static int piece_bits_for(int k, int m, int want, int min_piece_bits) {
-  int nb = 0;
-  while (nb < 3 && (2 << nb) <= want && (k - m) - (nb + 1) >= min_piece_bits && (k - m) - (nb + 1) >= kTileLow) ++nb;
-  return nb;
-}
-
-// The top nb index bits of a k-bit index that are none of the m slab bits, ascending (the piece bits of the split form).
-static void top_free_bits(int k, int m, const int32_t* slab_bits, int nb, int* out) {
-  for (int b = k - 1, found = 0; b >= 0 && found < nb; --b) {
-    bool slab = false;
-    for (int i = 0; i < m; ++i) slab = slab || slab_bits[i] == b;
-    if (!slab) out[nb - 1 - found++] = b;
-  }
-}
-
-static void plan_parts(PendingLast* p, int k, int want, const uint8_t* tile_high, int n_tile_high, int min_piece_bits) {
-  auto is_tile = [&](int b) { for (int j = 0; j < n_tile_high; ++j) if (tile_high[j] == b) return true; return false; };
-  p->nb = piece_bits_for(k, p->m, want, min_piece_bits);
-  top_free_bits(k, p->m, p->bits, p->nb, p->piece_bit);
-  p->nb_free = 0;
-  while (p->nb_free < p->nb && !is_tile(p->piece_bit[p->nb - 1 - p->nb_free])) ++p->nb_free;    // from the top
-  p->stored = p->launched = 0;
-}
-
 // One planned pass on its way to the device: buffers and the re-layout of the op list's ends (prepare_planned), then the
-// launch -- or, for the slab-storing pass of a split call, the stash (dispatch_planned).
+// launch (dispatch_planned) -- or, for the slab-storing pass of a split call, nothing yet (stays_for_parts).
 static void prepare_planned(qsim_chunk* c, TileArgs& a, int T, bool first, bool last, FusedIo* io) {
   a.amp = c->amp;
   a.amp_out = c->amp;
@@ -278,12 +225,13 @@ static void prepare_planned(qsim_chunk* c, TileArgs& a, int T, bool first, bool 
   }
 }
 
-static int dispatch_planned(qsim_chunk* c, TileArgs& a, int T, double alg_bytes, bool last, FusedIo* io) {
-  if (io && last && io->dst && io->parts && io->fused_out && T == kTileBitsMax) {
-    PendingLast* p = c->pending ? c->pending : (c->pending = new PendingLast());
-    p->mode = PendingLast::kStashed; p->a = a; p->T = T; p->alg_bytes = alg_bytes; p->launched = 0;
-    return QSIM_OK;                  // (qsim_apply_ops_io fills in the slab description and keeps it pending)
-  }
+// The slab-storing pass of a split call (FusedIo::parts) is not launched with the others: qsim_apply_ops_io_part launches
+// it piece by piece (full tiles only: the PART instantiations of k_tile).
+static bool stays_for_parts(const FusedIo& io, int T, bool last) {
+  return last && io.dst && io.parts && io.fused_out && T == kTileBitsMax;
+}
+
+static int dispatch_planned(qsim_chunk* c, TileArgs& a, int T, double alg_bytes) {
   if (tuning().debug_stats < 2) return launch_tile_any(a, T, c, c->stream, alg_bytes);
   // QSIM_DEBUG_STATS=2: time every pass synchronously and print its shape (profiling aid)
   hipEvent_t e0, e1;
@@ -301,18 +249,13 @@ static int dispatch_planned(qsim_chunk* c, TileArgs& a, int T, double alg_bytes,
   return rc;
 }
 
-static int launch_planned(qsim_chunk* c, TileArgs& a, int T, double alg_bytes, bool first, bool last, FusedIo* io) {
-  prepare_planned(c, a, T, first, last, io);
-  return dispatch_planned(c, a, T, alg_bytes, last, io);
-}
-
 // ---- plan cache ---------------------------------------------------------------------------------------------------
 // Runners execute the same op list again and again (a planned circuit repeated, one plan per chunk of a chunked run):
 // the pass images of the last few op lists are kept, keyed by the exact bytes of the call (local qubits, arities,
 // qubits, matrices), and launched again without planning.  Planning overlaps with the device for large states (the
 // images of pass p + 1 are made while pass p runs), so this matters where passes are short: 13 % of a step at 22
 // qubits, nothing at 28.  Images are stored without buffers or layouts: those are put in at
-// launch time (launch_planned), so one entry serves every chunk of its size and every re-layout.
+// launch time (prepare_planned), so one entry serves every chunk of its size and every re-layout.
 struct CachedPass { TileArgs a; int T; double alg_bytes; };
 struct CachedPlan {
   int k = 0;
@@ -325,24 +268,26 @@ constexpr size_t kPlanCacheMaxKeyBytes = 4u << 20;      // longer op lists are p
 static std::list<CachedPlan> g_plan_cache;             // most recently used first
 static std::mutex g_plan_cache_mu;
 
-// `defer` (an op list whose source arrives in pieces, qsim_ops_io::src_parts): the passes are planned and prepared (buffers
-// in) but not launched; the caller launches them when the source is complete.
-static int run_fused(qsim_chunk* c, const std::vector<FusedOp>& ops, int* n_passes, FusedIo* io = nullptr,
-                     int n_ops = 0, const int32_t* nq = nullptr, const int32_t* qubits = nullptr, const double* mats = nullptr,
-                     std::vector<CachedPass>* defer = nullptr, const TileHint* hint = nullptr) {
-  // key of the call (only when the caller handed the raw op list over)
+struct RawOps { int n; const int32_t* nq; const int32_t* qubits; const double* mats; };    // the op list as the caller gave it
+
+// Every pass of the op list, planned (or taken from the cache) and prepared, goes to `sink(a, T, alg_bytes, last)` -- pass
+// p before pass p + 1 is planned, so a sink that launches keeps the device busy while the host plans.
+template <class Sink>
+static int run_fused(qsim_chunk* c, const std::vector<FusedOp>& ops, const RawOps& raw, const TileHint* hint, FusedIo* io,
+                     int* n_passes, Sink&& sink) {
   std::vector<unsigned char> key;
   u64 hash = 0;
+  const size_t n_ops = (size_t)raw.n;
   const size_t hint_bytes = hint ? sizeof(uint64_t) * (size_t)hint->n : 0;
-  const size_t key_bytes = (size_t)n_ops * (sizeof(int32_t) * 3 + sizeof(double) * 32) + hint_bytes;
-  const bool cacheable = nq && qubits && mats && n_ops > 0 && key_bytes <= kPlanCacheMaxKeyBytes && tuning().debug_stats == 0 &&
+  const size_t key_bytes = n_ops * (sizeof(int32_t) * 3 + sizeof(double) * 32) + hint_bytes;
+  const bool cacheable = raw.nq && raw.qubits && raw.mats && raw.n > 0 && key_bytes <= kPlanCacheMaxKeyBytes && tuning().debug_stats == 0 &&
                          tuning().debug_skip_gates == 0;     // (probe passes take their tile bits from the environment at plan time)
   if (cacheable) {
     key.resize(key_bytes);
     unsigned char* w = key.data();
-    std::memcpy(w, nq, sizeof(int32_t) * (size_t)n_ops); w += sizeof(int32_t) * (size_t)n_ops;
-    std::memcpy(w, qubits, sizeof(int32_t) * 2 * (size_t)n_ops); w += sizeof(int32_t) * 2 * (size_t)n_ops;
-    std::memcpy(w, mats, sizeof(double) * 32 * (size_t)n_ops); w += sizeof(double) * 32 * (size_t)n_ops;
+    std::memcpy(w, raw.nq, sizeof(int32_t) * n_ops); w += sizeof(int32_t) * n_ops;
+    std::memcpy(w, raw.qubits, sizeof(int32_t) * 2 * n_ops); w += sizeof(int32_t) * 2 * n_ops;
+    std::memcpy(w, raw.mats, sizeof(double) * 32 * n_ops); w += sizeof(double) * 32 * n_ops;
     if (hint_bytes) std::memcpy(w, hint->masks, hint_bytes);
     hash = fnv1a(key.data(), key.size(), 1469598103934665603ull ^ (u64)c->k);
     std::vector<CachedPass> hit;
@@ -357,12 +302,9 @@ static int run_fused(qsim_chunk* c, const std::vector<FusedOp>& ops, int* n_pass
     }
     if (!hit.empty()) {
       for (size_t p = 0; p < hit.size(); ++p) {
-        if (defer) {
-          prepare_planned(c, hit[p].a, hit[p].T, p == 0, p + 1 == hit.size(), io);
-          defer->push_back(hit[p]);
-          continue;
-        }
-        const int rc = launch_planned(c, hit[p].a, hit[p].T, hit[p].alg_bytes, p == 0, p + 1 == hit.size(), io);
+        const bool last = p + 1 == hit.size();
+        prepare_planned(c, hit[p].a, hit[p].T, p == 0, last, io);
+        const int rc = sink(hit[p].a, hit[p].T, hit[p].alg_bytes, last);
         if (rc) return rc;
       }
       *n_passes = (int)hit.size();
@@ -372,12 +314,8 @@ static int run_fused(qsim_chunk* c, const std::vector<FusedOp>& ops, int* n_pass
   std::vector<CachedPass> made;
   const int rc = plan_fused(c->k, ops, n_passes, [&](TileArgs& a, int T, double alg_bytes, bool first, bool last) {
     if (cacheable) made.push_back(CachedPass{a, T, alg_bytes});      // (before buffers and layouts go in)
-    if (defer) {
-      prepare_planned(c, a, T, first, last, io);
-      defer->push_back(CachedPass{a, T, alg_bytes});
-      return (int)QSIM_OK;
-    }
-    return launch_planned(c, a, T, alg_bytes, first, last, io);
+    prepare_planned(c, a, T, first, last, io);
+    return sink(a, T, alg_bytes, last);
   }, hint);
   if (rc == QSIM_OK && cacheable && !made.empty()) {
     std::lock_guard<std::mutex> lock(g_plan_cache_mu);

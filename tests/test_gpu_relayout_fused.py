@@ -371,3 +371,203 @@ def test_split_source_consumes_the_pieces_as_they_arrive(k):
         assert 4 in launches_seen and 0 in launches_seen, launches_seen
     for c in (state, src, dst, keep):
         c.close()
+
+
+# ---- the one record of a split call (csrc/abi_pending.h SplitIo): k = 14 with four pieces asked for is the smallest size at
+# which a full 11-bit tile pass has piece bits above it, so partial launches really happen
+_K = 14
+_BITS_IN, _BITS_OUT = [5, 9], [4, 10]                         # slab bits >= 3: both ends fuse; top non-slab qubits: 13, 12
+
+
+def _split_lists(seed):
+    """(ops, first, last): a list that leaves the top two non-slab qubits (13, 12) alone -- they are no tile bits of any
+    pass, which then runs as 4 partial launches -- and the same with an H on each of them in front (`first`) or behind
+    (`last`), which makes them tile bits of that pass: it runs whole."""
+    free = [(qs, U) for qs, U in _random_ops(_K, 40, seed) if not set(qs) & {12, 13}]
+    hs = [([q], orc.gate_matrix("H")) for q in (13, 12)]
+    return free, hs + free, free + hs
+
+
+def _split_call(state, src, dst, keep, ops, psi0, mode, split, rng=None, refuse=False, own=-1):
+    """One qsim_apply_ops_io call in `mode` ("dst", "src", "both") from psi0, whole or split; `refuse`: the repeated and the
+    out-of-range pieces are tried first.  Returns (the buffers that hold the result, launches of the split sides, launches
+    and algorithmic bytes of k_tile in the launch profile of the call and its pieces).  `own`
+    >= 0: that slab goes to `keep` (its bits are tile bits of these lists' passes, so the slabs are then packed, not fused)."""
+    with_src, with_dst = mode != "dst", mode != "src"
+    if with_src:
+        src.upload(np.concatenate(_slabs(psi0, _BITS_IN)))
+        state.init_zero(False)
+    else:
+        state.upload(psi0)
+    dst.init_zero(False)
+    keep.init_zero(False)
+    state.profile_begin()
+    state.apply_ops_io(ops, src=(src, _BITS_IN) if with_src else None, dst=(dst, _BITS_OUT, keep, own) if with_dst else None,
+                       parts=-4 if split and with_dst else 0, src_parts=-4 if split and with_src else 0)
+    launches = []
+    if split:
+        sides = ([(state.load_part, "announced already", lambda: state.source_parts()[0], lambda: state.source_parts()[2])] if with_src else []) + \
+                ([(state.store_part, "stored already", lambda: len(state.pending_parts()), lambda: state.last_split_launches)] if with_dst else [])
+        for hand, repeated, count, n_launches in sides:
+            n_parts = count()
+            assert n_parts == 4
+            launches.append(n_launches())
+            rest = list(range(n_parts))
+            if refuse:
+                hand(0)
+                with pytest.raises(ValueError, match=repeated):
+                    hand(0)
+                for bad in (n_parts, -1):
+                    with pytest.raises(ValueError, match="out of range"):
+                        hand(bad)
+                rest = rest[1:]
+                assert count() == n_parts                   # the other pieces are still pending
+            for j in rng.permutation(rest):
+                hand(int(j))
+    tile = [(e["launches"], e["algorithmic_bytes"]) for e in state.profile_end() if e["kernel"].startswith("k_tile")]
+    return ([dst.download(), keep.download()] if with_dst else [state.download()]), launches, tile
+
+
+def _check_against_oracle(got, psi0, ops, with_dst, what, own=-1):
+    want = psi0.copy()
+    orc.apply_ops(want, ops)
+    if not with_dst:
+        np.testing.assert_allclose(got[0], want, rtol=0, atol=1e-11, err_msg=what)
+        return
+    slab = len(want) >> len(_BITS_OUT)
+    for d, w in enumerate(_slabs(want, _BITS_OUT)):
+        np.testing.assert_allclose(got[1 if d == own else 0][d * slab:(d + 1) * slab], w, rtol=0, atol=1e-11, err_msg=f"{what} slab {d}")
+
+
+@pytest.mark.parametrize("mode", ["dst", "src", "both"])
+def test_a_refused_piece_leaves_the_rest_pending(mode):
+    """A piece handed over twice, a piece n_parts and a piece -1 are refused by qsim_apply_ops_io_part / _load and change
+    nothing: the other pieces then go through in any order, the buffers equal the one-launch form of the same call bit
+    for bit, and the launch profile shows every partial launch queued once.  Destination split, source split, both at once; a pass in 4 partial launches and a pass that runs whole."""
+    from quantum_simulations_amd.kernel.device import DeviceChunk
+    rng = np.random.default_rng(1400 + len(mode))
+    state, src, dst, keep = (DeviceChunk.empty(_K) for _ in range(4))
+    free, first, last = _split_lists(1401)
+    psi0 = _rand_state(_K, 1402)
+    whole = {"dst": last, "src": first, "both": [first[0]] + free + [last[-1]]}[mode]     # both: H(13) in front, H(12) behind
+    for name, ops in (("free", free), ("whole", whole)):
+        want, _, [(whole_launches, whole_bytes)] = _split_call(state, src, dst, keep, ops, psi0, mode, split=False)
+        got, launches, [(tile_launches, tile_bytes)] = _split_call(state, src, dst, keep, ops, psi0, mode, split=True, rng=rng, refuse=True)
+        print(f"mode {mode} list {name}: launches {launches}, k_tile {whole_launches} -> {tile_launches}")
+        assert launches == [4] * len(launches) if name == "free" else max(launches) < 4, launches
+        # every partial launch is queued once (a pass in L > 1 launches adds L - 1) and accounts for its share of the bytes
+        assert tile_launches == whole_launches + sum(max(n, 1) - 1 for n in launches) and tile_bytes == whole_bytes
+        for g, w in zip(got, want):
+            np.testing.assert_array_equal(g, w, err_msg=f"{mode} {name}")
+        _check_against_oracle(got, psi0, ops, mode != "src", f"{mode} {name}")
+        for hand in (state.store_part, state.load_part):
+            with pytest.raises(ValueError):
+                hand(0)                                     # nothing pending any more
+    for c in (state, src, dst, keep):
+        c.close()
+
+
+def test_init_zero_drops_both_kinds_of_pending_pieces():
+    from quantum_simulations_amd.kernel.device import DeviceChunk
+    state, src, dst, keep = (DeviceChunk.empty(_K) for _ in range(4))
+    ops = _split_lists(1411)[0]
+    want = np.zeros(1 << _K, dtype=np.complex128)
+    want[0] = 1
+    orc.apply_ops(want, ops)
+    src.upload(np.concatenate(_slabs(_rand_state(_K, 1412), _BITS_IN)))
+    for mode in ("dst", "src", "both"):
+        state.apply_ops_io(ops, src=(src, _BITS_IN) if mode != "dst" else None, dst=(dst, _BITS_OUT, None, -1) if mode != "src" else None,
+                           parts=-4 if mode != "src" else 0, src_parts=-4 if mode != "dst" else 0)
+        if mode == "both":
+            state.load_part(2)
+        with pytest.raises(ValueError, match="pending"):
+            state.apply_ops(ops)
+        state.init_zero()
+        assert state.apply_ops(ops) >= 1
+        np.testing.assert_allclose(state.download(), want, rtol=0, atol=1e-11, err_msg=mode)
+        for refused in (lambda: state.store_part(0), state.pending_parts, lambda: state.load_part(0), state.source_parts):
+            with pytest.raises(ValueError):
+                refused()
+    # a chunk is closed with the source pieces of a call pending whose destination is split too, and one with both kinds of
+    # pass kept: the prepared passes of the source side (all announced) and the slab-storing pass
+    state.apply_ops_io(ops, src=(src, _BITS_IN), dst=(dst, _BITS_OUT, None, -1), parts=-4, src_parts=-4)
+    state.load_part(1)
+    state.close()
+    other = DeviceChunk.empty(_K)
+    other.apply_ops_io(ops, src=(src, _BITS_IN), dst=(dst, _BITS_OUT, None, -1), parts=-4, src_parts=-4)
+    for j in range(4):
+        other.load_part(j)
+    assert len(other.pending_parts()) == 4
+    other.store_part(3)
+    other.close()
+    for c in (src, dst, keep):
+        c.close()
+
+
+def test_split_source_from_the_plan_cache():
+    """The same op list twice with src_parts: the second call takes its pass images from the plan cache (run_fused's hit
+    loop feeding the sink that holds the passes).  Source and state are NaN before a piece is announced, as in
+    test_split_source_consumes_the_pieces_as_they_arrive; both calls equal the non-split call bit for bit."""
+    from quantum_simulations_amd import _lib
+    from quantum_simulations_amd.kernel.device import DeviceChunk
+    from quantum_simulations_amd.runner.distributed import split_pieces
+    state, src = DeviceChunk.empty(_K), DeviceChunk.empty(_K)
+    n, m = 1 << _K, len(_BITS_IN)
+    ops = _split_lists(1421)[0]
+    psi0 = _rand_state(_K, 1422)
+    packed = np.concatenate(_slabs(psi0, _BITS_IN))
+    pieces, slab = split_pieces(_K, m, -4), n >> m
+    _lib.check(_lib.load().qsim_plan_cache_clear())           # the first call plans, the second one finds the plan
+    results, reports = [], []
+    for order in ([2, 0, 3, 1], [1, 3, 0, 2]):
+        src.upload(np.full(n, np.nan + 1j * np.nan))
+        state.upload(np.full(n, np.nan + 1j * np.nan))
+        assert state.apply_ops_io(ops, src=(src, _BITS_IN), src_parts=-4) >= 1
+        reports.append(state.source_parts())
+        for j in order:
+            off, cnt = pieces[j]
+            for d in range(1 << m):
+                src.upload(packed[d * slab + off:d * slab + off + cnt], d * slab + off)
+            state.load_part(j)
+            state.sync()
+        results.append(state.download())
+    assert reports[0] == reports[1] == (4, pieces[0][1], 4), reports
+    src.upload(packed)
+    state.init_zero(False)
+    state.apply_ops_io(ops, src=(src, _BITS_IN))
+    want = state.download()
+    for got in results:
+        np.testing.assert_array_equal(got, want)
+    _check_against_oracle(results[:1], psi0, ops, False, "cached split source")
+    for c in (state, src):
+        c.close()
+
+
+def test_split_destinations_of_two_chunks_interleaved():
+    """Two chunks on one stream, each with a split destination pending, their pieces stored alternately: nothing of the
+    record is shared between chunks.  The first stores its slabs in 4 partial launches of its last pass, the second keeps
+    an own slab whose bits are tile bits of that pass: 4 pack pieces, the own slab with the first."""
+    from quantum_simulations_amd.kernel.device import DeviceChunk
+    chunks = [[DeviceChunk.empty(_K) for _ in range(4)] for _ in range(2)]       # state, (unused source), dst, keep
+    lists = [_split_lists(1431)[0], _split_lists(1432)[2]]
+    psis = [_rand_state(_K, 1433), _rand_state(_K, 1434)]
+    owns = [-1, 2]
+    want = [_split_call(*chunks[i], lists[i], psis[i], "dst", split=False, own=owns[i])[0] for i in range(2)]
+    for i in range(2):
+        state, _, dst, keep = chunks[i]
+        state.upload(psis[i])
+        dst.init_zero(False)
+        keep.init_zero(False)
+        state.apply_ops_io(lists[i], dst=(dst, _BITS_OUT, keep if owns[i] >= 0 else None, owns[i]), parts=-4)
+    assert len(chunks[0][0].pending_parts()) == len(chunks[1][0].pending_parts()) == 4
+    assert chunks[0][0].last_split_launches == chunks[1][0].last_split_launches == 4
+    for a, b in zip([3, 0, 2, 1], [1, 2, 0, 3]):
+        chunks[0][0].store_part(a)
+        chunks[1][0].store_part(b)
+    for i in range(2):
+        np.testing.assert_array_equal(chunks[i][2].download(), want[i][0], err_msg=f"chunk {i}")
+        np.testing.assert_array_equal(chunks[i][3].download(), want[i][1], err_msg=f"chunk {i} own slab")
+        _check_against_oracle([chunks[i][2].download(), chunks[i][3].download()], psis[i], lists[i], True, f"chunk {i}", owns[i])
+    for row in chunks:
+        for c in row:
+            c.close()
