@@ -394,6 +394,28 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
  * A bit >= n_local_qubits in x fails with QSIM_ERR_NONLOCAL. */
 int qsim_plan_expectation(int n_local_qubits, int n_terms, const uint64_t* x_masks, int32_t* pass_of_term,
                           uint64_t* tile_masks, int* n_passes);
+/* Pauli rotations, applied in place: psi := R_{n-1} ... R_1 R_0 psi with R_t = exp(-i thetas[t] P_t), in LIST ORDER
+ * (rotations do not commute).  P_t is two masks of physical local index bits as in qsim_expectation_pauli.  The
+ * convention has NO factor 1/2:  R = exp(-i theta P) = cos(theta) I - i sin(theta) P  (the gate RZ(phi) is the rotation
+ * of Z by theta = phi / 2).  With ny = popcount(x & z) and f = -i sin(theta) i^ny:
+ *   x == 0:  psi'_j = (cos(theta) + f (-1)^popcount(j & z)) psi_j
+ *   x != 0:  psi'_j = cos(theta) psi_j + f (-1)^popcount((j ^ x) & z) psi_{j ^ x}
+ * Read-modify-write passes over the chunk, grouped by qsim_plan_pauli_rotations: a tile pass applies up to 1024
+ * consecutive rotations whose x lies in its <= 11 tile bits from LDS (z is free: it need not lie in the tile), a wide
+ * pass one rotation whose x does not fit a tile.  cos, sin and f are computed in double on the host.  The passes are
+ * enqueued on the chunk's stream like the gate calls (no kernel is waited for); n == 0 launches nothing.  *n_passes = the passes made
+ * (= qsim_plan_pauli_rotations').  A bit of x | z >= log2(chunk) fails with QSIM_ERR_NONLOCAL, a theta that is not
+ * finite or a null argument with QSIM_ERR_INVALID; nothing is changed then. */
+int qsim_apply_pauli_rotations(qsim_chunk* c, int n, const uint64_t* x_masks, const uint64_t* z_masks,
+                               const double* thetas, int* n_passes);
+/* The pass plan of qsim_apply_pauli_rotations (pure function, no GPU), ORDER PRESERVING: pass_of[t] = the pass that
+ * applies rotation t, non-decreasing in t; tile_masks[p] = the tile bits of pass p (they contain the line bits 0..2 and
+ * the x of each of its rotations, min(n_local_qubits, 11) bits), 0 for a wide pass.  tile_masks needs room for n
+ * entries.  The list is walked once: a rotation whose x and the line bits exceed the tile width gets a wide pass of its
+ * own and closes the open pass; any other joins the open pass when that holds fewer than 1024 rotations and its tile
+ * stays within the width, else it opens a new pass.  A bit >= n_local_qubits in x fails with QSIM_ERR_NONLOCAL. */
+int qsim_plan_pauli_rotations(int n_local_qubits, int n, const uint64_t* x_masks, int32_t* pass_of,
+                              uint64_t* tile_masks, int* n_passes);
 /* Shot sampling of the full register: n_shots samples of the chunk-local index from |amp|^2 / total.  randnums[s] in
  * [0, 1) is the caller's uniform for shot s (the caller owns the generator); out_indices[s] is the smallest i with
  * cdf(i) > randnums[s] * total in the device's fixed summation order; results come back in the order of randnums.  An

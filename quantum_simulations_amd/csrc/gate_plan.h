@@ -143,8 +143,8 @@ static const char* const kClassNames[] = {
     "k_gate_shuffle<1,1> lane 1q", "k_gate_shuffle<1,2> lane 2q", "k_gate_shuffle<2,1> lane+reg 2q",
     "k_tile fused pass", "k_dense dense k-qubit block", "k_hist outcome probabilities",
     "k_sample_block_sums shot sampling, pass A", "k_sample_resolve shot sampling, pass B",
-    "k_rdm reduced density matrix"};
-constexpr int kNumClasses = 12;
+    "k_rdm reduced density matrix", "k_rot Pauli rotations"};
+constexpr int kNumClasses = 13;
 
 static hipEvent_t prof_event_locked() {
   if (!g_prof_pool.empty()) {

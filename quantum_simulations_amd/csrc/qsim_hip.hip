@@ -57,6 +57,7 @@ typedef unsigned long long u64;
 #include "readout_kernels.h"
 #include "dense_kernels.h"
 #include "expect_kernels.h"
+#include "rot_kernels.h"
 #include "rdm_kernels.h"
 #include "sample_kernels.h"
 #include "comm_rccl.h"
@@ -64,6 +65,7 @@ typedef unsigned long long u64;
 // The C ABI, by topic.  abi_pending.h first: every topic asks whether a split call has left pieces pending on a chunk.
 #include "abi_pending.h"
 #include "abi_readout.h"
+#include "abi_rotation.h"
 #include "abi_chunk.h"
 #include "abi_gates.h"
 #include "abi_plan.h"

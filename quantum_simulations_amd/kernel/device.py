@@ -181,6 +181,21 @@ class DeviceChunk:
         _lib.check(fn(self._h, len(nq), _lib.ptr(nq), _lib.ptr(qs), _lib.ptr(mats)))
         return lib.qsim_last_pass_count(self._h) if fused else len(nq)
 
+    def apply_pauli_rotations(self, x_masks, z_masks, thetas) -> int:
+        """psi := exp(-i thetas[t] P_t) psi for t = 0, 1, ... IN LIST ORDER, in place; P_t as masks of PHYSICAL index bits
+        of this chunk (x: X or Y, z: Z or Y).  No factor 1/2: exp(-i theta P) = cos(theta) I - i sin(theta) P
+        (qsim_apply_pauli_rotations: up to 1024 consecutive rotations per read-modify-write pass, enqueued on the chunk's
+        stream).  Returns the passes made, also kept in `self.last_rotation_passes`."""
+        x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
+        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
+        th = np.ascontiguousarray(thetas, dtype=np.float64).reshape(-1)
+        if not x.shape == z.shape == th.shape:
+            raise ValueError(f"apply_pauli_rotations: {x.size} x masks, {z.size} z masks, {th.size} angles")
+        passes = C.c_int(0)
+        _lib.check(_lib.load().qsim_apply_pauli_rotations(self._h, int(x.size), _lib.ptr(x), _lib.ptr(z), _lib.ptr(th), C.byref(passes)))
+        self.last_rotation_passes = passes.value
+        return passes.value
+
     # ---- sync / reductions / timing -------------------------------------------------
     def apply_ops_io(self, ops, src=None, dst=None, parts: int = 0, src_parts: int = 0, tiles=None) -> int:
         """`apply_ops` with a re-layout fused into its ends (qsim_apply_ops_io): `src` = (chunk, bits): the state

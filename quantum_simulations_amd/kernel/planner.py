@@ -1,6 +1,6 @@
 """The host planner of libqsim_hip.so in Python: what the pass builder would do with an op list, without a device
 (csrc/abi_plan.h: qsim_plan_ops, qsim_plan_ops_tiled, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass,
-qsim_rewrite_ops; csrc/tile_launch.h: qsim_tiles_per_workgroup).
+qsim_rewrite_ops; csrc/tile_launch.h: qsim_tiles_per_workgroup; csrc/abi_rotation.h: qsim_plan_pauli_rotations).
 
 A thin binding.  `ops` is [(qubits, U), ...] or the tuple `pack_ops` returns (`device.as_packed`).  Return codes become
 the exceptions of `_lib.check` and nothing else is read into them: what a caller makes of a list too short to plan is
@@ -129,3 +129,15 @@ def peek_pass(k: int, n: int, nq, qubits, mats, done, members, avoid: int = 0, h
     _lib.check(_lib.load().qsim_plan_peek_pass(k, n, len(nq), ptr(nq), ptr(qubits), ptr(mats), ptr(done), avoid, hint,
                                                C.byref(mask), C.byref(need), C.byref(count), ptr(members)))
     return int(mask.value), int(need.value), [int(i) for i in members[:count.value]]
+
+
+def plan_pauli_rotations(n: int, x_masks) -> tuple:
+    """The pass plan of `DeviceChunk.apply_pauli_rotations` on a chunk of n qubits (qsim_plan_pauli_rotations, device-free):
+    (pass of every rotation, tile-bit mask of every pass; 0 = a wide pass of one rotation).  Order preserving -- rotations
+    exp(-i theta P) do not commute -- so the passes are runs of the list and `pass_of` never decreases."""
+    x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
+    pass_of = np.empty(x.size, dtype=np.int32)
+    tiles = np.empty(max(x.size, 1), dtype=np.uint64)
+    count = C.c_int(0)
+    _lib.check(_lib.load().qsim_plan_pauli_rotations(int(n), int(x.size), ptr(x), ptr(pass_of), ptr(tiles), C.byref(count)))
+    return pass_of, tiles[:count.value].copy()

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from quantum_simulations_amd import readout
+from quantum_simulations_amd import evolution, readout
 from quantum_simulations_amd.circuit.fusion import batch_levels
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.kernel import gates as gate_table, planner
@@ -93,6 +93,23 @@ class SingleGpuEngine:
         """<psi|H|psi> (unnormalised) of a Pauli sum over LOGICAL qubits (observable.PauliSum or what it accepts),
         evaluated on the device through the current layout; the state does not move."""
         return readout.expectation(self.state, self.l2p, obs)
+
+    def apply_pauli_rotations(self, rotations) -> int:
+        """psi := exp(-i theta P) psi for every entry of `rotations`, first entry first, on the device through the
+        current layout (the state does not move).  No factor 1/2 on theta.  `rotations`: the (x, z, theta) arrays of
+        `evolution.trotter_rotations` over LOGICAL qubits, or a list of (pauli, theta) pairs / (x, z, theta) triples
+        (`evolution.rotation`).  Returns the HBM passes made."""
+        passes = evolution.apply_rotations(self.state, self.l2p, rotations)
+        self._zero = False
+        return passes
+
+    def evolve(self, obs, t, steps: int = 1, order: int = 1) -> int:
+        """exp(-i t H) psi by a product formula (`evolution.trotter_rotations`: order 1 or the symmetric order 2,
+        `steps` steps) of the Pauli sum H over LOGICAL qubits, applied on the device through the current layout; the
+        state does not move.  Returns the HBM passes made."""
+        passes = evolution.evolve(self.state, self.l2p, obs, t, steps, order)
+        self._zero = False
+        return passes
 
     def reduced_density_matrix(self, qubits) -> np.ndarray:
         """Reduced density matrix (unnormalised, complex128 (2^r, 2^r)) of 1 to 6 LOGICAL qubits, bit j of a row or

@@ -23,7 +23,7 @@ from pathlib import Path
 
 import numpy as np
 
-from quantum_simulations_amd import readout
+from quantum_simulations_amd import evolution, readout
 from quantum_simulations_amd.circuit.fusion import batch_levels, split_by_locality
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.circuit.staging import atlas_stages, permute_state
@@ -308,6 +308,13 @@ def expectation(buf: HbmStateBuffer, obs) -> float:
     """<psi|H|psi> (unnormalised) of a Pauli sum over LOGICAL qubits on the final state of `run`, evaluated on the
     device through the staging layout `buf.log_to_phys` (nothing is downloaded or permuted)."""
     return readout.expectation(buf.state, getattr(buf, "log_to_phys", None) or None, obs)
+
+
+def evolve(buf: HbmStateBuffer, obs, t, steps: int = 1, order: int = 1) -> int:
+    """exp(-i t H) applied to the final state of `run` by a product formula of Pauli rotations
+    (`evolution.trotter_rotations`: order 1 or 2, `steps` steps; H a Pauli sum over LOGICAL qubits), on the device
+    through the staging layout `buf.log_to_phys` (nothing is downloaded or permuted).  Returns the HBM passes made."""
+    return evolution.evolve(buf.state, getattr(buf, "log_to_phys", None) or None, obs, t, steps, order)
 
 
 def reduced_density_matrix(buf: HbmStateBuffer, qubits) -> np.ndarray:

@@ -1,0 +1,233 @@
+"""Pauli rotations exp(-i theta P) without a GPU: the host reference (tests/rotation_reference.py) against
+scipy.linalg.expm of explicit Kronecker products and against the gate decomposition through oracle.dense_oracle; the
+pass plan qsim_plan_pauli_rotations (a pure function); `evolution.trotter_rotations` / `to_physical` against
+expm(-i t H)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import scipy.linalg
+
+from oracle import dense_oracle as orc
+from quantum_simulations_amd import _lib, evolution
+from quantum_simulations_amd.circuit.staging import permute_state
+from quantum_simulations_amd.kernel import planner
+from quantum_simulations_amd.observable import PauliSum
+from tests.rotation_reference import rotate, rotate_list, rotation_gates
+
+_PAULI = {(0, 0): np.eye(2), (1, 0): np.array([[0, 1], [1, 0]]), (1, 1): np.array([[0, -1j], [1j, 0]]),
+          (0, 1): np.array([[1, 0], [0, -1]])}
+
+
+def _rand_state(n, seed):
+    rng = np.random.default_rng(seed)
+    psi = rng.standard_normal(1 << n) + 1j * rng.standard_normal(1 << n)
+    return psi / np.linalg.norm(psi)
+
+
+def _kron(n, x, z):
+    """P as a 2^n x 2^n matrix: qubit q = bit q of the index, so the highest qubit is the leftmost Kronecker factor."""
+    m = np.eye(1, dtype=np.complex128)
+    for q in reversed(range(n)):
+        m = np.kron(m, _PAULI[((x >> q) & 1, (z >> q) & 1)])
+    return m
+
+
+def _rand_masks(rng, n):
+    x = int(rng.integers(0, 1 << n))
+    z = int(rng.integers(0, 1 << n))
+    return x, z
+
+
+# ---- the reference -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5])
+def test_reference_against_expm(n):
+    rng = np.random.default_rng(10 + n)
+    cases = [(0, 0), ((1 << n) - 1, (1 << n) - 1), (1, 0), (1, 1), (0, 1)] + [_rand_masks(rng, n) for _ in range(12)]
+    for x, z in cases:
+        theta = float(rng.uniform(-np.pi, np.pi))
+        psi = _rand_state(n, int(rng.integers(1 << 30)))
+        want = scipy.linalg.expm(-1j * theta * _kron(n, x, z)) @ psi
+        assert float(np.max(np.abs(rotate(psi, x, z, theta) - want))) < 1e-13, (n, x, z)
+
+
+@pytest.mark.parametrize("n", [1, 3, 6, 9])
+def test_reference_against_the_gate_decomposition(n):
+    rng = np.random.default_rng(20 + n)
+    cases = [(0, 0), ((1 << n) - 1, 0), ((1 << n) - 1, (1 << n) - 1), (0, (1 << n) - 1)] + [_rand_masks(rng, n) for _ in range(10)]
+    for x, z in cases:
+        theta = float(rng.uniform(-np.pi, np.pi))
+        psi = _rand_state(n, int(rng.integers(1 << 30)))
+        got = psi.copy()
+        orc.apply_ops(got, rotation_gates(x, z, theta))
+        assert float(np.max(np.abs(got - rotate(psi, x, z, theta)))) < 1e-13, (n, x, z)
+        got = psi.copy()
+        orc.apply_ops(got, evolution.rotation_gates(x, z, theta))   # the package's own decomposition (the probe's baseline)
+        assert float(np.max(np.abs(got - rotate(psi, x, z, theta)))) < 1e-13, (n, x, z)
+
+
+def test_rotation_parses_dicts_and_labels():
+    assert evolution.rotation({0: "X", 3: "Z", 5: "Y"}, 0.25) == (0b100001, 0b101000, 0.25)
+    assert evolution.rotation("X0 Z3 Y5", 0.25) == (0b100001, 0b101000, 0.25)
+    assert evolution.rotation("ZIX", -1.0) == (0b001, 0b100, -1.0)          # dense: the rightmost letter is qubit 0
+    assert evolution.rotation({}, 0.5) == (0, 0, 0.5)
+    for bad in (({0: "Q"}, 0.1), ({0: "X"}, float("nan")), ({-1: "X"}, 0.1), (3, 0.1)):
+        with pytest.raises(ValueError):
+            evolution.rotation(*bad)
+
+
+# ---- the pass plan -------------------------------------------------------------------------------------------------
+def _check_plan(k, x):
+    pass_of, tiles = planner.plan_pauli_rotations(k, x)
+    K, line = min(k, 11), (1 << min(k, 3)) - 1
+    assert len(pass_of) == len(x)
+    assert np.all(np.diff(pass_of) >= 0)                           # order preserving
+    if len(x):
+        assert pass_of[0] == 0 and pass_of[-1] == len(tiles) - 1 and np.all(np.diff(pass_of) <= 1)
+    for p, T in enumerate(int(t) for t in tiles):
+        members = [int(x[t]) for t in range(len(x)) if pass_of[t] == p]
+        assert 1 <= len(members) <= 1024
+        if T == 0 and k > 0:                                       # wide: one rotation whose x does not fit a tile
+            assert len(members) == 1 and bin(members[0] | line).count("1") > K
+            continue
+        assert bin(T).count("1") == K and T & line == line and T >> k == 0
+        for m in members:
+            assert m & ~T == 0 and bin(m | line).count("1") <= K
+    return pass_of, tiles
+
+
+@pytest.mark.parametrize("k", [0, 1, 2, 3, 5, 10, 11, 12, 14, 20, 28, 40, 63])
+def test_plan_properties_on_random_lists(k):
+    rng = np.random.default_rng(30 + k)
+    xs = [0, (1 << k) - 1, 1 if k else 0, (1 << k) >> 1]
+    for w in range(0, k + 1):
+        for _ in range(3):
+            xs.append(sum(1 << int(q) for q in rng.choice(k, size=w, replace=False)) if w else 0)
+    x = np.array([xs[i] for i in rng.permutation(len(xs))], dtype=np.uint64)
+    _check_plan(k, x)
+    assert len(_check_plan(k, x[:0])[1]) == 0
+
+
+def test_plan_greedy_walk():
+    # the rule, step by step at k = 14: join while the union fits 11 bits, a wide rotation closes the open pass
+    x = [1 << 3, 1 << 4, 0, 0x7F8, 1 << 11, 0x3FFF, 1 << 11, 1 << 12, 0x3FF8, 0]
+    pass_of, tiles = _check_plan(14, x)
+    assert list(pass_of) == [0, 0, 0, 0, 1, 2, 3, 3, 4, 5]
+    assert [int(t) for t in tiles] == [0x7FF, 0xBFF, 0, 0x19FF, 0, 0x7FF]
+    # k < 3 and k < 11: the whole chunk is one tile, nothing is wide
+    assert [int(t) for t in _check_plan(2, [3, 0, 1, 2])[1]] == [3]
+    assert [int(t) for t in _check_plan(7, [0x7F, 0, 0x40])[1]] == [0x7F]
+    assert [int(t) for t in _check_plan(0, [0, 0])[1]] == [0]
+
+
+def test_plan_cap_of_1024_opens_a_new_pass():
+    x = np.ones(1024 + 1024 + 5, dtype=np.uint64)
+    pass_of, tiles = _check_plan(12, x)
+    assert len(tiles) == 3 and list(np.bincount(pass_of)) == [1024, 1024, 5]
+    pass_of, tiles = _check_plan(5, np.zeros(1025, dtype=np.uint64))
+    assert list(np.bincount(pass_of)) == [1024, 1]
+
+
+def heisenberg_chain(n, brick=False):
+    """sum over the bonds (q, q + 1) of XX + YY + ZZ, the bonds in order or in brick order (even bonds, then odd)."""
+    bonds = list(range(n - 1))
+    if brick:
+        bonds = bonds[0::2] + bonds[1::2]
+    return PauliSum([(1.0, {q: p, q + 1: p}) for q in bonds for p in "XYZ"], n_qubits=n)
+
+
+@pytest.mark.parametrize("k,rotations", [(28, 81), (30, 87)])
+def test_plan_of_the_heisenberg_chain_step(k, rotations):
+    for brick, passes in ((False, 4), (True, 7)):
+        x, z, th = evolution.trotter_rotations(heisenberg_chain(k, brick), 0.1)
+        assert len(x) == rotations
+        assert len(_check_plan(k, x)[1]) == passes
+
+
+def test_plan_errors():
+    lib = _lib.load()
+    x = np.array([1, 1 << 8], dtype=np.uint64)
+    pass_of, tiles, n = np.zeros(2, dtype=np.int32), np.zeros(2, dtype=np.uint64), C.c_int(-1)
+    args = (_lib.ptr(pass_of), _lib.ptr(tiles), C.byref(n))
+    assert lib.qsim_plan_pauli_rotations(8, 2, _lib.ptr(x), *args) == _lib.QSIM_ERR_NONLOCAL
+    assert lib.qsim_plan_pauli_rotations(9, 2, _lib.ptr(x), *args) == _lib.QSIM_OK and n.value == 1
+    assert lib.qsim_plan_pauli_rotations(9, 2, None, *args) == _lib.QSIM_ERR_INVALID
+    assert lib.qsim_plan_pauli_rotations(9, 2, _lib.ptr(x), None, _lib.ptr(tiles), C.byref(n)) == _lib.QSIM_ERR_INVALID
+    assert lib.qsim_plan_pauli_rotations(9, 2, _lib.ptr(x), _lib.ptr(pass_of), _lib.ptr(tiles), None) == _lib.QSIM_ERR_INVALID
+    assert lib.qsim_plan_pauli_rotations(9, -1, _lib.ptr(x), *args) == _lib.QSIM_ERR_INVALID
+    assert lib.qsim_plan_pauli_rotations(64, 2, _lib.ptr(x), *args) == _lib.QSIM_ERR_INVALID
+    assert lib.qsim_plan_pauli_rotations(9, 0, None, None, None, C.byref(n)) == _lib.QSIM_OK and n.value == 0
+    with pytest.raises(NotImplementedError):
+        planner.plan_pauli_rotations(8, [1 << 8])
+
+
+# ---- Trotter lists -------------------------------------------------------------------------------------------------
+def _dense(obs):
+    return sum(c * _kron(obs.n_qubits, x, z) for c, x, z in zip(obs.coeffs, obs.x, obs.z))
+
+
+def test_trotter_list_shapes():
+    obs = PauliSum([(0.5, {0: "X"}), (-2.0, {}), (1.5, {0: "Z", 1: "Y"})], n_qubits=2)
+    x, z, th = evolution.trotter_rotations(obs, 0.4, steps=2)
+    assert list(x) == [1, 0, 2] * 2 and list(z) == [0, 0, 3] * 2             # the identity stays: a global phase
+    np.testing.assert_allclose(th, [0.1, -0.4, 0.3] * 2, rtol=0, atol=1e-16)
+    x, z, th = evolution.trotter_rotations(obs, 0.4, steps=2, order=2)
+    assert list(x) == [1, 0, 2, 2, 0, 1] * 2 and list(z) == [0, 0, 3, 3, 0, 0] * 2
+    np.testing.assert_allclose(th, [0.05, -0.2, 0.15, 0.15, -0.2, 0.05] * 2, rtol=0, atol=1e-16)
+    assert x.dtype == z.dtype == np.uint64 and th.dtype == np.float64
+    for bad in (dict(steps=0), dict(order=3), dict(t=float("inf"))):
+        with pytest.raises(ValueError):
+            evolution.trotter_rotations(obs, **{"t": 0.4, **bad})
+
+
+def test_trotter_orders_converge_to_expm():
+    n, t = 6, 0.8
+    obs = PauliSum([(c, s) for (c, s) in zip(np.random.default_rng(5).uniform(0.5, 1.5, 15),
+                                              [{q: p, q + 1: p} for q in range(n - 1) for p in "XYZ"])] + [(0.3, {})], n_qubits=n)
+    psi = _rand_state(n, 6)
+    want = scipy.linalg.expm(-1j * t * _dense(obs)) @ psi
+    err = {}
+    for order in (1, 2):
+        for steps in (8, 16, 256):
+            err[order, steps] = float(np.max(np.abs(rotate_list(psi, *evolution.trotter_rotations(obs, t, steps, order)) - want)))
+    print("trotter errors", err)
+    assert err[1, 8] / err[1, 16] > 1.5                            # theory: 2
+    assert err[2, 8] / err[2, 16] > 3.0                            # theory: 4
+    assert err[1, 256] < err[1, 16] / 8 and err[2, 256] < err[2, 16] / 100 and err[2, 256] < 1e-4
+
+
+def test_trotter_of_a_single_term_is_exact():
+    n = 5
+    psi = _rand_state(n, 7)
+    for label, c in (("X0 Y2 Z4", 0.7), ("Z1", -1.3), ("I", 0.4)):
+        obs = PauliSum({label: c}, n_qubits=n)
+        want = scipy.linalg.expm(-1j * 0.9 * _dense(obs)) @ psi
+        for order, steps in ((1, 1), (1, 7), (2, 1), (2, 5)):
+            got = rotate_list(psi, *evolution.trotter_rotations(obs, 0.9, steps, order))
+            assert float(np.max(np.abs(got - want))) < 1e-13, (label, order, steps)
+
+
+def test_to_physical_equals_permuting_the_state():
+    n = 7
+    rng = np.random.default_rng(8)
+    l2p = [int(p) for p in rng.permutation(n)]
+    x, z, th = evolution.as_rotation_arrays([(*_rand_masks(rng, n), float(rng.uniform(-1, 1))) for _ in range(10)])
+    psi = _rand_state(n, 9)                                        # logical order
+    px, pz = evolution.to_physical(x, z, l2p)
+    for q in range(n):
+        assert np.all(((x >> np.uint64(q)) & np.uint64(1)) == ((px >> np.uint64(l2p[q])) & np.uint64(1)))
+    # the physical state: logical qubit q on bit l2p[q]; permute_state undoes the layout
+    idx = np.arange(1 << n)
+    to_logical = np.zeros_like(idx)
+    for q, p in enumerate(l2p):
+        to_logical |= ((idx >> p) & 1) << q
+    phys = psi[to_logical]
+    np.testing.assert_array_equal(permute_state(phys, l2p), psi)
+    got = permute_state(rotate_list(phys, px, pz, th), l2p)
+    assert float(np.max(np.abs(got - rotate_list(psi, x, z, th)))) < 1e-14
+    ix, iz = evolution.to_physical(x, z, None)
+    assert np.array_equal(ix, x) and np.array_equal(iz, z)
+    with pytest.raises(ValueError):
+        evolution.to_physical([1 << 3], [0], [0, 1, 2])
+    with pytest.raises(ValueError):
+        evolution.to_physical([1], [0], [0, 0])
