@@ -416,6 +416,34 @@ int qsim_apply_pauli_rotations(qsim_chunk* c, int n, const uint64_t* x_masks, co
  * stays within the width, else it opens a new pass.  A bit >= n_local_qubits in x fails with QSIM_ERR_NONLOCAL. */
 int qsim_plan_pauli_rotations(int n_local_qubits, int n, const uint64_t* x_masks, int32_t* pass_of,
                               uint64_t* tile_masks, int* n_passes);
+/* A Pauli sum applied as an operator, OUT OF PLACE: dst = sum_t coeffs[t] P_t src, with real finite coefficients and
+ * P_t two masks of physical local index bits as in qsim_expectation_pauli:
+ *   (P psi)_j = i^ny (-1)^popcount((j ^ x) & z) psi_{j ^ x},   ny = popcount(x & z).
+ * The terms are grouped by qsim_plan_expectation (they commute under the sum).  The FIRST pass writes dst -- what dst
+ * held before does not matter -- and every later pass accumulates into it: a tile pass reads src once and adds up to
+ * 1024 terms whose x lies in its <= 11 tile bits from LDS (32 B per amplitude for the writing pass, 48 B for an
+ * accumulating one), a wide pass one term whose x does not fit a tile.  The terms of a pass are added in a fixed
+ * order: two calls give the same bits.  n_terms == 0 fills dst with zeros (*n_passes = 0).  The passes are enqueued on
+ * dst's stream like the gate calls (no kernel is waited for).  *n_passes = the passes made (= qsim_plan_expectation's).
+ * src is only read.  A bit of x | z >= log2(chunk) fails with QSIM_ERR_NONLOCAL; a null argument, n_terms < 0, a
+ * coefficient that is not finite, chunks of different size, device or stream (all qsim_create chunks of a device share
+ * one stream), dst and src ranges that overlap at all (the same chunk, a view inside the other) and slab pieces pending
+ * on either chunk fail with QSIM_ERR_INVALID; nothing is changed then. */
+int qsim_apply_pauli_sum(qsim_chunk* dst, const qsim_chunk* src, int n_terms, const uint64_t* x_masks,
+                         const uint64_t* z_masks, const double* coeffs, int* n_passes);
+/* Matrix elements of Pauli strings between two states, unnormalised and complex:
+ *   out[t] = <bra|P_t|ket> = sum_j conj(bra_j) (P_t ket)_j   for t < n_terms,
+ * as (re, im) pairs: out_re_im holds 2 * n_terms doubles.  x = z = 0 gives <bra|ket>; bra == ket (or overlapping
+ * ranges: both chunks are only read) is allowed and gives <psi|P|psi> with an imaginary part of rounding size.
+ * Read-only passes grouped by qsim_plan_expectation: a tile pass holds a bra tile and a ket tile in LDS and evaluates
+ * up to 1024 terms from them (32 B per amplitude per pass), a wide pass one term whose x does not fit a tile.
+ * Per-workgroup partials are summed in workgroup order on the device (no atomics): two calls give the same bits.  The
+ * workspace is the ket's; only the 2 * n_terms doubles cross to the host; blocks until out_re_im is written.
+ * *n_passes = the passes that ran.  A bit of x | z >= log2(chunk) fails with QSIM_ERR_NONLOCAL; a null argument,
+ * n_terms < 0, chunks of different size, device or stream and slab pieces pending on either chunk with
+ * QSIM_ERR_INVALID. */
+int qsim_overlap_pauli(qsim_chunk* ket, const qsim_chunk* bra, int n_terms, const uint64_t* x_masks,
+                       const uint64_t* z_masks, double* out_re_im, int* n_passes);
 /* Shot sampling of the full register: n_shots samples of the chunk-local index from |amp|^2 / total.  randnums[s] in
  * [0, 1) is the caller's uniform for shot s (the caller owns the generator); out_indices[s] is the smallest i with
  * cdf(i) > randnums[s] * total in the device's fixed summation order; results come back in the order of randnums.  An

@@ -143,8 +143,9 @@ static const char* const kClassNames[] = {
     "k_gate_shuffle<1,1> lane 1q", "k_gate_shuffle<1,2> lane 2q", "k_gate_shuffle<2,1> lane+reg 2q",
     "k_tile fused pass", "k_dense dense k-qubit block", "k_hist outcome probabilities",
     "k_sample_block_sums shot sampling, pass A", "k_sample_resolve shot sampling, pass B",
-    "k_rdm reduced density matrix", "k_rot Pauli rotations"};
-constexpr int kNumClasses = 13;
+    "k_rdm reduced density matrix", "k_rot Pauli rotations", "k_psum Pauli-sum action",
+    "k_ovl two-state overlaps"};
+constexpr int kNumClasses = 15;
 
 static hipEvent_t prof_event_locked() {
   if (!g_prof_pool.empty()) {

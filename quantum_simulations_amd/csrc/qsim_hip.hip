@@ -58,6 +58,8 @@ typedef unsigned long long u64;
 #include "dense_kernels.h"
 #include "expect_kernels.h"
 #include "rot_kernels.h"
+#include "psum_kernels.h"
+#include "ovl_kernels.h"
 #include "rdm_kernels.h"
 #include "sample_kernels.h"
 #include "comm_rccl.h"
@@ -66,6 +68,7 @@ typedef unsigned long long u64;
 #include "abi_pending.h"
 #include "abi_readout.h"
 #include "abi_rotation.h"
+#include "abi_twostate.h"
 #include "abi_chunk.h"
 #include "abi_gates.h"
 #include "abi_plan.h"

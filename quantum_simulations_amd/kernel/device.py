@@ -196,6 +196,39 @@ class DeviceChunk:
         self.last_rotation_passes = passes.value
         return passes.value
 
+    def apply_pauli_sum(self, src: "DeviceChunk", x_masks, z_masks, coeffs) -> int:
+        """self := sum_t coeffs[t] P_t src, OUT OF PLACE (`self` is dst: what it held does not matter; `src` is only
+        read and may not overlap it); P_t as masks of PHYSICAL index bits (x: X or Y, z: Z or Y), real finite
+        coefficients (qsim_apply_pauli_sum: the first pass writes, the later ones accumulate, enqueued on the chunk's
+        stream).  No terms: self := 0.  Returns the passes made, also kept in `self.last_pauli_sum_passes`."""
+        x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
+        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
+        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
+        if not x.shape == z.shape == co.shape:
+            raise ValueError(f"apply_pauli_sum: {x.size} x masks, {z.size} z masks, {co.size} coefficients")
+        passes = C.c_int(0)
+        _lib.check(_lib.load().qsim_apply_pauli_sum(self._h, src._h, int(x.size), _lib.ptr(x), _lib.ptr(z), _lib.ptr(co), C.byref(passes)))
+        self.last_pauli_sum_passes = passes.value
+        return passes.value
+
+    def overlap_pauli(self, bra: "DeviceChunk", x_masks, z_masks) -> np.ndarray:
+        """<bra|P_t|self> of Pauli strings given as masks of PHYSICAL index bits (`self` is the ket), unnormalised,
+        complex128 (qsim_overlap_pauli: read-only passes over both chunks, a fixed summation order -- two calls give the
+        same bits).  `bra` may be `self`.  `self.last_overlap_passes` = the passes that ran."""
+        x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
+        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
+        if x.shape != z.shape:
+            raise ValueError(f"overlap_pauli: {x.size} x masks, {z.size} z masks")
+        out = np.empty(x.size, dtype=np.complex128)
+        passes = C.c_int(0)
+        _lib.check(_lib.load().qsim_overlap_pauli(self._h, bra._h, int(x.size), _lib.ptr(x), _lib.ptr(z), _lib.ptr(out), C.byref(passes)))
+        self.last_overlap_passes = passes.value
+        return out
+
+    def overlap(self, bra: "DeviceChunk") -> complex:
+        """<bra|self>, unnormalised: the identity string of `overlap_pauli`."""
+        return complex(self.overlap_pauli(bra, [0], [0])[0])
+
     # ---- sync / reductions / timing -------------------------------------------------
     def apply_ops_io(self, ops, src=None, dst=None, parts: int = 0, src_parts: int = 0, tiles=None) -> int:
         """`apply_ops` with a re-layout fused into its ends (qsim_apply_ops_io): `src` = (chunk, bits): the state

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from quantum_simulations_amd import evolution, readout
+from quantum_simulations_amd import evolution, hamiltonian, readout
 from quantum_simulations_amd.circuit.fusion import batch_levels
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.kernel import gates as gate_table, planner
@@ -68,6 +68,7 @@ class SingleGpuEngine:
         self.state = DeviceChunk.empty(n_qubits, device)
         self.l2p: list | None = None        # layout of the state right now (None = identity)
         self._zero = False                  # the state is |0..0>: the same vector in every layout
+        self._work: DeviceChunk | None = None   # a second chunk of the state's size (H|psi>, lambda): allocated on first use
 
     # ---- state ---------------------------------------------------------------------
     def init_zero_state(self) -> None:
@@ -110,6 +111,46 @@ class SingleGpuEngine:
         passes = evolution.evolve(self.state, self.l2p, obs, t, steps, order)
         self._zero = False
         return passes
+
+    def _work_chunk(self) -> DeviceChunk:
+        if self._work is None:
+            self._work = DeviceChunk.empty(self.n, self.state.device)
+        return self._work
+
+    def apply_observable(self, obs, out: DeviceChunk | None = None) -> DeviceChunk:
+        """H|psi> for a Pauli sum over LOGICAL qubits, written on the device into `out` (a chunk of the state's size
+        on its device; default: the engine's own second chunk, allocated on first use and overwritten by `variance` and
+        `gradient`) IN THE STATE'S CURRENT LAYOUT `self.l2p`; the state does not move.  Returns that chunk;
+        `out.last_pauli_sum_passes` = the HBM passes made."""
+        out = self._work_chunk() if out is None else out
+        hamiltonian.apply(out, self.state, self.l2p, obs)
+        return out
+
+    def variance(self, obs) -> float:
+        """<H^2> - <H>^2 (unnormalised: norm2(H psi) - <psi|H|psi>^2) of a Pauli sum over LOGICAL qubits, on the
+        device; the engine's second chunk is overwritten."""
+        return hamiltonian.variance(self.state, self._work_chunk(), self.l2p, obs)
+
+    def overlap_with(self, chunk: DeviceChunk, obs=None):
+        """<chunk|psi> (obs None: a complex number), or <chunk|H|psi> = sum_t c_t <chunk|P_t|psi> for a Pauli sum over
+        LOGICAL qubits, on the device; `chunk` holds a state of the same size in the state's current layout `self.l2p`
+        (what `apply_observable` writes, or a copy of an earlier state).  Neither state moves."""
+        if obs is None:
+            return self.state.overlap(chunk)
+        from quantum_simulations_amd.observable import as_pauli_sum
+        obs = as_pauli_sum(obs, self.n)
+        terms = hamiltonian.matrix_elements(self.state, chunk, self.l2p, obs)
+        return complex(sum(float(c) * complex(v) for c, v in zip(obs.coeffs, terms)))
+
+    def gradient(self, rotations, obs) -> tuple:
+        """(E, dE/dtheta) of E = <psi(theta)|H|psi(theta)> with psi(theta) = the rotation list (every entry its own
+        parameter, exp(-i theta P) without a factor 1/2; forms as in `apply_pauli_rotations`) applied to the CURRENT
+        state, by the adjoint method on the device (`hamiltonian.adjoint_gradient`: one forward run, then one overlap
+        and two single-rotation passes per parameter).  The state is the same afterwards up to rounding; the engine's
+        second chunk is overwritten."""
+        out = hamiltonian.adjoint_gradient(self.state, self._work_chunk(), self.l2p, rotations, obs)
+        self._zero = False
+        return out
 
     def reduced_density_matrix(self, qubits) -> np.ndarray:
         """Reduced density matrix (unnormalised, complex128 (2^r, 2^r)) of 1 to 6 LOGICAL qubits, bit j of a row or
@@ -396,6 +437,9 @@ class SingleGpuEngine:
         return worst
 
     def close(self) -> None:
+        if self._work is not None:
+            self._work.close()
+            self._work = None
         self.state.close()
 
 

@@ -23,7 +23,7 @@ from pathlib import Path
 
 import numpy as np
 
-from quantum_simulations_amd import evolution, readout
+from quantum_simulations_amd import evolution, hamiltonian, readout
 from quantum_simulations_amd.circuit.fusion import batch_levels, split_by_locality
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.circuit.staging import atlas_stages, permute_state
@@ -315,6 +315,29 @@ def evolve(buf: HbmStateBuffer, obs, t, steps: int = 1, order: int = 1) -> int:
     (`evolution.trotter_rotations`: order 1 or 2, `steps` steps; H a Pauli sum over LOGICAL qubits), on the device
     through the staging layout `buf.log_to_phys` (nothing is downloaded or permuted).  Returns the HBM passes made."""
     return evolution.evolve(buf.state, getattr(buf, "log_to_phys", None) or None, obs, t, steps, order)
+
+
+def variance(buf: HbmStateBuffer, obs) -> float:
+    """<H^2> - <H>^2 (unnormalised: norm2(H psi) - <psi|H|psi>^2) of a Pauli sum over LOGICAL qubits on the final state of
+    `run`, on the device through the staging layout `buf.log_to_phys`; a second chunk of the state's size is allocated
+    for the call and closed."""
+    work = DeviceChunk.empty(buf.state.k, buf.state.device)
+    try:
+        return hamiltonian.variance(buf.state, work, getattr(buf, "log_to_phys", None) or None, obs)
+    finally:
+        work.close()
+
+
+def gradient(buf: HbmStateBuffer, rotations, obs) -> tuple:
+    """(E, dE/dtheta) of E = <psi(theta)|H|psi(theta)>, psi(theta) = the rotation list (every entry its own parameter,
+    exp(-i theta P) without a factor 1/2) applied to the final state of `run`, by the adjoint method on the device
+    (`hamiltonian.adjoint_gradient`) through the staging layout `buf.log_to_phys`.  The state is the same afterwards up to
+    rounding; a second chunk of the state's size is allocated for the call and closed."""
+    work = DeviceChunk.empty(buf.state.k, buf.state.device)
+    try:
+        return hamiltonian.adjoint_gradient(buf.state, work, getattr(buf, "log_to_phys", None) or None, rotations, obs)
+    finally:
+        work.close()
 
 
 def reduced_density_matrix(buf: HbmStateBuffer, qubits) -> np.ndarray:
