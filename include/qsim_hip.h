@@ -105,6 +105,12 @@ int qsim_plan_cache_clear(void);   /* forget the cached pass images of earlier o
  * runner/engine.py -- gets the same passes on the new bits.  A mask that holds no op is ignored (the search takes over). */
 int qsim_apply_ops_tiled(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
                          int n_tiles, const uint64_t* tile_masks);
+/* qsim_apply_ops_tiled with a placement: op i does not run before pass earliest_pass[i] of the named passes (n_ops entries;
+ * NULL: qsim_apply_ops_tiled).  In an earlier pass the op waits like one whose target is not in the tile and blocks what
+ * depends on it, so any values give the same amplitudes; qsim_plan_balance chooses them so that ops which need no tile
+ * leave the passes whose gate engine is the bottleneck. */
+int qsim_apply_ops_placed(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                          int n_tiles, const uint64_t* tile_masks, const int32_t* earliest_pass);
 
 /* ---- op list with a re-layout fused into its ends ------------------------------------------------
  * Multi-GPU re-layouts (the staging SWAP lists of wenbo_engine/circuit/staging.py:136-152, merged into one
@@ -206,6 +212,42 @@ int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int
  * after).  Host only. */
 int qsim_rewrite_ops(int n_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, int32_t* out_nq,
                      int32_t* out_qubits, double* out_mats, int out_capacity, int32_t* n_out, int32_t* need_tile);
+
+/* The measured price of the fused pass's gate engine, as the caller hands it to the priced planning calls (the shipped
+ * table is runner/engine_cost_model.json; the library reads nothing from a file or the environment): entry
+ * QSIM_ENGINE_COST_x = microseconds one record of that kind adds to a pass of 2^FIT_QUBITS amplitudes once the pass is
+ * engine bound; FIXED_US = the engine time of a pass before its first record (a pass costs max(memory time, FIXED_US + its records)); GROUP = a change of register group;
+ * PRED_LANE / PRED_OUTER / REG_CTRL = the FRACTION of its plain cost that a record costs under a predicate on tile bits
+ * outside the register group, on index bits outside the tile, or with its control on a register bit; DIRECT_END = what an
+ * end of the pass that moves between global memory and registers without its LDS trip adds (negative).  A NULL table
+ * switches the pricing off. */
+enum { QSIM_ENGINE_COST_FIXED_US = 0, QSIM_ENGINE_COST_GROUP, QSIM_ENGINE_COST_DENSE1, QSIM_ENGINE_COST_REAL1,
+       QSIM_ENGINE_COST_HAD1, QSIM_ENGINE_COST_SWAP1, QSIM_ENGINE_COST_ASWAP1, QSIM_ENGINE_COST_ANTI1, QSIM_ENGINE_COST_PHASE,
+       QSIM_ENGINE_COST_PHASE_NEG, QSIM_ENGINE_COST_PHASE_I, QSIM_ENGINE_COST_DIAGR, QSIM_ENGINE_COST_DENSE2,
+       QSIM_ENGINE_COST_PRED_LANE, QSIM_ENGINE_COST_PRED_OUTER, QSIM_ENGINE_COST_REG_CTRL, QSIM_ENGINE_COST_DIRECT_END,
+       QSIM_ENGINE_COST_FIT_QUBITS, QSIM_ENGINE_COST_COUNT };
+/* Pass time = max(memory time of the tile, engine time of the records): the placement (qsim_apply_ops_placed,
+ * qsim_plan_ops_placed) of the op list over the n_tiles named passes under the caller's prices.  pass_memory_us[p]: what
+ * the tile of pass p costs without gates (the tile-cost model of runner/tile_layout.py); engine_costs: the engine table.
+ * An op that needs no tile may run in any pass from the one first come gives it to the earliest pass of a later op that
+ * targets one of its qubits (its window).  Passes are taken in order; while the records of a pass are priced above its
+ * memory time, the last such op of the pass moves to the pass of its window with the most slack (memory time minus
+ * engine time), if that slack holds it.  Out: earliest_pass (n_ops; NULL: the passes are only priced, nothing is placed),
+ * the modelled engine microseconds of every pass before and after (n_tiles each; either may be NULL).  A placement that
+ * would cost a pass more, or model no gain, is not made (all zero, after = before).  Host only. */
+int qsim_plan_balance(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                      int n_tiles, const uint64_t* tile_masks, const double* pass_memory_us, const double* engine_costs,
+                      int n_engine_costs, int32_t* earliest_pass, double* engine_us_before, double* engine_us_after);
+/* qsim_plan_ops_tiled under a placement (earliest_pass: n_ops entries or NULL). */
+int qsim_plan_ops_placed(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                         int n_tiles, const uint64_t* tile_masks, const int32_t* earliest_pass, void* out,
+                         uint64_t out_capacity_bytes, int32_t* n_passes);
+/* qsim_rewrite_ops with rule (d): a diagonal 1q gate is multiplied into a dense 1q gate on its qubit (U D or D U, exact)
+ * when only ops that are diagonal on that qubit lie between them and the table prices the product's record below the two
+ * it replaces.  Never more ops that need a tile than qsim_rewrite_ops leaves.  engine_costs NULL: qsim_rewrite_ops. */
+int qsim_rewrite_ops_priced(int n_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                            int32_t* out_nq, int32_t* out_qubits, double* out_mats, int out_capacity, int32_t* n_out,
+                            int32_t* need_tile, const double* engine_costs, int n_engine_costs);
 
 /* Pass counts of ONE op list under n_layouts qubit layouts (layouts[l * n_local_qubits + q] = index bit of logical qubit q),
  * planned in parallel on n_threads host threads, no device: the pass builder's result depends on which qubits live on the

@@ -62,7 +62,11 @@ SIGNATURES = {
     "qsim_plan_ops_tiled": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_uint64, _P]),
     "qsim_plan_search": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P]),
     "qsim_rewrite_ops": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "qsim_rewrite_ops_priced": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int]),
     "qsim_apply_ops_tiled": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "qsim_apply_ops_placed": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
+    "qsim_plan_ops_placed": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_uint64, _P]),
+    "qsim_plan_balance": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P]),
     "qsim_choose_layout": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_uint64, C.c_int, _P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "qsim_plan_count_layouts": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int]),
     "qsim_plan_peek_pass": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),

@@ -74,7 +74,7 @@ int qsim_apply_ops_unfused(qsim_chunk* c, int n_ops, const int32_t* nq, const in
 
 // qsim_apply_ops and qsim_apply_ops_tiled (n_tiles = 0: the pass builder searches every tile itself)
 static int apply_ops_fused(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
-                           int n_tiles, const uint64_t* tile_masks, const char* what) {
+                           int n_tiles, const uint64_t* tile_masks, const char* what, const int32_t* earliest_pass = nullptr) {
   int rc = validate_ops(c, n_ops, nq, qubits, mats);
   if (rc) return rc;
   if (n_tiles < 0 || (n_tiles && !tile_masks)) return fail(QSIM_ERR_INVALID, "%s: bad tile list", what);
@@ -85,9 +85,14 @@ static int apply_ops_fused(qsim_chunk* c, int n_ops, const int32_t* nq, const in
   }
   HIP_TRY(hipSetDevice(c->device));
   std::vector<FusedOp> ops;
-  classify_ops(n_ops, nq, qubits, mats, &ops);
+  std::vector<int32_t> origin, placed;           // (identities drop out of the planned list: the placement follows)
+  classify_ops(n_ops, nq, qubits, mats, &ops, &origin);
   int passes = 0;
-  const TileHint hint = {tile_masks, n_tiles};
+  TileHint hint = {tile_masks, n_tiles};
+  if (earliest_pass && n_tiles) {
+    for (int32_t i : origin) placed.push_back(earliest_pass[i]);
+    hint.earliest = placed.data();
+  }
   rc = run_fused(c, ops, RawOps{n_ops, nq, qubits, mats}, n_tiles ? &hint : nullptr, nullptr, &passes,
                  [&](TileArgs& a, int T, double alg_bytes, bool) { return dispatch_planned(c, a, T, alg_bytes); });
   c->last_passes = passes;
@@ -102,6 +107,11 @@ int qsim_apply_ops(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t* q
 int qsim_apply_ops_tiled(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
                          int n_tiles, const uint64_t* tile_masks) {
   return apply_ops_fused(c, n_ops, nq, qubits, mats, n_tiles, tile_masks, "qsim_apply_ops_tiled");
+}
+// ... and with a placement: op i not before pass earliest_pass[i] of the named passes (TileHint::earliest)
+int qsim_apply_ops_placed(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                          int n_tiles, const uint64_t* tile_masks, const int32_t* earliest_pass) {
+  return apply_ops_fused(c, n_ops, nq, qubits, mats, n_tiles, tile_masks, "qsim_apply_ops_placed", earliest_pass);
 }
 
 // Dense k-qubit block: new[idx with the block's bits = out] = sum_in M[out][in] old[idx with the block's bits = in], pattern

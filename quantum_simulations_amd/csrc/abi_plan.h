@@ -12,28 +12,31 @@ int qsim_plan_cache_clear(void) {
 
 static_assert(sizeof(TileArgs) == QSIM_PASS_IMAGE_BYTES, "pass image = the kernel-argument block of k_tile");
 
-int qsim_plan_ops(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
-                  void* out, uint64_t out_capacity_bytes, int32_t* n_passes) {
-  return qsim_plan_ops_tiled(n_local_qubits, n_ops, nq, qubits, mats, 0, nullptr, out, out_capacity_bytes, n_passes);
-}
-
-int qsim_plan_ops_tiled(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
-                        int n_tiles, const uint64_t* tile_masks, void* out, uint64_t out_capacity_bytes, int32_t* n_passes) {
-  if (n_tiles < 0 || (n_tiles && !tile_masks)) return fail(QSIM_ERR_INVALID, "qsim_plan_ops_tiled: bad tile list");
-  if (!n_passes) return fail(QSIM_ERR_INVALID, "qsim_plan_ops: n_passes is null");
+}  // extern "C"
+// qsim_plan_ops, qsim_plan_ops_tiled (no placement) and qsim_plan_ops_placed: one body, `what` names the call in its errors
+static int plan_ops_images(const char* what, int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits,
+                           const double* mats, int n_tiles, const uint64_t* tile_masks, const int32_t* earliest_pass, void* out,
+                           uint64_t out_capacity_bytes, int32_t* n_passes) {
+  if (n_tiles < 0 || (n_tiles && !tile_masks)) return fail(QSIM_ERR_INVALID, "%s: bad tile list", what);
+  if (!n_passes) return fail(QSIM_ERR_INVALID, "%s: n_passes is null", what);
   if (n_local_qubits < kTileMinChunk || n_local_qubits > kTileMaxQubits)
-    return fail(QSIM_ERR_INVALID, "qsim_plan_ops: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
+    return fail(QSIM_ERR_INVALID, "%s: fused passes need %d..%d local qubits", what, kTileMinChunk, kTileMaxQubits);
   int rc = check_op_list(n_ops, nq, qubits, mats, n_local_qubits, kQubitOfPlan);
   if (rc) return rc;
   std::vector<FusedOp> ops;
-  classify_ops(n_ops, nq, qubits, mats, &ops);
+  std::vector<int32_t> origin, placed;
+  classify_ops(n_ops, nq, qubits, mats, &ops, &origin);
   int passes = 0;
   char* dst = (char*)out;
   uint64_t used = 0;
-  const TileHint hint = {tile_masks, n_tiles};
+  TileHint hint = {tile_masks, n_tiles};
+  if (earliest_pass && n_tiles) {
+    for (int32_t i : origin) placed.push_back(earliest_pass[i]);
+    hint.earliest = placed.data();
+  }
   rc = plan_fused(n_local_qubits, ops, &passes, [&](TileArgs& a, int T, double, bool, bool) {
     if (dst) {
-      if (used + sizeof(TileArgs) > out_capacity_bytes) return fail(QSIM_ERR_INVALID, "qsim_plan_ops: output buffer too small");
+      if (used + sizeof(TileArgs) > out_capacity_bytes) return fail(QSIM_ERR_INVALID, "%s: output buffer too small", what);
       std::memcpy(dst + used, &a, sizeof a);
     }
     used += sizeof(TileArgs);
@@ -41,6 +44,22 @@ int qsim_plan_ops_tiled(int n_local_qubits, int n_ops, const int32_t* nq, const 
   }, n_tiles ? &hint : nullptr);
   *n_passes = passes;
   return rc;
+}
+extern "C" {
+int qsim_plan_ops(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                  void* out, uint64_t out_capacity_bytes, int32_t* n_passes) {
+  return plan_ops_images("qsim_plan_ops", n_local_qubits, n_ops, nq, qubits, mats, 0, nullptr, nullptr, out, out_capacity_bytes, n_passes);
+}
+int qsim_plan_ops_tiled(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                        int n_tiles, const uint64_t* tile_masks, void* out, uint64_t out_capacity_bytes, int32_t* n_passes) {
+  return plan_ops_images("qsim_plan_ops_tiled", n_local_qubits, n_ops, nq, qubits, mats, n_tiles, tile_masks, nullptr, out,
+                         out_capacity_bytes, n_passes);
+}
+int qsim_plan_ops_placed(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                         int n_tiles, const uint64_t* tile_masks, const int32_t* earliest_pass, void* out,
+                         uint64_t out_capacity_bytes, int32_t* n_passes) {
+  return plan_ops_images("qsim_plan_ops_placed", n_local_qubits, n_ops, nq, qubits, mats, n_tiles, tile_masks, earliest_pass, out,
+                         out_capacity_bytes, n_passes);
 }
 
 // The searching pass builder (tile_search.h): the tiles of a plan of the op list with as few passes as a beam search of
@@ -71,6 +90,36 @@ int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int
   return QSIM_OK;
 }
 
+// The placement of an op list over its named passes under the caller's prices (tile_search.h plan_balance); earliest_pass
+// NULL: the passes are only priced (engine_us_before), nothing is placed.
+int qsim_plan_balance(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                      int n_tiles, const uint64_t* tile_masks, const double* pass_memory_us, const double* engine_costs,
+                      int n_engine_costs, int32_t* earliest_pass, double* engine_us_before, double* engine_us_after) {
+  if (n_tiles < 1 || !tile_masks || !pass_memory_us) return fail(QSIM_ERR_INVALID, "qsim_plan_balance: bad arguments");
+  if (n_local_qubits < kTileMinChunk || n_local_qubits > kTileMaxQubits)
+    return fail(QSIM_ERR_INVALID, "qsim_plan_balance: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
+  EngineCosts ec;
+  if (!engine_costs_from(engine_costs, n_engine_costs, &ec))
+    return fail(QSIM_ERR_INVALID, "qsim_plan_balance: the cost table needs %d entries", (int)QSIM_ENGINE_COST_COUNT);
+  int rc = check_op_list(n_ops, nq, qubits, mats, n_local_qubits, kQubitOfPlan);
+  if (rc) return rc;
+  std::vector<FusedOp> ops;
+  std::vector<int32_t> origin;
+  classify_ops(n_ops, nq, qubits, mats, &ops, &origin);
+  const std::vector<u64> masks(tile_masks, tile_masks + n_tiles);
+  std::vector<int32_t> placed;
+  std::vector<double> before, after;
+  rc = plan_balance(n_local_qubits, ops, masks, pass_memory_us, ec, earliest_pass != nullptr, &placed, &before, &after);
+  if (rc) return rc;
+  for (int i = 0; earliest_pass && i < n_ops; ++i) earliest_pass[i] = 0;
+  for (size_t j = 0; earliest_pass && j < origin.size(); ++j) earliest_pass[origin[j]] = placed[j];
+  for (int p = 0; p < n_tiles; ++p) {
+    if (engine_us_before) engine_us_before[p] = before[(size_t)p];
+    if (engine_us_after) engine_us_after[p] = after[(size_t)p];
+  }
+  return QSIM_OK;
+}
+
 // The op list a plan for repeated execution is made from (op_rewrite.h): X / Y gates pushed into their neighbours, CNOTs with
 // an exact H on the target turned into CZ.  Same packed format in and out, same amplitudes (up to the rounding of the 2x2
 // products); identities drop out.  out_capacity: ops the three output arrays have room for (2 * n_ops + n_qubits is always
@@ -78,6 +127,13 @@ int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int
 // their target inside the tile, before and after.  Host only, no device, deterministic, linear in n_ops.
 int qsim_rewrite_ops(int n_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, int32_t* out_nq,
                      int32_t* out_qubits, double* out_mats, int out_capacity, int32_t* n_out, int32_t* need_tile) {
+  return qsim_rewrite_ops_priced(n_qubits, n_ops, nq, qubits, mats, out_nq, out_qubits, out_mats, out_capacity, n_out, need_tile, nullptr, 0);
+}
+
+// ... with rule (d) of op_rewrite.h under the caller's engine cost table (QSIM_ENGINE_COST_*; NULL: qsim_rewrite_ops).
+int qsim_rewrite_ops_priced(int n_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                            int32_t* out_nq, int32_t* out_qubits, double* out_mats, int out_capacity, int32_t* n_out,
+                            int32_t* need_tile, const double* engine_costs, int n_engine_costs) {
   if (!n_out || out_capacity < 0 || (out_capacity && (!out_nq || !out_qubits || !out_mats)))
     return fail(QSIM_ERR_INVALID, "qsim_rewrite_ops: bad arguments");
   if (n_qubits < 1 || n_qubits > 63) return fail(QSIM_ERR_INVALID, "qsim_rewrite_ops: bad qubit count %d", n_qubits);
@@ -85,7 +141,10 @@ int qsim_rewrite_ops(int n_qubits, int n_ops, const int32_t* nq, const int32_t* 
   if (rc) return rc;
   std::vector<RwOp> ops;
   int need_in = 0, need_out = 0;
-  rewrite_op_list(n_qubits, n_ops, nq, qubits, mats, &ops, &need_in);
+  EngineCosts ec;
+  const bool priced = engine_costs_from(engine_costs, n_engine_costs, &ec);
+  if (engine_costs && !priced) return fail(QSIM_ERR_INVALID, "qsim_rewrite_ops_priced: the cost table has %d entries, not %d", n_engine_costs, (int)QSIM_ENGINE_COST_COUNT);
+  rewrite_op_list(n_qubits, n_ops, nq, qubits, mats, &ops, &need_in, priced ? &ec : nullptr);
   *n_out = (int32_t)ops.size();
   if (ops.size() > (size_t)out_capacity) return fail(QSIM_ERR_INVALID, "qsim_rewrite_ops: output buffer too small (%d ops)", (int)ops.size());
   for (size_t i = 0; i < ops.size(); ++i) {

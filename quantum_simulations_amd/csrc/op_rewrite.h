@@ -12,6 +12,11 @@
 //       (C(V) -> C(X V X)) and takes it in on the control (the op becomes a dense 2q gate).
 //   (c) what is still pending at the end of the list is pushed BACKWARDS by the mirrored rules into the nearest earlier
 //       dense gate (X G); a frame that reaches the front of the list becomes an explicit X there.
+//   (d) (priced calls only) a diagonal 1q gate D is multiplied into a dense 1q gate U on its qubit -- U D when U comes later,
+//       D U when it came before -- when only ops that are diagonal on that qubit (controls, CZ / CR, other diagonals: they
+//       commute with D) lie between them and the engine cost table prices the product's record below the two it replaces: Z
+//       always pays, S or T make a complex 2x2 of a real one and pay only where that is cheaper.  The dense gate stays where
+//       it is, so no op that needs a tile appears or moves.
 // All identities are algebraic: they hold for non-unitary factors (collapse factors) and drop no global phase -- a diagonal
 // diag(d0, d1) that a frame leaves behind is written as the phase gate diag(1, d1 / d0), which needs no tile, and the
 // factor d0 is multiplied into one dense 1q gate of the list.  Same amplitudes up to the rounding of the 2x2 products.
@@ -319,9 +324,65 @@ static void rw_frame_sweep(const std::vector<RwOp>& in, bool backward, std::vect
   if (backward) std::reverse(out.begin(), out.end());
 }
 
-// One application of (a), (b), (c).  When the factor taken out of the diagonals finds no dense 1q gate to go into (a list
+// ---- (d) a diagonal 1q gate into a dense 1q gate on its qubit ------------------------------------------------------------------
+static double rw_record_us(const EngineCosts& ec, const RwOp& o) { return ec.of_family(op_shape(o.f).family); }
+// one sweep; true: something was merged (a host that turned complex takes further diagonals in for nothing: sweep again)
+static bool rw_merge_diagonals(std::vector<RwOp>* list, int n_qubits, const EngineCosts& ec) {
+  std::vector<RwOp>& ops = *list;
+  const size_t n = ops.size();
+  std::vector<char> dead(n, 0);
+  std::vector<std::vector<size_t>> on((size_t)n_qubits);      // the ops on every qubit, in list order
+  for (size_t i = 0; i < n; ++i)
+    for (int s = 0; s < ops[i].nq; ++s) on[(size_t)ops[i].q[s]].push_back(i);
+  bool any = false;
+  for (int q = 0; q < n_qubits; ++q) {
+    const std::vector<size_t>& w = on[(size_t)q];
+    for (size_t a = 0; a < w.size(); ++a) {
+      const size_t i = w[a];
+      if (dead[i] || rw_class(ops[i]) != RW_DIAG1) continue;
+      // the nearest op on q that is not diagonal on q, later [0] and earlier [1]: a host when it is a dense 1q gate
+      long host[2] = {-1, -1};
+      for (size_t b = a + 1; b < w.size(); ++b) {
+        if (dead[w[b]] || rw_diagonal_on(ops[w[b]], q)) continue;
+        if (rw_class(ops[w[b]]) == RW_DENSE1) host[0] = (long)w[b];
+        break;
+      }
+      for (size_t b = a; b-- > 0;) {
+        if (dead[w[b]] || rw_diagonal_on(ops[w[b]], q)) continue;
+        if (rw_class(ops[w[b]]) == RW_DENSE1) host[1] = (long)w[b];
+        break;
+      }
+      double2 d[4];
+      rw_1q_matrix(ops[i], d);
+      double best_gain = 0;
+      int best = -1;
+      RwOp merged[2];
+      bool identity[2] = {false, false};
+      for (int side = 0; side < 2; ++side) {
+        if (host[side] < 0) continue;
+        double2 u[4], prod[4];
+        rw_1q_matrix(ops[(size_t)host[side]], u);
+        if (side == 0) mul2x2(u, d, prod); else mul2x2(d, u, prod);
+        identity[side] = !rw_make_1q(q, prod, &merged[side]);
+        const double gain = rw_record_us(ec, ops[i]) + rw_record_us(ec, ops[(size_t)host[side]]) -
+                            (identity[side] ? 0.0 : rw_record_us(ec, merged[side]));
+        if (gain > best_gain) { best_gain = gain; best = side; }
+      }
+      if (best < 0) continue;
+      if (identity[best]) dead[(size_t)host[best]] = 1; else ops[(size_t)host[best]] = merged[best];
+      dead[i] = 1;
+      any = true;
+    }
+  }
+  size_t w = 0;
+  for (size_t i = 0; i < n; ++i) if (!dead[i]) { if (w != i) ops[w] = ops[i]; ++w; }
+  ops.resize(w);
+  return any;
+}
+
+// One application of (a), (b), (c) and, with a cost table, (d).  When the factor taken out of the diagonals finds no dense 1q gate to go into (a list
 // without one), the list after (a) is the result.
-static void rw_once(const std::vector<RwOp>& in, int n_qubits, std::vector<RwOp>* out) {
+static void rw_once(const std::vector<RwOp>& in, int n_qubits, std::vector<RwOp>* out, const EngineCosts* ec) {
   std::vector<RwOp> a, b, c;
   rw_h_conversion(in, &a, n_qubits);
   std::vector<char> frame((size_t)n_qubits, 0);
@@ -341,14 +402,18 @@ static void rw_once(const std::vector<RwOp>& in, int n_qubits, std::vector<RwOp>
       const int rank = cplx ? 3 : (real && !rw_is_h(c[i])) ? 2 : 1;
       if (rank > best) { best = rank; host = (long)i; }
     }
-    if (host < 0) { *out = a; return; }
-    double2 g[4];
-    rw_1q_matrix(c[(size_t)host], g);
-    for (int e = 0; e < 4; ++e) g[e] = cmul(scalar, g[e]);
-    RwOp scaled;
-    rw_make_1q(c[(size_t)host].q[0], g, &scaled);
-    c[(size_t)host] = scaled;
+    if (host < 0) {
+      c = a;
+    } else {
+      double2 g[4];
+      rw_1q_matrix(c[(size_t)host], g);
+      for (int e = 0; e < 4; ++e) g[e] = cmul(scalar, g[e]);
+      RwOp scaled;
+      rw_make_1q(c[(size_t)host].q[0], g, &scaled);
+      c[(size_t)host] = scaled;
+    }
   }
+  if (ec) while (rw_merge_diagonals(&c, n_qubits, *ec)) {}
   *out = c;
 }
 
@@ -364,7 +429,7 @@ static int rw_need_tile(const std::vector<RwOp>& ops) {
 // long as the list gets better -- fewer ops that need a tile, or as many and fewer ops -- and the last list that was an
 // improvement is the result: never more tile needs than the caller's list, and a rewritten list is a fixed point.
 static void rewrite_op_list(int n_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
-                            std::vector<RwOp>* out, int* need_tile_in) {
+                            std::vector<RwOp>* out, int* need_tile_in, const EngineCosts* ec = nullptr) {
   std::vector<RwOp> cur;
   cur.reserve((size_t)n_ops);
   for (int i = 0; i < n_ops; ++i) {
@@ -380,7 +445,7 @@ static void rewrite_op_list(int n_qubits, int n_ops, const int32_t* nq, const in
   if (need_tile_in) *need_tile_in = need;
   for (int round = 0; round < 8; ++round) {
     std::vector<RwOp> next;
-    rw_once(cur, n_qubits, &next);
+    rw_once(cur, n_qubits, &next, ec);
     const int need_next = rw_need_tile(next);
     if (need_next > need || (need_next == need && next.size() >= cur.size())) break;
     cur.swap(next);

@@ -279,7 +279,9 @@ static int run_fused(qsim_chunk* c, const std::vector<FusedOp>& ops, const RawOp
   u64 hash = 0;
   const size_t n_ops = (size_t)raw.n;
   const size_t hint_bytes = hint ? sizeof(uint64_t) * (size_t)hint->n : 0;
-  const size_t key_bytes = n_ops * (sizeof(int32_t) * 3 + sizeof(double) * 32) + hint_bytes;
+  const size_t placed_bytes = hint && hint->earliest ? sizeof(int32_t) * ops.size() : 0;
+  const int32_t hint_tag[2] = {hint ? hint->n : -1, placed_bytes != 0};   // (named tiles, placement present: no hint list reads as another)
+  const size_t key_bytes = n_ops * (sizeof(int32_t) * 3 + sizeof(double) * 32) + sizeof hint_tag + hint_bytes + placed_bytes;
   const bool cacheable = raw.nq && raw.qubits && raw.mats && raw.n > 0 && key_bytes <= kPlanCacheMaxKeyBytes && tuning().debug_stats == 0 &&
                          tuning().debug_skip_gates == 0;     // (probe passes take their tile bits from the environment at plan time)
   if (cacheable) {
@@ -288,7 +290,9 @@ static int run_fused(qsim_chunk* c, const std::vector<FusedOp>& ops, const RawOp
     std::memcpy(w, raw.nq, sizeof(int32_t) * n_ops); w += sizeof(int32_t) * n_ops;
     std::memcpy(w, raw.qubits, sizeof(int32_t) * 2 * n_ops); w += sizeof(int32_t) * 2 * n_ops;
     std::memcpy(w, raw.mats, sizeof(double) * 32 * n_ops); w += sizeof(double) * 32 * n_ops;
+    std::memcpy(w, hint_tag, sizeof hint_tag); w += sizeof hint_tag;
     if (hint_bytes) std::memcpy(w, hint->masks, hint_bytes);
+    if (placed_bytes) std::memcpy(w + hint_bytes, hint->earliest, placed_bytes);
     hash = fnv1a(key.data(), key.size(), 1469598103934665603ull ^ (u64)c->k);
     std::vector<CachedPass> hit;
     {

@@ -156,6 +156,62 @@ static int op_cost(const FusedOp& o) {
 }
 constexpr int kRecordCost = 8;                 // a record's fetch + dispatch, in the same unit
 
+// The MEASURED price of the gate engine (runner/engine_cost_model.json, fitted by tools/fit_engine_cost_model.py to one-pass
+// probes on MI355X): microseconds a record of each kind adds to a pass of the fitted state size once the pass is past the
+// knee -- the engine time a pass hides under its memory time.  Handed in by the caller (QSIM_ENGINE_COST_* of
+// include/qsim_hip.h name the entries), never read from the environment; a null table switches every priced decision off.
+struct EngineCosts {
+  double v[QSIM_ENGINE_COST_COUNT];
+  double of_family(int family) const {
+    switch (family) {
+      case OPC_DENSE1: return v[QSIM_ENGINE_COST_DENSE1];
+      case OPC_REAL1: return v[QSIM_ENGINE_COST_REAL1];
+      case OPC_HAD1: return v[QSIM_ENGINE_COST_HAD1];
+      case OPC_SWAP1: return v[QSIM_ENGINE_COST_SWAP1];
+      case OPC_ASWAP1: return v[QSIM_ENGINE_COST_ASWAP1];
+      case OPC_ANTI1: case OPC_YLIKE1: return v[QSIM_ENGINE_COST_ANTI1];
+      case OPC_PHASE: return v[QSIM_ENGINE_COST_PHASE];
+      case OPC_PHASE_NEG: return v[QSIM_ENGINE_COST_PHASE_NEG];
+      case OPC_PHASE_I: case OPC_PHASE_NI: return v[QSIM_ENGINE_COST_PHASE_I];
+      case OPC_DIAGR: return v[QSIM_ENGINE_COST_DIAGR];
+      case OPC_SCALE: return v[QSIM_ENGINE_COST_PHASE];
+      default: return v[QSIM_ENGINE_COST_DENSE2];
+    }
+  }
+  // family of a written record's case entry (families are runs of entries: the last base at or below it)
+  static int family_of_entry(int opcode) {
+    static const int bases[] = {OPC_DENSE1, OPC_SWAP1, OPC_ANTI1, OPC_PHASE, OPC_DENSE2, OPC_REAL1, OPC_YLIKE1, OPC_PHASE_NEG,
+                                OPC_PHASE_I, OPC_PHASE_NI, OPC_DIAGR, OPC_HAD1, OPC_SCALE, OPC_ASWAP1};
+    int best = OPC_DENSE1;
+    for (int b : bases) if (b <= opcode && b > best) best = b;
+    return best;
+  }
+  // microseconds of one written record at the fitted state size
+  double of_record(const TileDesc& d) const {
+    const int fam = family_of_entry(d.opcode);
+    const bool one_q = fam == OPC_DENSE1 || fam == OPC_SWAP1 || fam == OPC_ANTI1 || fam == OPC_REAL1 || fam == OPC_YLIKE1 || fam == OPC_ASWAP1;
+    return of_family(fam) * (d.blk_mask ? v[QSIM_ENGINE_COST_PRED_LANE] : 1.0) * (d.outer_mask ? v[QSIM_ENGINE_COST_PRED_OUTER] : 1.0) *
+           ((one_q && d.opcode - fam >= 3) ? v[QSIM_ENGINE_COST_REG_CTRL] : 1.0);
+  }
+  // modelled engine microseconds of a pass on 2^k amplitudes
+  double of_pass(const std::vector<TileGroup>& groups, int k) const {
+    double us = v[QSIM_ENGINE_COST_FIXED_US];
+    if (!groups.empty() && tuning().tile_direct)          // (full tiles: an end above the line bits skips its LDS trip)
+      us += v[QSIM_ENGINE_COST_DIRECT_END] * ((groups.front().s[0] >= kTileLow) + (groups.back().s[0] >= kTileLow));
+    for (const TileGroup& g : groups) {
+      us += v[QSIM_ENGINE_COST_GROUP];
+      for (const TileDesc& d : g.gates) us += of_record(d);
+    }
+    return us * std::ldexp(1.0, k - (int)v[QSIM_ENGINE_COST_FIT_QUBITS]);
+  }
+};
+// (false: no table, pricing off)
+static bool engine_costs_from(const double* table, int count, EngineCosts* ec) {
+  if (!table || count < QSIM_ENGINE_COST_COUNT) return false;
+  for (int i = 0; i < QSIM_ENGINE_COST_COUNT; ++i) ec->v[i] = table[i];
+  return true;
+}
+
 // ---- commutation-aware fusion of one-qubit gates -------------------------------------------------
 // The host planners (circuit/fusion.py, the reference's fuse_1q_ops) only merge 1q gates that are ADJACENT on their
 // qubit.  Inside the library a 1q gate G on qubit q also moves forward past every op it commutes with -- a

@@ -25,8 +25,12 @@ constexpr int kTileMinChunk = kTileThreadBits > 8 ? kTileThreadBits : 8;   // sm
 // `hint` (qsim_apply_ops_tiled): the caller names the high tile bits of the first passes itself -- a host that has planned
 // the list once and moved its qubits to other index bits (a layout chosen for the memory pattern of the tiles:
 // runner/engine.py) gets the SAME passes on the new bits instead of whatever the search finds there.  A hint that holds no
-// op (or too many bits) is ignored and the search takes over for that pass.
-struct TileHint { const uint64_t* masks; int n; };
+// op (or too many bits) is ignored and the search takes over for that pass.  `earliest` (qsim_apply_ops_placed; optional, one
+// entry per op of the planned list): op i does not run before pass earliest[i] of the named passes -- in an earlier pass
+// it waits like an op whose target is not in the tile, and blocks what depends on it, so ANY values give a correct
+// program.  It is how a host that has priced the passes (qsim_plan_balance) moves ops that need no tile out of a pass
+// whose gate engine is the bottleneck into a later one that has room.  Ignored from the first pass the hint does not name.
+struct TileHint { const uint64_t* masks; int n; const int32_t* earliest = nullptr; };
 // Peek mode (qsim_plan_peek_pass, the partition planner of runner/partition_plan.py): the op list lives on `n_total` >= k
 // index bits; the bits >= k are RANK bits of a partitioned state -- never tile bits, never targets (an op that targets one
 // waits, and blocks like any waiting op), but fine as controls and phase bits (a rank applies or skips such an op by its own
@@ -56,6 +60,8 @@ struct PassBuilder {
   std::vector<u64> xm;                         // ... of those, the ones it acts on as 1 or X only (X, CNOT targets): X-diagonal
   u64 all_qubits, rank_bits;                   // (rank bits: peek mode only: no tile bit, no target)
   bool lookahead;
+  const int32_t* earliest = nullptr;           // TileHint::earliest while the hint names the pass, and the pass being built
+  int pass_no = 0;
   size_t remaining, first = 0;
   // How far behind `first` a pass looks for ops (counted in ops not yet done).  The scans below end early once every
   // qubit is blocked for everything (`bt`), which never happens while some qubit is used only as a control, phase bit or
@@ -66,9 +72,14 @@ struct PassBuilder {
   // (byte-identical plans to the unbounded scan on the 28- / 30-qubit bench and Clifford+T circuits from 384 on; lists
   // of more than four windows use two thirds of it: 7.5 -> 1.4 ms per pass on a 4000-op list with a control-only qubit)
   int scan_window;
-  // A pass is memory bound up to ~32 descriptors and pays ~0.03 ms for each one beyond that
-  // (tools/gate_cost_probe.py), so holding more than kSaturated ops buys nothing: a first-come pass
-  // that is already that full is kept (phase-heavy circuits: QFT).
+  // What a pass costs (round 19, runner/engine_cost_model.json, profiles/r19a_pass_engine_split.txt): max(memory time of its
+  // tile, 0.68 ms + its records), a record 12 (Z) .. 27 (real 2x2) .. 57 us (complex 2x2) at 28 qubits, a group change 44 us.
+  // With tiles of 1.33-1.73 ms a pass is memory bound up to 32-52 records of the bench mix (20 us on average) and bound by
+  // the gate engine beyond -- which 7 of the 13 passes of the bench plan measurably are.  Records are therefore never free, but a
+  // pass more costs what 65 of them cost, so holding more ops keeps paying up to the record budget: kSaturated is no
+  // knee of the hardware.  It is the count from which a first-come pass is kept without looking for a fuller tile
+  // (phase-heavy circuits: QFT) and the cap of the look-ahead scores, and it stays at the value the plans of the tests and
+  // of profiles/ were made with; the engine time itself is priced after the search (tile_search.h plan_balance).
   static constexpr int kSaturated = 64;
   bool tie_break;                              // plan_conflict_cost = -1: conflicts only break ties between tiles that hold the same number of ops
   u64 jit_state;
@@ -137,7 +148,7 @@ struct PassBuilder {
     for (size_t i = first; i < n_ops && count < tune.max_gates_per_pass; ++i) {
       if (done[i]) continue;
       if (++seen > scan_window) break;
-      if (!blocked.admits(i) || (need[i] & ~tile_mask)) {
+      if (!blocked.admits(i) || (need[i] & ~tile_mask) || (earliest && earliest[i] > pass_no)) {
         if (blocked.add(i)) break;
         continue;
       }
@@ -395,10 +406,17 @@ static int plan_fused(int k, const std::vector<FusedOp>& ops_in, int* n_passes, 
   u64 prev_mask = 0;                            // high bits of the pass before (anchored tiles)
   while (pb.remaining) {
     pb.begin_pass();
-    const u64 best_mask = pb.choose_tile(hint, *n_passes, prev_mask, depth2);
-    std::vector<int> high = pb.bits_of(best_mask);   // chosen high bits
+    pb.pass_no = *n_passes;
+    pb.earliest = (hint && hint->earliest && *n_passes < hint->n && !tune.tile_commute_fuse) ? hint->earliest : nullptr;
+    u64 best_mask = pb.choose_tile(hint, *n_passes, prev_mask, depth2);
     std::vector<size_t> members;
     pb.holds(best_mask, &members);
+    if (members.empty() && pb.earliest) {          // everything admissible was told to wait: the pass is built without that
+      pb.earliest = nullptr;
+      best_mask = pb.choose_tile(hint, *n_passes, prev_mask, depth2);
+      pb.holds(best_mask, &members);
+    }
+    std::vector<int> high = pb.bits_of(best_mask);   // chosen high bits
     if (peek) {
       // (everything that is left may be waiting for a rank bit: an empty pass is an answer here, not an error)
       if (members.empty()) { *n_passes = 0; return QSIM_OK; }

@@ -166,3 +166,90 @@ static int plan_search(int k, const std::vector<FusedOp>& ops_in, int beam, std:
   if (replay_passes == (int)found.size() && replay == found) { *masks = found; *n_passes = replay_passes; }
   return QSIM_OK;
 }
+
+// ---- pass time = max(memory, engine): the placement of the ops that need no tile ----------------------------------------
+// The builders above fill every pass first come, and treat its records as free.  They are not: past FIXED_US + its records
+// > the memory time of its tile a pass is bound by the gate engine (profiles/r19a_pass_engine_split.txt: 1.45 of 21.3 ms at
+// 28 qubits, while the last two passes of the plan carry next to nothing).  Ops that need no tile -- diagonal 1q gates, CZ /
+// CR: 43 % of the rewritten bench list -- may run in any pass from the one first come puts them in to the pass of the
+// first later op that TARGETS one of their qubits (everything else on their qubits is diagonal there and commutes).  So:
+// the named passes are replayed first come and priced (what PassBuilder::emit really writes, by the table); then, pass by
+// pass, while the records of a pass cost more than its memory time, the last such op of the pass goes to the pass of its
+// window with the most engine slack, if that slack holds it (TileHint::earliest).  Waiting is the builder's own notion, so
+// the result is a correct program whatever is moved, and inside its window an op blocks nothing that runs; what could
+// still go wrong is the record budget of the receiving pass, hence the replay at the end: a placement that does not give
+// the named passes exactly, or that the model does not price lower, is dropped.
+// mem_us: per named pass; eng_before / eng_after: modelled engine microseconds per pass; place = false: priced only.
+static int plan_balance(int k, const std::vector<FusedOp>& ops_in, const std::vector<u64>& masks, const double* mem_us,
+                        const EngineCosts& ec, bool place, std::vector<int32_t>* earliest, std::vector<double>* eng_before,
+                        std::vector<double>* eng_after) {
+  const std::vector<FusedOp> ops = planned_ops(ops_in);
+  const size_t n_pass = masks.size(), n_ops = ops.size();
+  earliest->assign(ops_in.size(), 0);
+  eng_before->assign(n_pass, 0.0);
+  eng_after->assign(n_pass, 0.0);
+  if (n_ops != ops_in.size() || !n_pass) return QSIM_OK;              // (the probe build's commuting fusion renumbers the ops)
+  std::vector<size_t> members;
+  std::vector<char> emitted;
+  std::vector<TileGroup> groups;
+  std::vector<int32_t> pass_of(n_ops, -1);
+  PassBuilder rules(k, ops, k);                                        // (the masks qm / tm of every op)
+  // the named passes under a placement: modelled engine time and the pass of every op; false: they do not finish the list
+  auto replay = [&](const int32_t* place, std::vector<double>* eng) {
+    PassBuilder pb(k, ops, k);
+    for (size_t p = 0; p < n_pass && pb.remaining; ++p) {
+      pb.begin_pass();
+      pb.pass_no = (int)p;
+      pb.earliest = place;
+      members.clear();
+      pb.holds(masks[p], &members);
+      if (members.empty()) return false;
+      pb.emit(members, pb.filled(pb.bits_of(masks[p])), &groups, &emitted);
+      (*eng)[p] = ec.of_pass(groups, k);
+      for (size_t mi = 0; mi < members.size(); ++mi) if (emitted[mi]) pass_of[members[mi]] = (int32_t)p;
+      size_t n_emitted = 0;
+      pb.account(members, emitted, &n_emitted);
+      if (!n_emitted) return false;
+    }
+    return pb.remaining == 0;
+  };
+  if (!replay(nullptr, eng_before)) return QSIM_OK;
+  *eng_after = *eng_before;
+  if (!place) return QSIM_OK;                                          // (the caller only wanted the prices)
+  const double scale = std::ldexp(1.0, k - (int)ec.v[QSIM_ENGINE_COST_FIT_QUBITS]);
+  std::vector<double> slack(n_pass);
+  for (size_t p = 0; p < n_pass; ++p) slack[p] = mem_us[p] - (*eng_before)[p];
+  // the last pass an op without a tile need may run in: the earliest pass of a later op that targets one of its qubits
+  // (not the first such op of the list: CNOTs with a common target commute, and a later one may run a pass earlier)
+  std::vector<int32_t> window(n_ops, -1);
+  for (size_t i = 0; i < n_ops; ++i) {
+    if (ops[i].ntargets) continue;
+    window[i] = (int32_t)n_pass - 1;
+    for (size_t j = i + 1; j < n_ops; ++j)
+      if (rules.tm[j] & rules.qm[i]) window[i] = std::min(window[i], pass_of[j]);
+  }
+  std::vector<int32_t> placed(n_ops, 0);
+  bool any = false;
+  for (size_t p = 0; p + 1 < n_pass; ++p)
+    for (size_t i = n_ops; i-- > 0 && slack[p] < 0;) {
+      if (pass_of[i] != (int32_t)p || window[i] <= (int32_t)p) continue;
+      const double us = ec.of_family(op_shape(ops[i]).family) * scale;
+      size_t to = p;
+      for (size_t q = p + 1; q <= (size_t)window[i]; ++q) if (to == p || slack[q] > slack[to]) to = q;
+      if (slack[to] < us) continue;
+      placed[i] = (int32_t)to;
+      slack[to] -= us;
+      slack[p] += us;
+      any = true;
+    }
+  if (!any) return QSIM_OK;
+  // the check: the placement handed back through the hint path gives the named passes, and the model prices them lower
+  std::vector<double> check(n_pass, 0.0);
+  if (!replay(placed.data(), &check)) return QSIM_OK;
+  double before = 0, after = 0;
+  for (size_t p = 0; p < n_pass; ++p) { before += std::max(mem_us[p], (*eng_before)[p]); after += std::max(mem_us[p], check[p]); }
+  if (!(after < before)) return QSIM_OK;
+  *earliest = placed;
+  *eng_after = check;
+  return QSIM_OK;
+}

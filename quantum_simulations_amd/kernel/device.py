@@ -169,6 +169,19 @@ class DeviceChunk:
         _lib.check(lib.qsim_apply_ops_tiled(self._h, len(nq), _lib.ptr(nq), _lib.ptr(qs), _lib.ptr(mats), len(tm), _lib.ptr(tm)))
         return lib.qsim_last_pass_count(self._h)
 
+    def apply_ops_placed(self, ops, tile_masks, earliest) -> int:
+        """`apply_ops_tiled` under a placement (qsim_apply_ops_placed): op i of `ops` does not run before pass earliest[i]
+        (int32, one per op: `planner.balance`) of the named passes.  Returns the HBM round trips."""
+        nq, qs, mats = as_packed(ops)
+        tm = np.ascontiguousarray(tile_masks, dtype=np.uint64)
+        place = np.ascontiguousarray(earliest, dtype=np.int32)
+        if len(place) != len(nq):
+            raise ValueError("one earliest pass per op expected")
+        lib = _lib.load()
+        _lib.check(lib.qsim_apply_ops_placed(self._h, len(nq), _lib.ptr(nq), _lib.ptr(qs), _lib.ptr(mats), len(tm), _lib.ptr(tm),
+                                             _lib.ptr(place)))
+        return lib.qsim_last_pass_count(self._h)
+
     def apply_ops(self, ops, fused: bool = True) -> int:
         """One pass: every (qubits, U) of `ops` in one C call.  `fused` groups them into LDS-tile
         launches (order kept for ops sharing a qubit); returns the number of HBM round trips.

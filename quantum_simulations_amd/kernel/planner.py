@@ -1,6 +1,6 @@
 """The host planner of libqsim_hip.so in Python: what the pass builder would do with an op list, without a device
-(csrc/abi_plan.h: qsim_plan_ops, qsim_plan_ops_tiled, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass,
-qsim_rewrite_ops; csrc/tile_launch.h: qsim_tiles_per_workgroup; csrc/abi_rotation.h: qsim_plan_pauli_rotations).
+(csrc/abi_plan.h: qsim_plan_ops, qsim_plan_ops_tiled, qsim_plan_ops_placed, qsim_plan_balance, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass,
+qsim_rewrite_ops_priced; csrc/tile_launch.h: qsim_tiles_per_workgroup; csrc/abi_rotation.h: qsim_plan_pauli_rotations).
 
 A thin binding.  `ops` is [(qubits, U), ...] or the tuple `pack_ops` returns (`device.as_packed`).  Return codes become
 the exceptions of `_lib.check` and nothing else is read into them: what a caller makes of a list too short to plan is
@@ -40,37 +40,64 @@ def tile_masks(images) -> np.ndarray:
     return np.array([sum(1 << b for b in tile_bits(img)) for img in images], dtype=np.uint64)
 
 
-def _plan(n: int, ops, tiles, images) -> tuple:
-    """(return code, pass count) of one qsim_plan_ops / qsim_plan_ops_tiled call; `images`: None to count only."""
+def _plan(n: int, ops, tiles, images, earliest=None) -> tuple:
+    """(return code, pass count) of one qsim_plan_ops / qsim_plan_ops_tiled / qsim_plan_ops_placed call; `images`: None to
+    count only."""
     nq, qubits, mats = as_packed(ops)
     lib, count = _lib.load(), C.c_int32()
     head = (n, len(nq), ptr(nq), ptr(qubits), ptr(mats))
     tail = (ptr(images), 0 if images is None else images.nbytes, C.byref(count))
     tm = np.ascontiguousarray(tiles if tiles is not None else [], dtype=np.uint64)
+    if len(tm) and earliest is not None:
+        place = np.ascontiguousarray(earliest, dtype=np.int32)
+        if len(place) != len(nq):
+            raise ValueError("one earliest pass per op expected")
+        return lib.qsim_plan_ops_placed(*head, len(tm), ptr(tm), ptr(place), *tail), count.value
     rc = lib.qsim_plan_ops_tiled(*head, len(tm), ptr(tm), *tail) if len(tm) else lib.qsim_plan_ops(*head, *tail)
     return rc, count.value
 
 
-def plan_ops(n: int, ops, tiles=None) -> np.ndarray:
+def plan_ops(n: int, ops, tiles=None, earliest=None) -> np.ndarray:
     """The pass images (PASS_IMAGE) of the fused plan of `ops` on n qubits; `tiles`: uint64 masks, the high tile bits of
-    the first passes named by the caller (qsim_plan_ops_tiled).  Planned once when the plan has up to 64 passes: the
+    the first passes named by the caller (qsim_plan_ops_tiled); `earliest`: with tiles, the placement of `balance` (op i
+    not before pass earliest[i]: qsim_plan_ops_placed).  Planned once when the plan has up to 64 passes: the
     library fills the buffer it is given and fails at the first image that does not fit, the count then being the images
     written -- a full buffer is planned again into one of twice the size."""
     room = _FIRST_BUFFER
     while True:
         images = np.zeros(room, dtype=PASS_IMAGE)
-        rc, count = _plan(n, ops, tiles, images)
+        rc, count = _plan(n, ops, tiles, images, earliest)
         if rc != _lib.QSIM_ERR_INVALID or count < room:     # (any other failure leaves the buffer short of full, or shows again below)
             _lib.check(rc)
             return images[:count]
         room *= 2
 
 
-def pass_count(n: int, ops, tiles=None) -> int:
-    """len(plan_ops(n, ops, tiles)) without the images."""
-    rc, count = _plan(n, ops, tiles, None)
+def pass_count(n: int, ops, tiles=None, earliest=None) -> int:
+    """len(plan_ops(n, ops, tiles, earliest)) without the images."""
+    rc, count = _plan(n, ops, tiles, None, earliest)
     _lib.check(rc)
     return count
+
+
+def balance(n: int, ops, tiles, pass_memory_us, engine_costs, place: bool = True) -> tuple:
+    """(earliest, engine_us_before, engine_us_after) of qsim_plan_balance: the placement of `ops` over the passes named by
+    `tiles` under pass time = max(pass_memory_us[p], engine time of the records priced by `engine_costs`) -- an op that
+    needs no tile leaves a pass whose records cost more than its memory time for the pass with the most slack among those
+    it may run in (up to the earliest pass of a later op that targets one of its qubits).  earliest: int32 per op (all zero
+    when no placement is modelled cheaper), for `plan_ops` / `DeviceChunk.apply_ops_placed`; the other two: modelled engine
+    microseconds per pass.  place = False: the passes are only priced (earliest is None, after = before)."""
+    nq, qubits, mats = as_packed(ops)
+    tm = np.ascontiguousarray(tiles, dtype=np.uint64)
+    mem = np.ascontiguousarray(pass_memory_us, dtype=np.float64)
+    costs = np.ascontiguousarray(engine_costs, dtype=np.float64)
+    if len(mem) != len(tm):
+        raise ValueError("one memory time per named pass expected")
+    earliest = np.zeros(len(nq), dtype=np.int32) if place else None
+    before, after = np.zeros(len(tm)), np.zeros(len(tm))
+    _lib.check(_lib.load().qsim_plan_balance(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), len(tm), ptr(tm), ptr(mem), ptr(costs),
+                                             len(costs), ptr(earliest), ptr(before), ptr(after)))
+    return earliest, before, after
 
 
 def tiles_per_workgroup(n: int, tile_bits: int, fixed_bits: int = 0) -> int:
@@ -93,17 +120,20 @@ def search_tiles(n: int, ops, beam: int = 0) -> np.ndarray:
     return out[:count.value].copy()
 
 
-def rewrite_ops(n: int, ops, stats: dict = None) -> list:
+def rewrite_ops(n: int, ops, stats: dict = None, engine_costs=None) -> list:
     """`ops` rewritten for planning (qsim_rewrite_ops, csrc/op_rewrite.h): X / Y gates pushed into their neighbours, CNOTs
     with an exact H on the target turned into CZ -- the same amplitudes from fewer ops that need their target inside a
-    tile.  Returns [(qubits, U), ...]; `stats`, when given, receives ops_in, ops_out, need_tile_in, need_tile_out."""
+    tile.  `engine_costs` (the table of `runner.engine_cost.table()`, QSIM_ENGINE_COST_* entries) adds rule (d): diagonal
+    1q gates multiplied into dense 1q gates where the table prices the product's record lower; None: pricing off.
+    Returns [(qubits, U), ...]; `stats`, when given, receives ops_in, ops_out, need_tile_in, need_tile_out."""
     nq, qubits, mats = as_packed(ops)
     room = 2 * len(nq) + n
     out_nq, out_q = np.zeros(room, dtype=np.int32), np.zeros(2 * room, dtype=np.int32)
     out_m = np.zeros((room, 16), dtype=np.complex128)
     count, need = C.c_int32(), np.zeros(2, dtype=np.int32)
-    _lib.check(_lib.load().qsim_rewrite_ops(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), ptr(out_nq), ptr(out_q), ptr(out_m),
-                                            room, C.byref(count), ptr(need)))
+    costs = None if engine_costs is None else np.ascontiguousarray(engine_costs, dtype=np.float64)
+    _lib.check(_lib.load().qsim_rewrite_ops_priced(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), ptr(out_nq), ptr(out_q), ptr(out_m),
+                                                   room, C.byref(count), ptr(need), ptr(costs), 0 if costs is None else len(costs)))
     if stats is not None:
         stats.update(ops_in=len(nq), ops_out=int(count.value), need_tile_in=int(need[0]), need_tile_out=int(need[1]))
     return [([int(out_q[2 * i])], out_m[i, :4].reshape(2, 2).copy()) if out_nq[i] == 1 else

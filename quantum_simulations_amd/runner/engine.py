@@ -30,6 +30,7 @@ class GpuPlan(list):
     `tiles` (per batch the high tile bits of its fused passes as uint64 masks, or None: let the library search) and `l2p`
     (the qubit layout the batches were written for: logical qubit q on index bit l2p[q]; None = identity)."""
     tiles: list
+    placed: list | None = None           # per batch the placement of its ops over the named passes (int32 per op: `planner.balance`), or None
     l2p: list | None = None
     model_ms: tuple | None = None        # (identity, chosen) totals of the tile-cost model over the passes, when a layout was chosen
 
@@ -57,6 +58,8 @@ class SingleGpuEngine:
     LAYOUT_CANDIDATES = 31         # random line-qubit triples (next to the identity) whose plans are searched
     LAYOUT_BEAM = 0                # beam width of the pass search (0: the library's default)
     LAYOUT_FINALISTS = 8           # minimum-pass layouts timed on the device (tune_on_device, |0..0> state only)
+    ENGINE_PRICING = True          # plans made for many executions price the gate engine (runner/engine_cost.py): rule (d) of the
+                                   # op rewrite, and ops that need no tile leave the passes whose records cost more than their memory time
 
     def __init__(self, n_qubits: int, device: int = 0, mode: str = "fused", layout: str = "auto", tune_on_device: bool = False):
         if layout not in ("auto", "search", "identity"):
@@ -204,19 +207,28 @@ class SingleGpuEngine:
         # tile, hence fewer passes (16 -> 13 on the 28-qubit bench circuit).  `passes_identity` stays what it was:
         # the greedy identity-layout count of the circuit's own ops.
         own_batches, rewrite = batches, {"ops_in": 0, "ops_out": 0, "need_tile_in": 0, "need_tile_out": 0}
+        from quantum_simulations_amd.runner import engine_cost
+        costs = engine_cost.table() if self.ENGINE_PRICING else None
         batches = []
         for ops in own_batches:
             stats = {}
             batches.append(planner.rewrite_ops(self.n, ops, stats))
             for key in rewrite:
                 rewrite[key] += stats[key]
+        # ... and, priced (runner/engine_cost.py), the same lists with rule (d): diagonal 1q gates multiplied into dense ones
+        # where the engine cost table prices the product's record lower.  The tiles are searched on the lists above -- ops
+        # that need no tile fewer never cost a pass under the same tiles -- and every finalist keeps whichever list the
+        # model prices lower under them (`priced_variant`).
+        priced = None if costs is None else [planner.rewrite_ops(self.n, ops, None, costs) for ops in own_batches]
         own_identity = int(_count_passes(self.n, own_batches, np.arange(self.n, dtype=np.int32)[None, :], 1)[0])
         finalists = choose_plan_layout(self.n, batches, self.LAYOUT_CANDIDATES, n_finalists=self.LAYOUT_FINALISTS if tune else 4,
-                                       all_finalists=True, beam=self.LAYOUT_BEAM)
+                                       all_finalists=True, beam=self.LAYOUT_BEAM, engine_costs=costs, priced_batches=priced)
 
         def build(l2p, masks, info):
-            plan = GpuPlan([pack_ops([([l2p[q] for q in qs], U) for qs, U in ops]) for ops in batches])
+            planned = info.pop("planned", None) or [[([l2p[q] for q in qs], U) for qs, U in ops] for ops in batches]
+            plan = GpuPlan([pack_ops(ops) for ops in planned])
             plan.tiles = masks
+            plan.placed = info.pop("placed", None)
             plan.l2p = None if l2p == list(range(self.n)) else l2p
             plan.model_ms = info["model_ms"]
             plan.layout_info = dict(info, passes_identity=own_identity, rewrite=dict(rewrite))
@@ -261,8 +273,11 @@ class SingleGpuEngine:
         self._zero = False
         self.last_passes = 0
         tiles = getattr(plan, "tiles", None) or [None] * len(plan)
-        for ops, masks in zip(plan, tiles):
-            if masks is not None and self.mode != "per-gate":
+        placed = getattr(plan, "placed", None) or [None] * len(plan)
+        for ops, masks, place in zip(plan, tiles, placed):
+            if masks is not None and place is not None and self.mode != "per-gate":
+                self.last_passes += self.state.apply_ops_placed(ops, masks, place)
+            elif masks is not None and self.mode != "per-gate":
                 self.last_passes += self.state.apply_ops_tiled(ops, masks)
             else:
                 self.last_passes += self.state.apply_ops(ops, fused=self.mode != "per-gate")
@@ -469,14 +484,19 @@ def _count_passes(n: int, batches, layouts: np.ndarray, threads: int) -> np.ndar
 
 
 def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 20260504, n_finalists: int = 4,
-                       all_finalists: bool = False, beam: int = 0):
+                       all_finalists: bool = False, beam: int = 0, engine_costs=None, priced_batches=None):
     """(l2p, tile masks per batch on the chosen index bits, info) for the op lists `batches` (logical qubits).  The three
     qubits on the line bits belong to every tile, so they decide how many passes a plan needs; which index bits the OTHER
     qubits live on does not (a relabelling of the bits >= 3 maps every valid pass sequence to a valid one).  So: for the
     identity and `n_candidates` random line-qubit triples the library's searching pass builder (qsim_plan_search, beam
     width `beam`, 0 = its default) plans the batches, in parallel on the host; the triples that need the fewest passes
     are kept and their other qubits placed by the tile-cost model (runner/tile_layout.py).  Host only.  all_finalists: the
-    list of up to n_finalists minimum-pass layouts, best model cost first (the engine may time them on the device)."""
+    list of up to n_finalists minimum-pass layouts, best model cost first (the engine may time them on the device).
+    engine_costs (the table of runner/engine_cost.py; None: pricing off): a pass is priced max(memory model of its tile,
+    engine time of its records); `priced_variant` then chooses between `batches` and `priced_batches` (the same lists
+    under rule (d) of the rewrite, optional) and places the ops that need no tile: info gains `planned` (the op lists to
+    run, on their index bits), `placed` (their placements, per batch) and the modelled split (`model_split_ms`), and the
+    finalists rank by that total instead of the memory model alone."""
     import os
     from concurrent.futures import ThreadPoolExecutor
 
@@ -528,9 +548,64 @@ def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 2026
                 "candidates_by_passes": {int(c): int((counts == c).sum()) for c in np.unique(counts)},
                 "passes_identity_searched": int(counts[0]), "beam": int(beam) if beam > 0 else "default",
                 "model_ms": (round(cost0, 3), round(cost1, 3))}
+        if engine_costs is not None:
+            def on_bits(lists):
+                return [[([l2p[q] for q in qs], U) for qs, U in ops] for ops in lists]
+            # info["planned"]: the op lists the plan runs (on their index bits), info["placed"]: their placements
+            info["planned"], info["placed"], info["model_split_ms"] = priced_variant(
+                n, on_bits(batches), None if priced_batches is None else on_bits(priced_batches), final_masks, engine_costs)
+            info["passes_chosen"] = info["model_split_ms"]["pass_count"]       # (a list under rule (d) may finish a pass early)
         out.append((l2p, final_masks, info))
-    out.sort(key=lambda r: r[2]["model_ms"][1])
+    out.sort(key=lambda r: r[2]["model_split_ms"]["passes"] if "model_split_ms" in r[2] else r[2]["model_ms"][1])
     return out if all_finalists else out[0]
+
+
+def pass_memory_us(n: int, masks) -> np.ndarray:
+    """Microseconds the tile-cost model (runner/tile_layout.py) gives every pass of the tiles `masks` without its gates, on
+    2^n amplitudes (the model's own state size scaled to n)."""
+    from quantum_simulations_amd.runner import tile_layout
+    model = tile_layout.model_for(n)
+    scale = 2.0 ** (n - min(tile_layout._load_models(), key=lambda k: (abs(k - n), k)))
+    return np.array([tile_layout.tile_cost(model, [b for b in range(tile_layout.LOW, n) if (int(m) >> b) & 1]) * scale * 1e3 for m in masks])
+
+
+def priced_variant(n: int, batches, priced_batches, masks, engine_costs) -> tuple:
+    """(batches kept, placement per batch, model split): the cheaper of the plans the SAME tiles `masks` (one mask array
+    per batch; the batches already on their index bits) give -- `batches` run first come, which is the plan with the
+    pricing off, against `priced_batches` (the same lists under rule (d) of the rewrite; may be None) and `batches`
+    themselves with their ops that need no tile placed by `planner.balance`.  A candidate is taken when it needs no more
+    passes than the unpriced plan and the model prices it lower, so a priced plan never has a pass more and is never
+    modelled dearer.  The split (milliseconds summed over the passes): `memory` (the tile model), `engine` (the records by
+    the table), `passes` (sum of max(memory, engine)), `passes_unpriced` (the same of the unpriced plan); `pass_count`,
+    `moved_ops` (placed later than first come) and `rule_d_ops` (ops rule (d) removed; 0: `batches` kept)."""
+    mems = [pass_memory_us(n, ms) for ms in masks]
+
+    def price(lists, place):
+        tot = {"memory": 0.0, "engine": 0.0, "passes": 0.0, "pass_count": 0, "moved_ops": 0}
+        placed = []
+        for ops, ms, mem in zip(lists, masks, mems):
+            if len(ops) < 2 or not len(ms):                 # (a single op is not planned: one pass, not priced)
+                placed.append(None)
+                tot["pass_count"] += len(ops)
+                continue
+            earliest, before, after = planner.balance(n, ops, ms, mem, engine_costs, place)
+            placed.append(earliest if earliest is not None and earliest.any() else None)
+            tot["memory"] += mem.sum() / 1e3
+            tot["engine"] += after.sum() / 1e3
+            tot["passes"] += np.maximum(mem, after).sum() / 1e3
+            tot["pass_count"] += planner.pass_count(n, ops, ms, placed[-1])
+            tot["moved_ops"] += 0 if placed[-1] is None else int((placed[-1] > 0).sum())
+        return tot, placed
+
+    def shown(tot, **more):
+        return dict({k: (round(float(v), 6) if isinstance(v, float) else int(v)) for k, v in tot.items()}, **more)
+    plain, none_placed = price(batches, False)
+    for lists in ([priced_batches] if priced_batches is not None else []) + [batches]:
+        tot, placed = price(lists, True)
+        if tot["pass_count"] <= plain["pass_count"] and tot["passes"] < plain["passes"]:
+            removed = sum(len(a) - len(b) for a, b in zip(batches, lists))
+            return lists, placed, shown(tot, passes_unpriced=round(float(plain["passes"]), 6), rule_d_ops=removed)
+    return batches, none_placed, shown(plain, passes_unpriced=round(float(plain["passes"]), 6), rule_d_ops=0)
 
 
 def _planned_tile_masks(n: int, ops) -> np.ndarray:
