@@ -18,6 +18,82 @@ static int check_qubit_list(qsim_chunk* c, int r, const int32_t* qubits, const v
   return QSIM_OK;
 }
 
+// the pair checks of a call on two chunks
+static int check_two_chunks(const qsim_chunk* a, const qsim_chunk* b, const char* what) {
+  if (a->k != b->k) return fail(QSIM_ERR_INVALID, "%s: chunks of %d and %d index bits", what, a->k, b->k);
+  if (a->device != b->device) return fail(QSIM_ERR_INVALID, "%s: chunks live on different devices", what);
+  if (a->stream != b->stream) return fail(QSIM_ERR_INVALID, "%s: chunks are bound to different streams", what);
+  return QSIM_OK;
+}
+
+// The checks of the four Pauli-string calls, in this order: the chunks, n, null arguments, the pair (a one-chunk call
+// passes its chunk twice: the pair checks then hold trivially), pending parts, then term by term locality and, where the
+// call has a value per term (`value`: what it is called), that it is finite.  `noun`: "term" or "rotation".
+static int check_pauli_call(const qsim_chunk* a, const qsim_chunk* b, int n, const uint64_t* x_masks, const uint64_t* z_masks,
+                            const double* values, const char* value, const void* out, const int* n_passes, const char* noun,
+                            const char* what) {
+  int rc = check_chunk(a, what);
+  if (rc || (rc = check_chunk(b, what))) return rc;
+  if (n < 0) return fail(QSIM_ERR_INVALID, "%s: %s = %d", what, std::strcmp(noun, "term") ? "n" : "n_terms", n);
+  if (!n_passes || (n > 0 && (!x_masks || !z_masks || !out || (value && !values))))
+    return fail(QSIM_ERR_INVALID, "%s: null argument", what);
+  if ((rc = check_two_chunks(a, b, what)) || (rc = require_no_parts(a, what)) || (rc = require_no_parts(b, what))) return rc;
+  const u64 all = (1ull << a->k) - 1;
+  for (int t = 0; t < n; ++t) {
+    if ((x_masks[t] | z_masks[t]) & ~all)
+      return fail(QSIM_ERR_NONLOCAL, "%s: %s %d acts on index bit %d >= log2(chunk_size)=%d", what, noun, t,
+                  63 - __builtin_clzll((x_masks[t] | z_masks[t]) & ~all), a->k);
+    if (value && !std::isfinite(values[t])) return fail(QSIM_ERR_INVALID, "%s: %s of %s %d is not finite", what, value, noun, t);
+  }
+  return QSIM_OK;
+}
+
+// qsim_plan_expectation and qsim_plan_pauli_rotations: the plan into the caller's arrays
+static int plan_pauli_out(bool ordered, int k, int n, const uint64_t* x_masks, int32_t* pass_of, uint64_t* tile_masks, int* n_passes) {
+  if (!n_passes || (n > 0 && (!pass_of || !tile_masks)))
+    return fail(QSIM_ERR_INVALID, "%s: null argument", ordered ? "qsim_plan_pauli_rotations" : "qsim_plan_expectation");
+  PauliPlan p;
+  const int rc = plan_pauli(ordered, k, n, x_masks, &p);
+  if (rc) return rc;
+  for (int t = 0; t < n; ++t) pass_of[t] = p.pass_of[(size_t)t];
+  for (size_t q = 0; q < p.tile.size(); ++q) tile_masks[q] = p.tile[q];
+  *n_passes = (int)p.tile.size();
+  return QSIM_OK;
+}
+
+// What qsim_expectation_pauli (width 1: a double per term) and qsim_overlap_pauli (width 2: re, im) share.  In the
+// chunk's workspace: the partials | the term table | the results.  Per pass launch(q, table entries of the pass,
+// partials, &rows) starts k_*_tile or k_*_wide with at most tile_wg or kExpMaxWg workgroups, and k_hist_sum adds the
+// rows in workgroup order into the per-term results, in pass order; one copy to the host at the end, back in call order.
+template <class Launch>
+static int pauli_reduce_call(qsim_chunk* c, const PauliPasses& pp, int width, unsigned tile_wg, Launch launch, double* out, int* n_passes) {
+  const u64 n = pp.slot.size(), w8 = sizeof(double) * (u64)width;
+  const int np = (int)pp.plan.tile.size();
+  int max_count = 1;
+  for (int q = 0; q < np; ++q) max_count = std::max(max_count, pp.plan.count[(size_t)q]);
+  const u64 table_off = w8 * std::max<u64>((u64)tile_wg * (u64)max_count, kExpMaxWg), out_off = table_off + ((pp.table.size() + 7) & ~7ull);
+  int rc = ensure_work(c, out_off + w8 * n);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->work);
+  double* partial = reinterpret_cast<double*>(base);
+  char* dev_table = base + table_off;
+  double* dev_out = reinterpret_cast<double*>(base + out_off);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(dev_table, pp.table.data(), pp.table.size(), hipMemcpyHostToDevice, c->stream));
+  for (int q = 0; q < np; ++q) {
+    const int first = pp.first[(size_t)q];
+    unsigned rows = 0;
+    if ((rc = launch(q, pp.at(dev_table, first), partial, &rows))) return rc;
+    if ((rc = sum_rows(c, partial, rows, width * pp.plan.count[(size_t)q], dev_out + width * first))) return rc;
+  }
+  std::vector<double> res((size_t)(width * n));
+  if ((rc = fetch_doubles(c, dev_out, width * n, res.data()))) return rc;
+  for (u64 t = 0; t < n; ++t)
+    for (int j = 0; j < width; ++j) out[width * t + j] = res[(size_t)(width * pp.slot[t] + j)];
+  *n_passes = np;
+  return QSIM_OK;
+}
+
 extern "C" {
 int qsim_norm2(qsim_chunk* c, double* out) {
   int rc = check_chunk(c, "qsim_norm2");
@@ -88,79 +164,23 @@ int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out)
   return fetch_doubles(c, dev_out, (u64)nbins, out);
 }
 
-// Pauli-sum expectation values (expect_kernels.h): the pass plan on the host, then per pass k_expect_tile (or
-// k_expect_wide) and k_hist_sum (the workgroup rows in workgroup order) into a device array of per-term results, in
-// pass order; one copy of n_terms doubles to the host at the end.
+// Pauli-sum expectation values (expect_kernels.h): the pass plan and the term table on the host (pauli_passes), then
+// per pass k_expect_tile (or k_expect_wide) and the rest of pauli_reduce_call, one double per term.
 int qsim_plan_expectation(int n_local_qubits, int n_terms, const uint64_t* x_masks, int32_t* pass_of_term, uint64_t* tile_masks, int* n_passes) {
-  if (!n_passes || (n_terms > 0 && (!pass_of_term || !tile_masks)))
-    return fail(QSIM_ERR_INVALID, "qsim_plan_expectation: null argument");
-  ExpPlan p;
-  const int rc = plan_expectation(n_local_qubits, n_terms, x_masks, &p);
-  if (rc) return rc;
-  for (int t = 0; t < n_terms; ++t) pass_of_term[t] = p.pass_of[(size_t)t];
-  for (size_t q = 0; q < p.tile.size(); ++q) tile_masks[q] = p.tile[q];
-  *n_passes = (int)p.tile.size();
-  return QSIM_OK;
+  return plan_pauli_out(false, n_local_qubits, n_terms, x_masks, pass_of_term, tile_masks, n_passes);
 }
 
 int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, const uint64_t* z_masks, double* out, int* n_passes) {
-  int rc = check_chunk(c, "qsim_expectation_pauli");
+  int rc = check_pauli_call(c, c, n_terms, x_masks, z_masks, nullptr, nullptr, out, n_passes, "term", "qsim_expectation_pauli");
   if (rc) return rc;
-  if (n_terms < 0) return fail(QSIM_ERR_INVALID, "qsim_expectation_pauli: n_terms = %d", n_terms);
-  if (!n_passes || (n_terms > 0 && (!x_masks || !z_masks || !out)))
-    return fail(QSIM_ERR_INVALID, "qsim_expectation_pauli: null argument");
-  if ((rc = require_no_parts(c, "qsim_expectation_pauli"))) return rc;
-  const int k = c->k;
-  const u64 all = (1ull << k) - 1;
-  for (int t = 0; t < n_terms; ++t)
-    if ((x_masks[t] | z_masks[t]) & ~all)
-      return fail(QSIM_ERR_NONLOCAL, "qsim_expectation_pauli: term %d acts on index bit %d >= log2(chunk_size)=%d", t,
-                  63 - __builtin_clzll((x_masks[t] | z_masks[t]) & ~all), k);
-  ExpPlan p;
-  if ((rc = plan_expectation(k, n_terms, x_masks, &p))) return rc;
+  PauliPasses pp;
+  if ((rc = pauli_passes(kPauliExpect, c->k, n_terms, x_masks, z_masks, nullptr, &pp))) return rc;
   *n_passes = 0;
   if (n_terms == 0) return QSIM_OK;
-  const int np = (int)p.tile.size();
-  // term tables of the tile passes (in pass order) and the result slot of every term
-  std::vector<int> first(np + 1, 0);
-  for (int q = 0; q < np; ++q) first[q + 1] = first[q] + p.count[q];
-  std::vector<int> fill(first.begin(), first.end() - 1), order((size_t)n_terms);
-  for (int t = 0; t < n_terms; ++t) order[(size_t)t] = fill[(size_t)p.pass_of[(size_t)t]]++;   // result slot of term t
-  std::vector<ExpTerm> table((size_t)n_terms);
-  std::memset(table.data(), 0, sizeof(ExpTerm) * table.size());
-  std::vector<int> wide_term((size_t)np, -1);       // the term of a wide-X pass
-  for (int t = 0; t < n_terms; ++t) {
-    const u64 T = p.tile[(size_t)p.pass_of[(size_t)t]];
-    const u64 x = x_masks[t], z = z_masks[t];
-    ExpTerm& e = table[(size_t)order[(size_t)t]];
-    exp_phase(x, z, &e.cr, &e.ci);
-    if (!T && x) {                                  // wide-X: the masks go as launch arguments
-      wide_term[(size_t)p.pass_of[(size_t)t]] = t;
-      continue;
-    }
-    e.xi = (unsigned)exp_pext(x, T);
-    e.zi = (unsigned)exp_pext(z & T, T);
-    e.zo = z & ~T;
-    e.h = e.xi ? 31 - __builtin_clz(e.xi) : -1;
-  }
-  const u64 n_tiles_max = 1ull << (k - std::min(k, kExpTileBits));
-  const unsigned grid_tile = (unsigned)std::min<u64>(n_tiles_max, kExpMaxWg);
-  int max_count = 1;
-  for (int q = 0; q < np; ++q) max_count = std::max(max_count, p.count[q]);
-  const u64 partial_bytes = sizeof(double) * (u64)kExpMaxWg * (u64)max_count;
-  const u64 table_off = partial_bytes, out_off = table_off + sizeof(ExpTerm) * (u64)n_terms;
-  if ((rc = ensure_work(c, out_off + sizeof(double) * (u64)n_terms))) return rc;
-  char* base = static_cast<char*>(c->work);
-  double* partial = reinterpret_cast<double*>(base);
-  ExpTerm* dev_table = reinterpret_cast<ExpTerm*>(base + table_off);
-  double* dev_out = reinterpret_cast<double*>(base + out_off);
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(dev_table, table.data(), sizeof(ExpTerm) * table.size(), hipMemcpyHostToDevice, c->stream));
   const bool nt = c->span_bytes > tuning().mall_bytes;
-  for (int q = 0; q < np; ++q) {
-    const u64 T = p.tile[(size_t)q];
-    if (wide_term[(size_t)q] >= 0) {
-      const int t = wide_term[(size_t)q];
+  const auto launch = [&](int q, const PauliTerm* terms, double* partial, unsigned* rows) {
+    if (pp.wide_term[(size_t)q] >= 0) {
+      const int t = pp.wide_term[(size_t)q];
       ExpWideArgs w;
       std::memset(&w, 0, sizeof w);
       w.amp = c->amp;
@@ -169,38 +189,26 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
       w.x = x_masks[t];
       w.z = z_masks[t];
       w.h = 63 - __builtin_clzll(w.x);
-      w.cr = table[(size_t)first[q]].cr;
-      w.ci = table[(size_t)first[q]].ci;
-      const unsigned grid = (unsigned)std::min<u64>(std::max<u64>(w.half / kBlock, 1), kExpMaxWg);
-      QSIM_WITH_NT(hipLaunchKernelGGL((k_expect_wide<NT>), dim3(grid), dim3(kBlock), 0, c->stream, w));
-      HIP_TRY(hipGetLastError());
-      if ((rc = sum_rows(c, partial, grid, 1, dev_out + first[q]))) return rc;
-      continue;
+      w.cr = pp.entry(pp.first[(size_t)q]).f0;
+      w.ci = pp.entry(pp.first[(size_t)q]).f1;
+      *rows = pauli_wide_grid(w.half);
+      QSIM_WITH_NT(hipLaunchKernelGGL((k_expect_wide<NT>), dim3(*rows), dim3(kBlock), 0, c->stream, w));
+    } else {
+      ExpArgs a;
+      std::memset(&a, 0, sizeof a);
+      a.amp = c->amp;
+      a.terms = terms;
+      a.partial = partial;
+      a.w = tile_walk(c->k, pp.plan.tile[(size_t)q]);
+      a.n_terms = pp.plan.count[(size_t)q];
+      a.slices = pauli_slices(a.n_terms);
+      *rows = (unsigned)std::min<u64>(a.w.n_tiles, kExpMaxWg);
+      QSIM_WITH_NT(hipLaunchKernelGGL((k_expect_tile<NT>), dim3(*rows), dim3(kBlock), 0, c->stream, a));
     }
-    ExpArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.amp = c->amp;
-    a.terms = dev_table + first[q];
-    a.partial = partial;
-    a.tb = __builtin_popcountll(T);
-    for (int b = 0, j = 0; b < k; ++b)
-      if ((T >> b) & 1) a.tile_bit[j++] = b;
-    a.outer_mask = all & ~T;
-    a.n_tiles = 1ull << (k - a.tb);
-    a.n_terms = p.count[q];
-    int slices = 1;
-    while (slices * 2 * a.n_terms <= kBlock) slices *= 2;
-    a.slices = slices;
-    const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, grid_tile);
-    QSIM_WITH_NT(hipLaunchKernelGGL((k_expect_tile<NT>), dim3(grid), dim3(kBlock), 0, c->stream, a));
     HIP_TRY(hipGetLastError());
-    if ((rc = sum_rows(c, partial, grid, a.n_terms, dev_out + first[q]))) return rc;
-  }
-  std::vector<double> res((size_t)n_terms);
-  if ((rc = fetch_doubles(c, dev_out, (u64)n_terms, res.data()))) return rc;
-  for (int t = 0; t < n_terms; ++t) out[t] = res[(size_t)order[(size_t)t]];
-  *n_passes = np;
-  return QSIM_OK;
+    return QSIM_OK;
+  };
+  return pauli_reduce_call(c, pp, 1, kExpMaxWg, launch, out, n_passes);
 }
 
 // Reduced density matrix (rdm_kernels.h): one read-only pass (k_rdm_small for r <= 3, k_rdm_mfma for r = 4..6), one

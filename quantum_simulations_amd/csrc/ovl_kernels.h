@@ -2,15 +2,15 @@
 // Part of the single translation unit qsim_hip.hip (included there after psum_kernels.h; not a standalone header).
 //
 //   <bra|P|ket> = i^ny sum_j conj(bra_j) s(j ^ x) ket_{j ^ x},   s(i) = (-1)^popcount(i & z),
-// complex; x = z = 0 gives <bra|ket>.  The passes are those of plan_expectation, the term table that of psum_kernels.h
-// with g = i^ny.
+// complex; x = z = 0 gives <bra|ket>.  Masks, ny and s(i) as in pauli_tile.h; the passes are those of
+// qsim_plan_expectation, and a term keeps g = i^ny in f0, f1 (kPauliSum without coefficients).
 //
-// Tile pass (k_ovl_tile): the structure of k_expect_tile -- threads dealt out to (term, slice) pairs, running sums kept
-// per thread across the tiles of the workgroup -- with TWO tiles in LDS, bra and ket, and two sums per term.  The sum
-// runs over ALL j of the slice, not over the half space of k_expect_tile: that pairing rests on <psi|P|psi> being real,
-// and the value here is complex.  i^ny and the outer sign are applied once per tile and term.  At the end the slices of
-// a term are added in slice order into the workgroup's row of partials [workgroup][2 * n_terms], and k_hist_sum adds the
-// rows in workgroup order: no atomics, every call gives the same bits.
+// Tile pass (k_ovl_tile): the tile walk of pauli_tile.h and the structure of k_expect_tile -- threads dealt out to
+// (term, slice) pairs, running sums kept per thread across the tiles of the workgroup -- with TWO tiles in LDS, bra and
+// ket, and two sums per term.  The sum runs over ALL j of the slice, not over the half space of k_expect_tile: that
+// pairing rests on <psi|P|psi> being real, and the value here is complex.  i^ny and the outer sign are applied once per
+// tile and term.  At the end the slices of a term are added in slice order into the workgroup's row of partials
+// [workgroup][2 * n_terms], and k_hist_sum adds the rows in workgroup order: no atomics, every call gives the same bits.
 // Two 11-bit tiles are 64 KiB of LDS: two workgroups per CU, so the grid is capped at kOvlMaxWg = 512.  (10-bit tiles
 // would keep four, but the planner's 11-bit tile masks would no longer fit a tile.)  What the pass costs next to
 // qsim_norm2 and qsim_expectation_pauli is measured in profiles/r18_hamiltonian_probe.json; the 10-bit form was not
@@ -23,35 +23,24 @@ constexpr int kOvlMaxWg = 512;                      // workgroups per tile launc
 struct OvlArgs {
   const double2* bra;
   const double2* ket;
-  const PauliTerm* terms;
+  const PauliTerm* terms;   // entries of kSumStride bytes
   double* partial;       // [workgroup][2 * n_terms]
-  u64 n_tiles;           // 2^(k - tb)
-  u64 outer_mask;        // physical bits outside the tile (outer index bit j <-> the j-th set bit)
-  int tile_bit[kExpTileBits];
-  int tb;                // tile bits
+  TileWalk w;
   int n_terms;           // <= kExpMaxTerms
   int slices;            // threads per term: a power of two, slices * min(n_terms, 256) <= 256
 };
 
 template <bool NT>
 __global__ __launch_bounds__(kBlock) void k_ovl_tile(const OvlArgs a) {
-  constexpr int kTile = 1 << kExpTileBits;
-  constexpr int kLoads = kTile / kBlock;
-  __shared__ double2 tile[2 * kTile];               // bra, then ket
+  __shared__ double2 tile[2 * kExpTile];            // bra, then ket
   double2* const tb_ = tile;
-  double2* const tk_ = tile + kTile;
-  const int S = 1 << a.tb;
+  double2* const tk_ = tile + kExpTile;
+  const int S = 1 << a.w.tb;
   const int tid = threadIdx.x;
   const int slice = tid & (a.slices - 1);
   const int per = kBlock / a.slices;                // terms per slot row
-  u64 off[kLoads];                                  // physical offsets of the amplitudes this thread loads (every tile)
-#pragma unroll
-  for (int it = 0; it < kLoads; ++it) {
-    const int j = tid + it * kBlock;
-    u64 o = 0;
-    for (int b = 0; b < a.tb; ++b) o |= (u64)((j >> b) & 1) << a.tile_bit[b];
-    off[it] = o;
-  }
+  u64 off[kExpLoads];
+  tile_offsets(a.w, off);
   PauliTerm tm[kExpSlots];
   bool live[kExpSlots];
   double accr[kExpSlots], acci[kExpSlots];
@@ -59,31 +48,22 @@ __global__ __launch_bounds__(kBlock) void k_ovl_tile(const OvlArgs a) {
   for (int s = 0; s < kExpSlots; ++s) {
     const int t = tid / a.slices + per * s;
     live[s] = t < a.n_terms;
-    if (live[s]) tm[s] = a.terms[t];
+    if (live[s]) term_load<kSumStride>(a.terms, t, &tm[s]);
     accr[s] = 0.0;
     acci[s] = 0.0;
   }
-  for (u64 o = blockIdx.x; o < a.n_tiles; o += gridDim.x) {
-    u64 base = 0;                                   // the outer index o deposited on the outer bits
-    {
-      u64 m = a.outer_mask, v = o;
-      while (m) {
-        const u64 low = m & (~m + 1);
-        if (v & 1) base |= low;
-        v >>= 1;
-        m ^= low;
-      }
-    }
-    double2 xb[kLoads], xk[kLoads];
+  for (u64 o = blockIdx.x; o < a.w.n_tiles; o += gridDim.x) {
+    const u64 base = tile_base(a.w.outer_mask, o);
+    double2 xb[kExpLoads], xk[kExpLoads];           // tile_load and tile_fill for both tiles at once, slot by slot
 #pragma unroll
-    for (int it = 0; it < kLoads; ++it)
+    for (int it = 0; it < kExpLoads; ++it)
       if (tid + it * kBlock < S) {
         xb[it] = ld_amp<NT>(a.bra + (base | off[it]));
         xk[it] = ld_amp<NT>(a.ket + (base | off[it]));
       }
     __syncthreads();                                // (the previous tiles are consumed)
 #pragma unroll
-    for (int it = 0; it < kLoads; ++it)
+    for (int it = 0; it < kExpLoads; ++it)
       if (tid + it * kBlock < S) {
         tb_[tid + it * kBlock] = xb[it];
         tk_[tid + it * kBlock] = xk[it];
@@ -101,13 +81,13 @@ __global__ __launch_bounds__(kBlock) void k_ovl_tile(const OvlArgs a) {
         if (__popc((unsigned)p & e.zi) & 1) { sr -= re; si -= im; } else { sr += re; si += im; }
       }
       const bool neg = __popcll(base & e.zo) & 1;   // the sign over the outer bits: one per tile and term
-      const double vr = fma(e.gr, sr, -(e.gi * si)), vi = fma(e.gr, si, e.gi * sr);
+      const double vr = fma(e.f0, sr, -(e.f1 * si)), vi = fma(e.f0, si, e.f1 * sr);
       accr[s] += neg ? -vr : vr;
       acci[s] += neg ? -vi : vi;
     }
   }
   __syncthreads();
-  double* red = reinterpret_cast<double*>(tile);    // [slot][re | im][thread]: 2 * kExpSlots * kBlock doubles (<= 4 kTile)
+  double* red = reinterpret_cast<double*>(tile);    // [slot][re | im][thread]: 2 * kExpSlots * kBlock doubles (<= 4 kExpTile)
 #pragma unroll
   for (int s = 0; s < kExpSlots; ++s) {
     red[(2 * s) * kBlock + tid] = accr[s];

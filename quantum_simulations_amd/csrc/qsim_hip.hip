@@ -56,6 +56,9 @@ typedef unsigned long long u64;
 #include "state_kernels.h"
 #include "readout_kernels.h"
 #include "dense_kernels.h"
+// pauli_tile.h first: the tile walk, the term record and the plan that the four Pauli-string families below share
+// (rdm_kernels.h takes its tile_base from it too)
+#include "pauli_tile.h"
 #include "expect_kernels.h"
 #include "rot_kernels.h"
 #include "psum_kernels.h"

@@ -83,22 +83,11 @@ __device__ __forceinline__ void rdm_thread_slots(const RdmArgs& a, u64* off, int
   }
 }
 
-__device__ __forceinline__ u64 rdm_tile_base(u64 outer_mask, u64 o) {   // the outer index o deposited on the outer bits
-  u64 base = 0, m = outer_mask;
-  while (m) {
-    const u64 low = m & (~m + 1);
-    if (o & 1) base |= low;
-    o >>= 1;
-    m ^= low;
-  }
-  return base;
-}
-
 template <bool NT>
 __device__ __forceinline__ void rdm_fetch(const RdmArgs& a, u64 o, const u64* off, double2* x) {   // tile o -> registers
   if (o >= a.n_tiles) return;
   const int S = 1 << a.tb;
-  const u64 base = rdm_tile_base(a.outer_mask, o);
+  const u64 base = tile_base(a.outer_mask, o);       // pauli_tile.h
 #pragma unroll
   for (int it = 0; it < kRdmLoads; ++it)
     if ((int)threadIdx.x + it * kBlock < S) x[it] = ld_amp<NT>(a.amp + (base | off[it]));

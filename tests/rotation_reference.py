@@ -24,6 +24,22 @@ def rotate_list(psi: np.ndarray, xs, zs, thetas) -> np.ndarray:
     return psi
 
 
+LONG_N = 13
+LONG_TILE = 0b1111110110111             # 11 tile bits, the line bits among them; bits 3 and 6 stay outside: four tiles
+
+
+def long_rotation_list(count: int = 1030, seed: int = 60):
+    """(x, z, thetas) of `count` rotations on LONG_N qubits that fit ONE tile: about a third Z-only strings, the others
+    with X/Y on one to three bits of LONG_TILE; Z anywhere, the outer bits 3 and 6 included.  More than the 1024 rotations
+    of a pass: the planner splits the list.  Shared by the device test and the check of this reference's own rounding."""
+    rng = np.random.default_rng(seed)
+    inside = [b for b in range(LONG_N) if (LONG_TILE >> b) & 1]
+    x = [0 if rng.random() < 1 / 3 else int(sum(1 << int(b) for b in rng.choice(inside, size=int(rng.integers(1, 4)), replace=False)))
+         for _ in range(count)]
+    z = rng.integers(0, 1 << LONG_N, count)
+    return np.array(x, dtype=np.uint64), z.astype(np.uint64), rng.uniform(-np.pi, np.pi, count)
+
+
 _H = np.array([[1, 1], [1, -1]], dtype=np.complex128) / np.sqrt(2.0)
 _SDG = np.diag([1.0, -1j]).astype(np.complex128)
 _CNOT = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, 1], [0, 0, 1, 0]], dtype=np.complex128)    # control = MSB

@@ -1,7 +1,7 @@
 """qsim_apply_pauli_rotations on an MI355X against the host reference tests/rotation_reference.rotate (R = exp(-i theta P)
 = cos(theta) I - i sin(theta) P, no factor 1/2) at 1e-12 absolute on unit-norm states, the project's bound for gate
-parity at n <= 14; at most 128 rotations per compared call, so rounding (a few 1e-16 per rotation) stays orders below
-the bound.  Every single-qubit Pauli, random strings of every weight, Z outside the tile, X on the top bits, pass
+parity at n <= 14; at most 128 rotations per compared call (1531 in the one test of the pass split at 1024), so rounding
+(a few 1e-16 per rotation) stays orders below the bound.  Every single-qubit Pauli, random strings of every weight, Z outside the tile, X on the top bits, pass
 breaks, strings wider than a tile; the order of non-commuting rotations; inverse, norm and bitwise repeatability; the
 gate path; views; the grid-stride loop (n = 22); the streaming instantiation; errors; the engine and the runner."""
 import ctypes as C
@@ -15,7 +15,7 @@ from quantum_simulations_amd.circuit.staging import permute_state
 from quantum_simulations_amd.kernel.device import DeviceChunk
 from quantum_simulations_amd.kernel.planner import plan_pauli_rotations
 from quantum_simulations_amd.observable import PauliSum
-from tests.rotation_reference import rotate_list, rotation_gates
+from tests.rotation_reference import LONG_N, LONG_TILE, long_rotation_list, rotate_list, rotation_gates
 
 pytestmark = pytest.mark.gpu
 
@@ -115,6 +115,38 @@ def test_rotations_are_applied_in_list_order():
             forward, backward = rotate_list(psi, x, z, th), rotate_list(psi, x[::-1], z[::-1], th[::-1])
             assert float(np.max(np.abs(got - forward))) < ATOL, name
             assert float(np.max(np.abs(got - backward))) > 1e-3, name
+    finally:
+        c.close()
+
+
+def test_more_rotations_than_a_pass_holds():
+    """1030 rotations inside one 11-bit tile of a 13-qubit state (four tiles): the planner splits the list at 1024, so the
+    second pass reads the term table at an offset of 1024 entries; then 1530 such rotations with a wide rotation at
+    position 500: three tile passes and one wide pass (500, 1, 1024, 6 rotations; table offsets 500, 501 and 1525), the
+    split at 1024 behind a wide pass.  Every amplitude against the reference at ATOL:
+    tests/test_pauli_rotation_cpu.py shows that the reference's own rounding over the longer list and back stays below
+    1e-13, so the bound tests the kernel."""
+    psi = _rand_state(LONG_N, 61)
+    x, z, th = long_rotation_list()
+    pass_of, tiles = plan_pauli_rotations(LONG_N, x)
+    assert [int(v) for v in np.bincount(pass_of)] == [1024, 6] and int(tiles[0]) == LONG_TILE and 0 not in [int(t) for t in tiles]
+    assert np.count_nonzero(x == 0) > 300 and np.count_nonzero(z & np.uint64(0b1001000)) > 500
+    full = (1 << LONG_N) - 1
+    xw, zw, thw = long_rotation_list(1530, seed=62)
+    xw, zw, thw = np.insert(xw, 500, np.uint64(full)), np.insert(zw, 500, np.uint64(0b1001001)), np.insert(thw, 500, 0.45)
+    pass_w, tiles_w = plan_pauli_rotations(LONG_N, xw)
+    assert [int(v) for v in np.bincount(pass_w)] == [500, 1, 1024, 6]
+    assert [int(t) != 0 for t in tiles_w] == [True, False, True, True]
+    c = DeviceChunk.empty(LONG_N)
+    try:
+        for what, (xs, zs, ts), passes in (("one tile", (x, z, th), 2), ("with a wide rotation", (xw, zw, thw), 4)):
+            c.upload(psi)
+            assert c.apply_pauli_rotations(xs, zs, ts) == passes == c.last_rotation_passes, what
+            got = c.download()
+            err = float(np.max(np.abs(got - rotate_list(psi, xs, zs, ts))))
+            print(f"{what}: {len(xs)} rotations in {passes} passes, max |got - want| = {err:.3e} (bound {ATOL:g})")
+            assert err < ATOL, (what, err)
+            assert float(np.max(np.abs(got - rotate_list(psi, xs[::-1], zs[::-1], ts[::-1])))) > 1e-3, what
     finally:
         c.close()
 

@@ -231,3 +231,20 @@ def test_to_physical_equals_permuting_the_state():
         evolution.to_physical([1 << 3], [0], [0, 1, 2])
     with pytest.raises(ValueError):
         evolution.to_physical([1], [0], [0, 0])
+
+
+def test_reference_rounding_over_the_long_list():
+    """The longer list of tests/test_gpu_pauli_rotation.py::test_more_rotations_than_a_pass_holds: 1530 rotations followed
+    by their inverses (3060 roundings) come back to the start within 1e-13, a tenth of the device test's bound.  The worst
+    case of 3 ulp per rotation on amplitudes of at most 0.05 adding up linearly is 3060 * 3 * 1.1e-16 * 0.05 = 5.0e-14.
+    (The reference applies rotations strictly one after the other, so there is no other association of it to compare.)"""
+    from tests.rotation_reference import LONG_N, long_rotation_list
+    x, z, th = long_rotation_list(1530, seed=62)
+    rng = np.random.default_rng(61)
+    psi = rng.standard_normal(1 << LONG_N) + 1j * rng.standard_normal(1 << LONG_N)
+    psi /= np.linalg.norm(psi)
+    assert float(np.max(np.abs(psi))) < 0.05
+    whole = rotate_list(psi, x, z, th)
+    back = float(np.max(np.abs(rotate_list(whole, x[::-1], z[::-1], -th[::-1]) - psi)))
+    print(f"reference, 1530 rotations and back: max |after - before| = {back:.3e} (bound 1e-13)")
+    assert back < 1e-13 and float(np.max(np.abs(whole - psi))) > 1e-3
