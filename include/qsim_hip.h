@@ -486,6 +486,28 @@ int qsim_apply_pauli_sum(qsim_chunk* dst, const qsim_chunk* src, int n_terms, co
  * QSIM_ERR_INVALID. */
 int qsim_overlap_pauli(qsim_chunk* ket, const qsim_chunk* bra, int n_terms, const uint64_t* x_masks,
                        const uint64_t* z_masks, double* out_re_im, int* n_passes);
+/* Vector algebra on whole chunks, ONE pass over them: a linear combination with complex coefficients (re, im pairs),
+ *   dst_j := a_d dst_j + sum_{s < n_src} a_s src_s,j      0 <= n_src <= 4,
+ * formed per amplitude in this fixed order: the complex product a_d dst_j first, then s = 0, 1, ... each added with
+ * fused multiply-adds in double (re: fma(a.re, x.re, fma(-a.im, x.im, acc.re)), im: fma(a.re, x.im, fma(a.im, x.re,
+ * acc.im))); and, of the NEW dst in the same pass,
+ *   dots[b] = <bra_b|dst> = sum_j conj(bra_b,j) dst_j     for b < n_bras, 0 <= n_bras <= 4 (2 * n_bras doubles),
+ *   *norm2  = sum_j |dst_j|^2                             if norm2 is not NULL.
+ * dst_coeff exactly 0 + 0i: dst is NOT read -- what it held does not matter, NaNs included -- and the sum starts at
+ * zero (n_src == 0 fills dst with zeros).  dst_coeff exactly 1 + 0i with n_src == 0: dst is NOT written, the call is a
+ * read-only multi-dot / norm (with nothing to reduce either, nothing is launched).  A bra on the memory of a source
+ * (the same pointer; all chunks of a call have one size) is loaded once.  Per-workgroup partials are summed in
+ * workgroup order on the device (no atomics): two calls give the same bits.  The workspace is dst's.  With n_bras == 0
+ * and norm2 == NULL the pass is only enqueued on dst's stream like the gate calls (no kernel is waited for); otherwise
+ * the call blocks until the 2 * n_bras (+ 1) doubles are on the host.  16 B per amplitude for every stream read (dst
+ * if it is read, the sources, the bras that are no source) and 16 B if dst is written.  Sources and bras are only read
+ * and may overlap each other freely.  A null required argument, n_src or n_bras out of range, a coefficient that is
+ * not finite, chunks of different size, device or stream, slab pieces pending on any chunk, and a source or a bra
+ * whose range overlaps dst's at all (the same chunk, a view inside, the same range through another handle) fail with
+ * QSIM_ERR_INVALID; nothing is changed then. */
+int qsim_lincomb(qsim_chunk* dst, const double dst_coeff[2], int n_src, const qsim_chunk* const* srcs,
+                 const double* coeffs_re_im, int n_bras, const qsim_chunk* const* bras, double* dots_re_im,
+                 double* norm2);
 /* Shot sampling of the full register: n_shots samples of the chunk-local index from |amp|^2 / total.  randnums[s] in
  * [0, 1) is the caller's uniform for shot s (the caller owns the generator); out_indices[s] is the smallest i with
  * cdf(i) > randnums[s] * total in the device's fixed summation order; results come back in the order of randnums.  An

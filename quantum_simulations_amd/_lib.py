@@ -121,6 +121,7 @@ SIGNATURES = {
     "qsim_plan_pauli_rotations": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_apply_pauli_sum": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_overlap_pauli": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
+    "qsim_lincomb": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     "qsim_sample": (C.c_int, [_P, C.c_uint64, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "qsim_sample_locate": (C.c_int, [C.c_uint64, _P, C.c_uint64, _P, _P, _P]),
     "qsim_sample_block_bits": (C.c_int, []),

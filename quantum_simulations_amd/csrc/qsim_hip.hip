@@ -63,6 +63,7 @@ typedef unsigned long long u64;
 #include "rot_kernels.h"
 #include "psum_kernels.h"
 #include "ovl_kernels.h"
+#include "lincomb_kernels.h"
 #include "rdm_kernels.h"
 #include "sample_kernels.h"
 #include "comm_rccl.h"
@@ -72,6 +73,7 @@ typedef unsigned long long u64;
 #include "abi_readout.h"
 #include "abi_rotation.h"
 #include "abi_twostate.h"
+#include "abi_lincomb.h"
 #include "abi_chunk.h"
 #include "abi_gates.h"
 #include "abi_plan.h"

@@ -242,6 +242,30 @@ class DeviceChunk:
         """<bra|self>, unnormalised: the identity string of `overlap_pauli`."""
         return complex(self.overlap_pauli(bra, [0], [0])[0])
 
+    def lincomb(self, dst_coeff, srcs=(), coeffs=(), bras=(), want_norm2: bool = False) -> tuple:
+        """self := dst_coeff self + sum_s coeffs[s] srcs[s] (complex coefficients, at most 4 sources, added in list
+        order) and, of the NEW self in the same pass, dots[b] = <bras[b]|self> (at most 4 bras) and with `want_norm2`
+        sum |self|^2 (qsim_lincomb: one streaming pass, a fixed summation order -- two calls give the same bits).
+        dst_coeff == 0: what self held does not matter; dst_coeff == 1 without sources: self is not written (a
+        read-only multi-dot / norm).  Sources and bras are only read and may not overlap self.  Without bras and norm the
+        pass is only enqueued on the chunk's stream.  Returns (dots: complex128 array, norm2: float or None)."""
+        srcs, bras = list(srcs), list(bras)
+        co = np.ascontiguousarray(coeffs, dtype=np.complex128).reshape(-1)
+        if co.size != len(srcs):
+            raise ValueError(f"lincomb: {len(srcs)} sources, {co.size} coefficients")
+        dc = np.array([complex(dst_coeff)], dtype=np.complex128)
+        src_h = (C.c_void_p * max(len(srcs), 1))(*[s._h.value for s in srcs])
+        bra_h = (C.c_void_p * max(len(bras), 1))(*[b._h.value for b in bras])
+        dots = np.empty(len(bras), dtype=np.complex128)
+        norm2 = C.c_double(0.0)
+        _lib.check(_lib.load().qsim_lincomb(self._h, _lib.ptr(dc), len(srcs), src_h, _lib.ptr(co), len(bras), bra_h, _lib.ptr(dots),
+                                            C.byref(norm2) if want_norm2 else None))
+        return dots, (norm2.value if want_norm2 else None)
+
+    def dot(self, bra: "DeviceChunk") -> complex:
+        """<bra|self>, unnormalised: one read-only streaming pass over both chunks (`lincomb`); `bra` may not overlap self."""
+        return complex(self.lincomb(1.0, bras=[bra])[0][0])
+
     # ---- sync / reductions / timing -------------------------------------------------
     def apply_ops_io(self, ops, src=None, dst=None, parts: int = 0, src_parts: int = 0, tiles=None) -> int:
         """`apply_ops` with a re-layout fused into its ends (qsim_apply_ops_io): `src` = (chunk, bits): the state

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from quantum_simulations_amd import evolution, hamiltonian, readout
+from quantum_simulations_amd import evolution, hamiltonian, krylov, readout
 from quantum_simulations_amd.circuit.fusion import batch_levels
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.kernel import gates as gate_table, planner
@@ -154,6 +154,33 @@ class SingleGpuEngine:
         out = hamiltonian.adjoint_gradient(self.state, self._work_chunk(), self.l2p, rotations, obs)
         self._zero = False
         return out
+
+    def _with_krylov_chunks(self, m: int, call):
+        """call(work) with `m` chunks of the state's size that live for the call only (everything allocated so far is
+        closed when an allocation fails); `variance`'s second chunk is not touched."""
+        work = []
+        try:
+            for _ in range(max(int(m), 0)):
+                work.append(DeviceChunk.empty(self.n, self.state.device))
+            self._zero = False
+            return call(work)
+        finally:
+            for c in work:
+                c.close()
+
+    def ground_state(self, obs, m: int = 16, tol: float = 1e-8, max_restarts: int = 50) -> tuple:
+        """The lowest eigenpair of a Pauli sum over LOGICAL qubits by restarted Lanczos on the device
+        (`krylov.ground_state`), started from the CURRENT state, which must overlap the ground state
+        (`init_random_state` does) and is replaced by the normalised eigenvector estimate in the current layout.
+        m + 1 chunks of the state's size are alive during the call: m work chunks are allocated for it and freed.
+        Returns (energy, residual |H psi - E psi|, restarts, H applications)."""
+        return self._with_krylov_chunks(m, lambda work: krylov.ground_state(self.state, work, self.l2p, obs, m, tol, max_restarts))
+
+    def evolve_krylov(self, obs, t, m: int = 16, steps: int = 1) -> float:
+        """psi := exp(-i t H) psi to Krylov accuracy (`krylov.evolve`: `steps` steps of m Lanczos vectors each) for a
+        Pauli sum over LOGICAL qubits, on the device through the current layout; t = -i tau gives exp(-tau H) psi,
+        unnormalised.  m work chunks are allocated for the call and freed.  Returns the a-posteriori error estimate."""
+        return self._with_krylov_chunks(m, lambda work: krylov.evolve(self.state, work, self.l2p, obs, t, m, steps))
 
     def reduced_density_matrix(self, qubits) -> np.ndarray:
         """Reduced density matrix (unnormalised, complex128 (2^r, 2^r)) of 1 to 6 LOGICAL qubits, bit j of a row or

@@ -23,7 +23,7 @@ from pathlib import Path
 
 import numpy as np
 
-from quantum_simulations_amd import evolution, hamiltonian, readout
+from quantum_simulations_amd import evolution, hamiltonian, krylov, readout
 from quantum_simulations_amd.circuit.fusion import batch_levels, split_by_locality
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.circuit.staging import atlas_stages, permute_state
@@ -338,6 +338,32 @@ def gradient(buf: HbmStateBuffer, rotations, obs) -> tuple:
         return hamiltonian.adjoint_gradient(buf.state, work, getattr(buf, "log_to_phys", None) or None, rotations, obs)
     finally:
         work.close()
+
+
+def _with_krylov_chunks(buf: HbmStateBuffer, m: int, call):
+    """call(work, l2p) with `m` chunks of the state's size, allocated for the call and closed."""
+    work = []
+    try:
+        for _ in range(max(int(m), 0)):
+            work.append(DeviceChunk.empty(buf.state.k, buf.state.device))
+        return call(work, getattr(buf, "log_to_phys", None) or None)
+    finally:
+        for c in work:
+            c.close()
+
+
+def ground_state(buf: HbmStateBuffer, obs, m: int = 16, tol: float = 1e-8, max_restarts: int = 50) -> tuple:
+    """The lowest eigenpair of a Pauli sum over LOGICAL qubits by restarted Lanczos (`krylov.ground_state`), started from
+    the final state of `run` and left there, normalised, in the staging layout `buf.log_to_phys`; m work chunks of the
+    state's size are allocated for the call and closed.  Returns (energy, residual, restarts, H applications)."""
+    return _with_krylov_chunks(buf, m, lambda work, l2p: krylov.ground_state(buf.state, work, l2p, obs, m, tol, max_restarts))
+
+
+def evolve_krylov(buf: HbmStateBuffer, obs, t, m: int = 16, steps: int = 1) -> float:
+    """exp(-i t H) applied to the final state of `run` to Krylov accuracy (`krylov.evolve`; t = -i tau: exp(-tau H),
+    unnormalised) for a Pauli sum over LOGICAL qubits, on the device through the staging layout `buf.log_to_phys`; m work
+    chunks of the state's size are allocated for the call and closed.  Returns the a-posteriori error estimate."""
+    return _with_krylov_chunks(buf, m, lambda work, l2p: krylov.evolve(buf.state, work, l2p, obs, t, m, steps))
 
 
 def reduced_density_matrix(buf: HbmStateBuffer, qubits) -> np.ndarray:
