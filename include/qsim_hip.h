@@ -450,6 +450,26 @@ int qsim_plan_expectation(int n_local_qubits, int n_terms, const uint64_t* x_mas
  * finite or a null argument with QSIM_ERR_INVALID; nothing is changed then. */
 int qsim_apply_pauli_rotations(qsim_chunk* c, int n, const uint64_t* x_masks, const uint64_t* z_masks,
                                const double* thetas, int* n_passes);
+/* Diagonal Pauli sums D = sum_t coeffs[t] Z^{z_masks[t]}: z_masks[t] is a mask of physical local index bits (0: the
+ * identity), E(i) = sum_t coeffs[t] (-1)^popcount(i & z_masks[t]) the diagonal entry of D at index i.
+ *   qsim_apply_diagonal_phase:  psi_i *= cos(gamma E(i)) - i sin(gamma E(i)), that is psi := exp(-i gamma D) psi, in
+ *     place.  No factor 1/2: one Z-only rotation exp(-i theta Z^z) of qsim_apply_pauli_rotations is the term (z, theta)
+ *     with gamma = 1, and ANY number of them (they commute) is one call.
+ *   qsim_diagonal_moments:      out = {sum |psi_i|^2, sum |psi_i|^2 E(i), sum |psi_i|^2 E(i)^2}, unnormalised: <D> =
+ *     out[1] / out[0], <D^2> = out[2] / out[0].  Read-only.
+ * ONE pass over the chunk whatever n_terms is (32 B per amplitude for the phase, 16 B for the moments): per tile of 2^11
+ * contiguous amplitudes the terms are scattered into a spectrum of 2^11 doubles in LDS, an unscaled Walsh-Hadamard
+ * transform turns it into E over the tile, and E is evaluated in double (sin and cos on the device).  The terms are
+ * sorted by the part of z inside the tile (stable) and every sum runs in a fixed order that depends on the term list
+ * and the chunk size only -- no atomics, per-workgroup partials of the moments summed in workgroup order -- so two calls
+ * give the same bits.  At most 16384 terms per call; equal masks may repeat (their coefficients add).  The term tables
+ * go into the chunk's workspace.  The phase is enqueued on the chunk's stream like the gate calls (no kernel is waited
+ * for); the moments call blocks until out is written.  n_terms == 0: the phase launches nothing and leaves the chunk
+ * untouched, the moments are {norm2, 0, 0}.  A bit of z >= log2(chunk) fails with QSIM_ERR_NONLOCAL; a null argument,
+ * n_terms < 0 or > 16384, a coefficient or gamma that is not finite, and slab pieces pending on the chunk with
+ * QSIM_ERR_INVALID; nothing is changed then. */
+int qsim_apply_diagonal_phase(qsim_chunk* c, int n_terms, const uint64_t* z_masks, const double* coeffs, double gamma);
+int qsim_diagonal_moments(qsim_chunk* c, int n_terms, const uint64_t* z_masks, const double* coeffs, double out[3]);
 /* The pass plan of qsim_apply_pauli_rotations (pure function, no GPU), ORDER PRESERVING: pass_of[t] = the pass that
  * applies rotation t, non-decreasing in t; tile_masks[p] = the tile bits of pass p (they contain the line bits 0..2 and
  * the x of each of its rotations, min(n_local_qubits, 11) bits), 0 for a wide pass.  tile_masks needs room for n

@@ -1,0 +1,80 @@
+// abi_diagonal.h -- C ABI: diagonal Pauli sums D = sum_t c_t Z^{z_t} on a chunk: the phase exp(-i gamma D) in place and
+// the moments sum |psi|^2 (1, E, E^2) read-only, each ONE pass whatever the number of terms (diag_kernels.h).
+// Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
+
+// What the two calls share: the checks (the chunk, then check_diag_args, then pending parts), the tables of diag_plan.h
+// as one block in the chunk's workspace -- terms | pieces | joins, 16-byte records, then `extra` bytes for the caller --
+// and the launch arguments.  The block is copied from a vector of this call (hipMemcpyAsync from host memory that is
+// not pinned copies before it returns, as in qsim_apply_pauli_rotations).
+static int diag_prepare(qsim_chunk* c, int n_terms, const uint64_t* z_masks, const double* coeffs, const double* gamma, u64 extra,
+                        const char* what, DiagArgs* a, char** extra_at) {
+  int rc = check_chunk(c, what);
+  if (rc || (rc = check_diag_args(c->k, n_terms, z_masks, coeffs, gamma, what)) || (rc = require_no_parts(c, what))) return rc;
+  std::memset(a, 0, sizeof *a);
+  a->amp = c->amp;
+  a->tb = std::min(c->k, kExpTileBits);
+  a->n_tiles = 1ull << (c->k - a->tb);
+  if (n_terms == 0 && extra == 0) return QSIM_OK;   // (nothing will be launched)
+  DiagTable d;
+  diag_table(a->tb, n_terms, z_masks, coeffs, &d);
+  if (d.n_slots > kDiagMaxSlots) return fail(QSIM_ERR_INVALID, "internal: %s needs %d piece slots", what, d.n_slots);
+  static_assert(sizeof(DiagTerm) == 16 && sizeof(DiagPiece) == 16 && sizeof(DiagJoin) == 16, "16-byte records");
+  const u64 piece_off = 16 * d.terms.size(), join_off = piece_off + 16 * d.pieces.size(), extra_off = join_off + 16 * d.joins.size();
+  if ((rc = ensure_work(c, extra_off + extra))) return rc;
+  char* const base = static_cast<char*>(c->work);
+  HIP_TRY(hipSetDevice(c->device));
+  if (extra_off) {
+    std::vector<char> block((size_t)extra_off);
+    if (piece_off) std::memcpy(block.data(), d.terms.data(), (size_t)piece_off);
+    if (join_off > piece_off) std::memcpy(block.data() + piece_off, d.pieces.data(), (size_t)(join_off - piece_off));
+    if (extra_off > join_off) std::memcpy(block.data() + join_off, d.joins.data(), (size_t)(extra_off - join_off));
+    HIP_TRY(hipMemcpyAsync(base, block.data(), (size_t)extra_off, hipMemcpyHostToDevice, c->stream));
+  }
+  a->terms = reinterpret_cast<const DiagTerm*>(base);
+  a->pieces = reinterpret_cast<const DiagPiece*>(base + piece_off);
+  a->joins = reinterpret_cast<const DiagJoin*>(base + join_off);
+  a->n_pieces = (int)d.pieces.size();
+  a->n_joins = (int)d.joins.size();
+  *extra_at = base + extra_off;
+  return QSIM_OK;
+}
+
+extern "C" {
+int qsim_apply_diagonal_phase(qsim_chunk* c, int n_terms, const uint64_t* z_masks, const double* coeffs, double gamma) {
+  DiagArgs a;
+  char* extra = nullptr;
+  int rc = diag_prepare(c, n_terms, z_masks, coeffs, &gamma, 0, "qsim_apply_diagonal_phase", &a, &extra);
+  if (rc || n_terms == 0) return rc;
+  a.gamma = gamma;
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, kExpMaxWg);
+  ProfileScope prof(16, 32.0 * (double)amps(c), c->stream, nt);
+  QSIM_WITH_NT(hipLaunchKernelGGL((k_diag_tile<NT, kDiagPhase>), dim3(grid), dim3(kBlock), 0, c->stream, a));
+  HIP_TRY(hipGetLastError());
+  prof.done(c->stream);
+  return QSIM_OK;
+}
+
+int qsim_diagonal_moments(qsim_chunk* c, int n_terms, const uint64_t* z_masks, const double* coeffs, double out[3]) {
+  const char* const what = "qsim_diagonal_moments";
+  int rc = check_chunk(c, what);
+  if (rc) return rc;
+  if (!out) return fail(QSIM_ERR_INVALID, "%s: null argument", what);
+  DiagArgs a;
+  char* extra = nullptr;
+  const unsigned max_grid = kExpMaxWg;
+  if ((rc = diag_prepare(c, n_terms, z_masks, coeffs, nullptr, sizeof(double) * 3 * ((u64)max_grid + 1), what, &a, &extra))) return rc;
+  const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, max_grid);
+  a.partial = reinterpret_cast<double*>(extra);
+  double* const dev_out = a.partial + 3 * (u64)grid;
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  {
+    ProfileScope prof(16, 16.0 * (double)amps(c), c->stream, nt);
+    QSIM_WITH_NT(hipLaunchKernelGGL((k_diag_tile<NT, kDiagMoments>), dim3(grid), dim3(kBlock), 0, c->stream, a));
+    HIP_TRY(hipGetLastError());
+    prof.done(c->stream);
+  }
+  if ((rc = sum_rows(c, a.partial, grid, 3, dev_out))) return rc;
+  return fetch_doubles(c, dev_out, 3, out);
+}
+}  // extern "C"

@@ -1,0 +1,172 @@
+// diag_kernels.h -- diagonal Pauli sums D = sum_t c_t Z^{z_t}: the phase exp(-i gamma D) and the moments <D>, <D^2>
+// (qsim_apply_diagonal_phase, qsim_diagonal_moments).
+// Part of the single translation unit qsim_hip.hip (included there after rot_kernels.h; not a standalone header).
+//
+// E(i) = sum_t c_t (-1)^popcount(i & z_t) is the diagonal entry of D at index i.  D moves no amplitude, so a tile is the
+// 2^tb CONTIGUOUS amplitudes on the lowest tb = min(k, kExpTileBits) index bits (no TileWalk), base = o << tb.  With the
+// outer bits fixed,   E(base | j) = sum_m W[m] (-1)^popcount(j & m),   W[m] = sum_{t: zi_t = m} c_t (-1)^popcount(base & zo_t):
+// E over the tile is the Walsh-Hadamard transform of the sparse spectrum W (tables and summation order: diag_plan.h).
+// Per tile (k_diag_tile, one workgroup per tile in a grid-stride loop):
+//   1. the thread's kExpLoads amplitudes j = tid + it * kBlock are loaded into REGISTERS and stay there (tile_load's
+//      slots): the LDS of a workgroup is W (16 KiB) and the piece slots (8 KiB), 24 KiB against the 32 KiB tile of the
+//      other Pauli passes, so four workgroups per CU fit with room to spare, and the loads are in flight during 2. and 3.;
+//   2. W is built: a thread per piece (kDiagPiece terms in table order, one __popcll(base & zo) each), then a thread per
+//      join.  Pieces are dealt to LANES, so these table reads are per-lane loads (through the constant address space;
+//      consecutive lanes read consecutive pieces); only the launch arguments are wave-uniform.  No atomics;
+//   3. the transform, unscaled (it IS E), always over all kExpTileBits bits -- for a chunk of fewer bits W is zero
+//      above 2^tb and E(j) repeats -- in four rounds of register butterflies: bits 0-2, 3-5, 6-7 through LDS with a
+//      __syncthreads() between rounds, bits 8-10 on the thread's own slots tid + r * kBlock, which leaves E(j) in
+//      registers next to amplitude j.  The last round zeroes what it reads: W is clear for the next tile;
+//   4. phase:   psi_j *= cos(gamma E_j) - i sin(gamma E_j) (diag_sincos), stored back in place (tiles partition the
+//      index space);
+//      moments: p = |psi_j|^2 into the thread's running sums of p, p E, p E^2 over its slots and tiles; at the end lane
+//      tree -> waves in wave order -> the workgroup's row of partials; k_hist_sum adds the rows in workgroup order.
+// The cost per tile is T term reads, 11 add/sub stages and one sincos per amplitude: nearly independent of T
+// (profiles/r22_diagonal_probe.json).
+constexpr int kDiagPhase = 0, kDiagMoments = 1;
+
+struct DiagArgs {
+  double2* amp;
+  const DiagTerm* terms;
+  const DiagPiece* pieces;
+  const DiagJoin* joins;
+  double* partial;       // moments: [workgroup][3]
+  u64 n_tiles;           // 2^(k - tb)
+  double gamma;          // phase
+  int tb;                // tile bits: min(k, kExpTileBits)
+  int n_pieces, n_joins;
+};
+
+// the butterflies of NB stages over 2^NB values in registers
+template <int NB>
+__device__ __forceinline__ void diag_butterflies(double* v) {
+#pragma unroll
+  for (int s = 0; s < NB; ++s)
+#pragma unroll
+    for (int i = 0; i < (1 << NB); ++i)
+      if (!((i >> s) & 1)) {
+        const double p = v[i], q = v[i | (1 << s)];
+        v[i] = p + q;
+        v[i | (1 << s)] = p - q;
+      }
+}
+
+// stages B .. B + NB - 1 of the transform in LDS: the thread's kExpLoads entries as kExpLoads >> NB groups of 2^NB
+template <int B, int NB>
+__device__ __forceinline__ void diag_round(double* W) {
+  constexpr int G = kExpLoads >> NB;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int u = (int)threadIdx.x * G + g;
+    const int j0 = (u & ((1 << B) - 1)) | ((u >> B) << (B + NB));
+    double v[1 << NB];
+#pragma unroll
+    for (int r = 0; r < (1 << NB); ++r) v[r] = W[j0 | (r << B)];
+    diag_butterflies<NB>(v);
+#pragma unroll
+    for (int r = 0; r < (1 << NB); ++r) W[j0 | (r << B)] = v[r];
+  }
+}
+
+// cos(v), sin(v) for any finite v: the angle in turns, r = v / (2 pi) - rint(v / (2 pi)) with 1 / (2 pi) as a double-double
+// (the fma keeps the product exact before the subtraction, so |r| <= 1/2 carries an error of about 1 ulp for the
+// |v| of a cost layer), then sincospi(2 r), which has no large-argument path: with sincos(v) the kernel takes 140 VGPRs
+// and spills 18 of them at the 128 of four workgroups per CU, with this form 132 and 5.  k_diag_tile asks for the four
+// (amdgpu_waves_per_eu): left at 132 VGPRs and three workgroups per CU the phase pass measured 4 % slower at 8 terms
+// and 26 % slower at 4096 (profiles/r22_diagonal_ab.json).
+__device__ __forceinline__ void diag_sincos(double v, double* s, double* c) {
+  constexpr double kInv2PiHi = 0x1.45f306dc9c883p-3, kInv2PiLo = -0x1.6b01ec5417056p-57;
+  const double k = rint(v * kInv2PiHi);
+  const double r = fma(v, kInv2PiHi, -k) + v * kInv2PiLo;
+  sincospi(2.0 * r, s, c);
+}
+
+template <bool NT, int MODE>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_tile(const DiagArgs a) {
+  static_assert(kExpTileBits == 11 && kExpLoads == 8, "the rounds below are bits 0-2, 3-5, 6-7 and 8-10");
+  __shared__ double W[kExpTile];
+  __shared__ double slots[kDiagMaxSlots];
+  const int S = 1 << a.tb;
+  const int tid = threadIdx.x;
+  typedef __attribute__((address_space(4))) const DiagTerm cterm_t;
+  typedef __attribute__((address_space(4))) const DiagPiece cpiece_t;
+  typedef __attribute__((address_space(4))) const DiagJoin cjoin_t;
+  cterm_t* const terms = (cterm_t*)(unsigned long long)a.terms;
+  cpiece_t* const pieces = (cpiece_t*)(unsigned long long)a.pieces;
+  cjoin_t* const joins = (cjoin_t*)(unsigned long long)a.joins;
+#pragma unroll
+  for (int it = 0; it < kExpLoads; ++it) W[tid + it * kBlock] = 0.0;
+  double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+  for (u64 o = blockIdx.x; o < a.n_tiles; o += gridDim.x) {
+    const u64 base = o << a.tb;
+    double2 x[kExpLoads];
+#pragma unroll
+    for (int it = 0; it < kExpLoads; ++it)
+      x[it] = tid + it * kBlock < S ? ld_amp<NT>(a.amp + (base | (u64)(tid + it * kBlock))) : make_double2(0.0, 0.0);
+    __syncthreads();                                // W is zero: every thread is past the last round of the previous tile
+    for (int p = tid; p < a.n_pieces; p += kBlock) {
+      const int first = pieces[p].first, count = pieces[p].count, slot = pieces[p].slot;
+      const unsigned zi = pieces[p].zi;
+      double v = 0.0;
+      for (int i = 0; i < count; ++i) {
+        const double c = terms[first + i].c;
+        v += (__popcll(base & terms[first + i].zo) & 1) ? -c : c;
+      }
+      if (slot < 0) W[zi] = v;
+      else slots[slot] = v;
+    }
+    if (a.n_joins) {                                // (the same in every thread)
+      __syncthreads();
+      for (int q = tid; q < a.n_joins; q += kBlock) {
+        const int slot = joins[q].slot, count = joins[q].count;
+        double v = slots[slot];
+        for (int i = 1; i < count; ++i) v += slots[slot + i];
+        W[joins[q].zi] = v;
+      }
+    }
+    __syncthreads();
+    diag_round<0, 3>(W);
+    __syncthreads();
+    diag_round<3, 3>(W);
+    __syncthreads();
+    diag_round<6, 2>(W);
+    __syncthreads();
+    double e[kExpLoads];
+#pragma unroll
+    for (int it = 0; it < kExpLoads; ++it) {        // bits 8-10: the thread's own slots, read by nobody else
+      e[it] = W[tid + it * kBlock];
+      W[tid + it * kBlock] = 0.0;
+    }
+    diag_butterflies<3>(e);
+#pragma unroll
+    for (int it = 0; it < kExpLoads; ++it) {
+      if (MODE == kDiagPhase) {
+        double s, c;
+        diag_sincos(a.gamma * e[it], &s, &c);
+        if (tid + it * kBlock < S)
+          st_amp<NT>(a.amp + (base | (u64)(tid + it * kBlock)),
+                     make_double2(fma(x[it].x, c, x[it].y * s), fma(x[it].y, c, -(x[it].x * s))));
+        __builtin_amdgcn_sched_barrier(0);          // one slot at a time: interleaved they need more than 128 VGPRs
+      } else {
+        const double p = fma(x[it].x, x[it].x, x[it].y * x[it].y), pe = p * e[it];
+        m0 += p;
+        m1 += pe;
+        m2 = fma(pe, e[it], m2);
+      }
+    }
+  }
+  if (MODE == kDiagMoments) {
+    __shared__ double red[kBlock / 64][3];
+    const int lane = tid & 63, wave = tid >> 6;
+    m0 = wave_sum(m0);
+    m1 = wave_sum(m1);
+    m2 = wave_sum(m2);
+    if (lane == 0) { red[wave][0] = m0; red[wave][1] = m1; red[wave][2] = m2; }
+    __syncthreads();
+    if (tid < 3) {
+      double s = red[0][tid];
+      for (int w = 1; w < kBlock / 64; ++w) s += red[w][tid];
+      a.partial[(u64)blockIdx.x * 3 + tid] = s;
+    }
+  }
+}

@@ -61,6 +61,8 @@ typedef unsigned long long u64;
 #include "pauli_tile.h"
 #include "expect_kernels.h"
 #include "rot_kernels.h"
+#include "diag_plan.h"
+#include "diag_kernels.h"
 #include "psum_kernels.h"
 #include "ovl_kernels.h"
 #include "lincomb_kernels.h"
@@ -72,6 +74,7 @@ typedef unsigned long long u64;
 #include "abi_pending.h"
 #include "abi_readout.h"
 #include "abi_rotation.h"
+#include "abi_diagonal.h"
 #include "abi_twostate.h"
 #include "abi_lincomb.h"
 #include "abi_chunk.h"

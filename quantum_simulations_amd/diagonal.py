@@ -1,0 +1,113 @@
+"""Diagonal Pauli sums D = sum_t c_t Z^{z_t}: the phase exp(-i gamma D), the moments <D>, <D^2> and QAOA layers, each
+cost layer ONE pass over the state whatever the number of terms (qsim_apply_diagonal_phase, qsim_diagonal_moments).
+
+Convention as in `evolution`: NO factor 1/2.  exp(-i gamma D) multiplies amplitude i by exp(-i gamma E(i)), E(i) =
+sum_t c_t (-1)^popcount(i & z_t); a Z-only rotation `evolution.rotation("Z0 Z1", theta)` is the term (z, theta) with gamma
+= 1, and all Z-only strings commute, so a whole list of them is one call.
+
+    diagonal_part(obs)                        -> (z, coeffs) over LOGICAL qubits; ValueError if a term carries X or Y
+    split(obs)                                -> (the Z-only terms, the rest) as two PauliSums
+    apply_phase(chunk, l2p, obs, gamma)       -> psi := exp(-i gamma D) psi through the layout
+    moments(chunk, l2p, obs)                  -> (<D>, <D^2> - <D>^2) of the normalised state, one read-only pass
+    qaoa(chunk, l2p, cost, gammas, betas)     -> alternating cost and mixer layers; the HBM passes made
+
+Everything here is host bookkeeping on small arrays; the amplitudes are touched by the device only.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from quantum_simulations_amd import evolution
+from quantum_simulations_amd.observable import PauliSum
+
+
+def _as_sum(obs, n_qubits=None) -> PauliSum:
+    return obs if isinstance(obs, PauliSum) else PauliSum(obs, n_qubits=n_qubits)
+
+
+def _from_masks(x, z, coeffs, n_qubits: int) -> PauliSum:
+    terms = []
+    for xt, zt, c in zip(x, z, coeffs):
+        ops = {}
+        for q in range(max(int(xt), int(zt)).bit_length()):
+            bx, bz = (int(xt) >> q) & 1, (int(zt) >> q) & 1
+            if bx or bz:
+                ops[q] = ("Y" if bz else "X") if bx else "Z"
+        terms.append((float(c), ops))
+    return PauliSum(terms, n_qubits=n_qubits)
+
+
+def diagonal_part(obs) -> tuple[np.ndarray, np.ndarray]:
+    """(z, coeffs) of a Pauli sum whose every term is a product of Z (or the identity: z = 0), masks over LOGICAL
+    qubits as uint64; terms of equal mask are merged (their coefficients added, in order of first appearance).  A term
+    with an X or a Y raises ValueError."""
+    obs = _as_sum(obs)
+    acc: dict = {}
+    for t, (x, z, c) in enumerate(zip(obs.x, obs.z, obs.coeffs)):
+        if x:
+            raise ValueError(f"term {t} ({obs.labels()[t]}) is not diagonal: it carries X or Y")
+        acc[int(z)] = acc.get(int(z), 0.0) + float(c)
+    return np.array(list(acc.keys()), dtype=np.uint64), np.array(list(acc.values()), dtype=np.float64)
+
+
+def split(obs) -> tuple[PauliSum, PauliSum]:
+    """(diagonal, rest): the Z-only terms of a Pauli sum (the identity among them) and the terms with an X or a Y, each
+    in term order, on the same number of qubits."""
+    obs = _as_sum(obs)
+    diag = [t for t, x in enumerate(obs.x) if not x]
+    rest = [t for t, x in enumerate(obs.x) if x]
+    pick = lambda idx: _from_masks([obs.x[t] for t in idx], [obs.z[t] for t in idx], [obs.coeffs[t] for t in idx], obs.n_qubits)
+    return pick(diag), pick(rest)
+
+
+def _physical(chunk, l2p, obs) -> tuple[np.ndarray, np.ndarray]:
+    n = chunk.k if l2p is None else len(l2p)
+    z, co = diagonal_part(_as_sum(obs, n))
+    return evolution.to_physical(np.zeros_like(z), z, l2p)[1], co
+
+
+def apply_phase(chunk, l2p, obs, gamma) -> int:
+    """psi := exp(-i gamma D) psi for the diagonal Pauli sum D over LOGICAL qubits, on a chunk whose logical qubit q
+    lives on index bit l2p[q] (None: identity); the state does not move.  Returns the HBM passes made (1, or 0 for a
+    sum without terms)."""
+    gamma = float(gamma)
+    if not np.isfinite(gamma):
+        raise ValueError(f"gamma {gamma!r} is not finite")
+    z, co = _physical(chunk, l2p, obs)
+    chunk.apply_diagonal_phase(z, co, gamma)
+    return 1 if z.size else 0
+
+
+def moments(chunk, l2p, obs) -> tuple[float, float]:
+    """(<D>, <D^2> - <D>^2) of the diagonal Pauli sum D over LOGICAL qubits in the NORMALISED state (the three sums of
+    `DeviceChunk.diagonal_moments` divided by norm2), from one read-only pass."""
+    z, co = _physical(chunk, l2p, obs)
+    norm2, m1, m2 = chunk.diagonal_moments(z, co)
+    if not norm2 > 0.0:
+        raise ValueError(f"moments: sum |psi|^2 = {norm2}")
+    mean = m1 / norm2
+    return mean, m2 / norm2 - mean * mean
+
+
+def qaoa(chunk, l2p, cost, gammas, betas) -> int:
+    """The QAOA circuit  prod_l [ exp(-i betas[l] sum_q X_q) exp(-i gammas[l] C) ]  applied to the chunk, layer 0 first:
+    per layer one cost phase (`apply_phase`, one pass) and then the mixer exp(-i beta X_q) on every qubit through
+    `DeviceChunk.apply_pauli_rotations`.  NO factor 1/2 anywhere: the mixer on a qubit is the gate RX(2 beta), and a
+    cost term c Z_a Z_b contributes exp(-i gamma c Z_a Z_b) = RZZ(2 gamma c).  `cost`: a diagonal Pauli sum over LOGICAL
+    qubits.  The state does not move.  Returns the HBM passes made."""
+    gammas = np.asarray(gammas, dtype=np.float64).reshape(-1)
+    betas = np.asarray(betas, dtype=np.float64).reshape(-1)
+    if gammas.shape != betas.shape:
+        raise ValueError(f"qaoa: {gammas.size} gammas, {betas.size} betas")
+    if not (np.all(np.isfinite(gammas)) and np.all(np.isfinite(betas))):
+        raise ValueError("qaoa: an angle is not finite")
+    n = chunk.k if l2p is None else len(l2p)
+    z, co = _physical(chunk, l2p, cost)
+    mx = evolution.to_physical(np.array([1 << q for q in range(n)], dtype=np.uint64), np.zeros(n, dtype=np.uint64), l2p)[0]
+    mz = np.zeros(n, dtype=np.uint64)
+    passes = 0
+    for gamma, beta in zip(gammas, betas):
+        chunk.apply_diagonal_phase(z, co, float(gamma))
+        passes += 1 if z.size else 0
+        passes += chunk.apply_pauli_rotations(mx, mz, np.full(n, float(beta)))
+    return passes

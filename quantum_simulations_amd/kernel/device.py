@@ -209,6 +209,29 @@ class DeviceChunk:
         self.last_rotation_passes = passes.value
         return passes.value
 
+    def apply_diagonal_phase(self, z_masks, coeffs, gamma) -> None:
+        """psi := exp(-i gamma D) psi in place for D = sum_t coeffs[t] Z^{z_masks[t]}, the masks over PHYSICAL index bits
+        of this chunk (0: the identity): psi_i *= exp(-i gamma E(i)), E(i) = sum_t coeffs[t] (-1)^popcount(i & z_t).  No
+        factor 1/2.  ONE read-modify-write pass whatever the number of terms (at most 16384), enqueued on the chunk's
+        stream (qsim_apply_diagonal_phase); no terms: nothing is launched."""
+        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
+        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
+        if z.shape != co.shape:
+            raise ValueError(f"apply_diagonal_phase: {z.size} z masks, {co.size} coefficients")
+        _lib.check(_lib.load().qsim_apply_diagonal_phase(self._h, int(z.size), _lib.ptr(z), _lib.ptr(co), float(gamma)))
+
+    def diagonal_moments(self, z_masks, coeffs) -> tuple:
+        """(sum |psi_i|^2, sum |psi_i|^2 E(i), sum |psi_i|^2 E(i)^2), unnormalised, for the diagonal D of
+        `apply_diagonal_phase`: ONE read-only pass whatever the number of terms, a fixed summation order -- two calls give
+        the same bits (qsim_diagonal_moments).  No terms: (norm2, 0, 0)."""
+        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
+        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
+        if z.shape != co.shape:
+            raise ValueError(f"diagonal_moments: {z.size} z masks, {co.size} coefficients")
+        out = np.empty(3, dtype=np.float64)
+        _lib.check(_lib.load().qsim_diagonal_moments(self._h, int(z.size), _lib.ptr(z), _lib.ptr(co), _lib.ptr(out)))
+        return float(out[0]), float(out[1]), float(out[2])
+
     def apply_pauli_sum(self, src: "DeviceChunk", x_masks, z_masks, coeffs) -> int:
         """self := sum_t coeffs[t] P_t src, OUT OF PLACE (`self` is dst: what it held does not matter; `src` is only
         read and may not overlap it); P_t as masks of PHYSICAL index bits (x: X or Y, z: Z or Y), real finite

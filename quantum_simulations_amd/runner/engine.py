@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from quantum_simulations_amd import evolution, hamiltonian, krylov, readout
+from quantum_simulations_amd import diagonal, evolution, hamiltonian, krylov, readout
 from quantum_simulations_amd.circuit.fusion import batch_levels
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.kernel import gates as gate_table, planner
@@ -107,11 +107,33 @@ class SingleGpuEngine:
         self._zero = False
         return passes
 
-    def evolve(self, obs, t, steps: int = 1, order: int = 1) -> int:
+    def evolve(self, obs, t, steps: int = 1, order: int = 1, fuse_diagonal: bool = False) -> int:
         """exp(-i t H) psi by a product formula (`evolution.trotter_rotations`: order 1 or the symmetric order 2,
         `steps` steps) of the Pauli sum H over LOGICAL qubits, applied on the device through the current layout; the
-        state does not move.  Returns the HBM passes made."""
-        passes = evolution.evolve(self.state, self.l2p, obs, t, steps, order)
+        state does not move.  `fuse_diagonal`: runs of Z-only rotations go through one diagonal phase pass each
+        (`evolution.apply_rotations`).  Returns the HBM passes made."""
+        passes = evolution.evolve(self.state, self.l2p, obs, t, steps, order, fuse_diagonal)
+        self._zero = False
+        return passes
+
+    def apply_diagonal_phase(self, obs, gamma) -> int:
+        """psi := exp(-i gamma D) psi for a diagonal Pauli sum D (Z and identity only) over LOGICAL qubits: ONE pass on
+        the device whatever the number of terms, through the current layout; the state does not move.  No factor 1/2
+        (`diagonal.apply_phase`).  Returns the HBM passes made."""
+        passes = diagonal.apply_phase(self.state, self.l2p, obs, gamma)
+        self._zero = False
+        return passes
+
+    def diagonal_moments(self, obs) -> tuple:
+        """(<D>, <D^2> - <D>^2) of a diagonal Pauli sum over LOGICAL qubits in the normalised state, from one read-only
+        pass on the device through the current layout (`diagonal.moments`)."""
+        return diagonal.moments(self.state, self.l2p, obs)
+
+    def qaoa(self, cost, gammas, betas) -> int:
+        """QAOA layers on the current state: per layer exp(-i gamma_l C) for the diagonal cost C over LOGICAL qubits
+        (one pass), then exp(-i beta_l X_q) on every qubit; no factor 1/2 (`diagonal.qaoa`).  The state does not move.
+        Returns the HBM passes made."""
+        passes = diagonal.qaoa(self.state, self.l2p, cost, gammas, betas)
         self._zero = False
         return passes
 

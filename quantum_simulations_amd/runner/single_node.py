@@ -23,7 +23,7 @@ from pathlib import Path
 
 import numpy as np
 
-from quantum_simulations_amd import evolution, hamiltonian, krylov, readout
+from quantum_simulations_amd import diagonal, evolution, hamiltonian, krylov, readout
 from quantum_simulations_amd.circuit.fusion import batch_levels, split_by_locality
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.circuit.staging import atlas_stages, permute_state
@@ -310,11 +310,32 @@ def expectation(buf: HbmStateBuffer, obs) -> float:
     return readout.expectation(buf.state, getattr(buf, "log_to_phys", None) or None, obs)
 
 
-def evolve(buf: HbmStateBuffer, obs, t, steps: int = 1, order: int = 1) -> int:
+def evolve(buf: HbmStateBuffer, obs, t, steps: int = 1, order: int = 1, fuse_diagonal: bool = False) -> int:
     """exp(-i t H) applied to the final state of `run` by a product formula of Pauli rotations
     (`evolution.trotter_rotations`: order 1 or 2, `steps` steps; H a Pauli sum over LOGICAL qubits), on the device
-    through the staging layout `buf.log_to_phys` (nothing is downloaded or permuted).  Returns the HBM passes made."""
-    return evolution.evolve(buf.state, getattr(buf, "log_to_phys", None) or None, obs, t, steps, order)
+    through the staging layout `buf.log_to_phys` (nothing is downloaded or permuted).  `fuse_diagonal`: runs of Z-only
+    rotations go through one diagonal phase pass each (`evolution.apply_rotations`).  Returns the HBM passes made."""
+    return evolution.evolve(buf.state, getattr(buf, "log_to_phys", None) or None, obs, t, steps, order, fuse_diagonal)
+
+
+def apply_diagonal_phase(buf: HbmStateBuffer, obs, gamma) -> int:
+    """exp(-i gamma D) applied to the final state of `run` for a diagonal Pauli sum D (Z and identity only) over LOGICAL
+    qubits: ONE pass on the device whatever the number of terms, through the staging layout `buf.log_to_phys`; no factor
+    1/2 (`diagonal.apply_phase`).  Returns the HBM passes made."""
+    return diagonal.apply_phase(buf.state, getattr(buf, "log_to_phys", None) or None, obs, gamma)
+
+
+def diagonal_moments(buf: HbmStateBuffer, obs) -> tuple:
+    """(<D>, <D^2> - <D>^2) of a diagonal Pauli sum over LOGICAL qubits in the normalised final state of `run`, from one
+    read-only pass on the device through the staging layout (`diagonal.moments`)."""
+    return diagonal.moments(buf.state, getattr(buf, "log_to_phys", None) or None, obs)
+
+
+def qaoa(buf: HbmStateBuffer, cost, gammas, betas) -> int:
+    """QAOA layers applied to the final state of `run`: per layer exp(-i gamma_l C) for the diagonal cost C over LOGICAL
+    qubits (one pass), then exp(-i beta_l X_q) on every qubit, through the staging layout; no factor 1/2
+    (`diagonal.qaoa`).  Returns the HBM passes made."""
+    return diagonal.qaoa(buf.state, getattr(buf, "log_to_phys", None) or None, cost, gammas, betas)
 
 
 def variance(buf: HbmStateBuffer, obs) -> float:
