@@ -470,6 +470,22 @@ int qsim_apply_pauli_rotations(qsim_chunk* c, int n, const uint64_t* x_masks, co
  * QSIM_ERR_INVALID; nothing is changed then. */
 int qsim_apply_diagonal_phase(qsim_chunk* c, int n_terms, const uint64_t* z_masks, const double* coeffs, double gamma);
 int qsim_diagonal_moments(qsim_chunk* c, int n_terms, const uint64_t* z_masks, const double* coeffs, double out[3]);
+/* The same D as an OPERATOR between two chunks of the same size, device and stream, E(i) a multiplier instead of an angle:
+ *   qsim_apply_diagonal_sum:  dst_i = E(i) src_i (accumulate == 0) or dst_i += E(i) src_i (accumulate == 1; any other
+ *     value is QSIM_ERR_INVALID).  One pass, 32 B per amplitude when writing and 48 B when accumulating, enqueued on
+ *     dst's stream and not waited for; the tables go into dst's workspace.  dst may be exactly src (the same range)
+ *     when accumulate == 0, psi := D psi in place; the same range with accumulate == 1 and any partial overlap are
+ *     QSIM_ERR_INVALID.  n_terms == 0: dst := 0 when writing, dst untouched when accumulating (as qsim_apply_pauli_sum).
+ *   qsim_overlap_diagonal:    out = {Re, Im of sum_i conj(bra_i) ket_i, Re, Im of sum_i conj(bra_i) E(i) ket_i},
+ *     unnormalised.  One read-only pass, 32 B per amplitude; bra may be ket.  Per-workgroup rows of 4 partials summed
+ *     in workgroup order, no atomics: two calls give the same bits.  The tables and the rows go into ket's workspace;
+ *     the call blocks until out is written.  n_terms == 0: out[2] = out[3] = 0.
+ * Limits and errors as above, for both chunks: chunks of different size, device or stream, and slab pieces pending on
+ * either one, fail with QSIM_ERR_INVALID; nothing is changed then. */
+int qsim_apply_diagonal_sum(qsim_chunk* dst, const qsim_chunk* src, int n_terms, const uint64_t* z_masks, const double* coeffs,
+                            int accumulate);
+int qsim_overlap_diagonal(qsim_chunk* ket, const qsim_chunk* bra, int n_terms, const uint64_t* z_masks, const double* coeffs,
+                          double out[4]);
 /* The pass plan of qsim_apply_pauli_rotations (pure function, no GPU), ORDER PRESERVING: pass_of[t] = the pass that
  * applies rotation t, non-decreasing in t; tile_masks[p] = the tile bits of pass p (they contain the line bits 0..2 and
  * the x of each of its rotations, min(n_local_qubits, 11) bits), 0 for a wide pass.  tile_masks needs room for n

@@ -121,6 +121,8 @@ SIGNATURES = {
     "qsim_plan_pauli_rotations": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_apply_diagonal_phase": (C.c_int, [_P, C.c_int, _P, _P, C.c_double]),
     "qsim_diagonal_moments": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "qsim_apply_diagonal_sum": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
+    "qsim_overlap_diagonal": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "qsim_apply_pauli_sum": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_overlap_pauli": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_lincomb": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P]),

@@ -1,17 +1,21 @@
-// abi_diagonal.h -- C ABI: diagonal Pauli sums D = sum_t c_t Z^{z_t} on a chunk: the phase exp(-i gamma D) in place and
-// the moments sum |psi|^2 (1, E, E^2) read-only, each ONE pass whatever the number of terms (diag_kernels.h).
+// abi_diagonal.h -- C ABI: diagonal Pauli sums D = sum_t c_t Z^{z_t} on a chunk: the phase exp(-i gamma D) in place, the
+// moments sum |psi|^2 (1, E, E^2) read-only, and D as an operator between two chunks, dst (+)= D src and <bra|D|ket>,
+// each ONE pass whatever the number of terms (diag_kernels.h).
 // Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
 
-// What the two calls share: the checks (the chunk, then check_diag_args, then pending parts), the tables of diag_plan.h
+// What the four calls share: the checks (the chunk, then check_diag_args, then pending parts; with a second chunk
+// `other`, then that chunk, the pair checks of check_two_chunks and its pending parts), the tables of diag_plan.h
 // as one block in the chunk's workspace -- terms | pieces | joins, 16-byte records, then `extra` bytes for the caller --
 // and the launch arguments.  The block is copied from a vector of this call (hipMemcpyAsync from host memory that is
 // not pinned copies before it returns, as in qsim_apply_pauli_rotations).
-static int diag_prepare(qsim_chunk* c, int n_terms, const uint64_t* z_masks, const double* coeffs, const double* gamma, u64 extra,
-                        const char* what, DiagArgs* a, char** extra_at) {
+static int diag_prepare(qsim_chunk* c, const qsim_chunk* other, int n_terms, const uint64_t* z_masks, const double* coeffs,
+                        const double* gamma, u64 extra, const char* what, DiagArgs* a, char** extra_at) {
   int rc = check_chunk(c, what);
   if (rc || (rc = check_diag_args(c->k, n_terms, z_masks, coeffs, gamma, what)) || (rc = require_no_parts(c, what))) return rc;
+  if (other && ((rc = check_chunk(other, what)) || (rc = check_two_chunks(c, other, what)) || (rc = require_no_parts(other, what)))) return rc;
   std::memset(a, 0, sizeof *a);
   a->amp = c->amp;
+  a->other = other ? other->amp : nullptr;
   a->tb = std::min(c->k, kExpTileBits);
   a->n_tiles = 1ull << (c->k - a->tb);
   if (n_terms == 0 && extra == 0) return QSIM_OK;   // (nothing will be launched)
@@ -43,7 +47,7 @@ extern "C" {
 int qsim_apply_diagonal_phase(qsim_chunk* c, int n_terms, const uint64_t* z_masks, const double* coeffs, double gamma) {
   DiagArgs a;
   char* extra = nullptr;
-  int rc = diag_prepare(c, n_terms, z_masks, coeffs, &gamma, 0, "qsim_apply_diagonal_phase", &a, &extra);
+  int rc = diag_prepare(c, nullptr, n_terms, z_masks, coeffs, &gamma, 0, "qsim_apply_diagonal_phase", &a, &extra);
   if (rc || n_terms == 0) return rc;
   a.gamma = gamma;
   const bool nt = c->span_bytes > tuning().mall_bytes;
@@ -63,7 +67,7 @@ int qsim_diagonal_moments(qsim_chunk* c, int n_terms, const uint64_t* z_masks, c
   DiagArgs a;
   char* extra = nullptr;
   const unsigned max_grid = kExpMaxWg;
-  if ((rc = diag_prepare(c, n_terms, z_masks, coeffs, nullptr, sizeof(double) * 3 * ((u64)max_grid + 1), what, &a, &extra))) return rc;
+  if ((rc = diag_prepare(c, nullptr, n_terms, z_masks, coeffs, nullptr, sizeof(double) * 3 * ((u64)max_grid + 1), what, &a, &extra))) return rc;
   const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, max_grid);
   a.partial = reinterpret_cast<double*>(extra);
   double* const dev_out = a.partial + 3 * (u64)grid;
@@ -76,5 +80,60 @@ int qsim_diagonal_moments(qsim_chunk* c, int n_terms, const uint64_t* z_masks, c
   }
   if ((rc = sum_rows(c, a.partial, grid, 3, dev_out))) return rc;
   return fetch_doubles(c, dev_out, 3, out);
+}
+
+// dst = D src (accumulate 0) or dst += D src (1), one pass on dst's stream, not waited for; the tables in dst's workspace.
+int qsim_apply_diagonal_sum(qsim_chunk* dst, const qsim_chunk* src, int n_terms, const uint64_t* z_masks, const double* coeffs,
+                            int accumulate) {
+  const char* const what = "qsim_apply_diagonal_sum";
+  int rc = check_chunk(dst, what);
+  if (rc || (rc = check_chunk(src, what))) return rc;
+  if (accumulate != 0 && accumulate != 1) return fail(QSIM_ERR_INVALID, "%s: accumulate = %d, 0 or 1 expected", what, accumulate);
+  if (dst->amp < src->amp + amps(src) && src->amp < dst->amp + amps(dst) && (dst->amp != src->amp || dst->k != src->k || accumulate))
+    return fail(QSIM_ERR_INVALID, "%s: dst and src overlap (only dst = D dst over the same range, without accumulate, is in place)", what);
+  DiagArgs a;
+  char* extra = nullptr;
+  if ((rc = diag_prepare(dst, src, n_terms, z_masks, coeffs, nullptr, 0, what, &a, &extra))) return rc;
+  if (n_terms == 0) {
+    if (accumulate) return QSIM_OK;
+    HIP_TRY(hipSetDevice(dst->device));
+    hipLaunchKernelGGL(k_fill_zero, dim3(stream_grid(amps(dst))), dim3(kBlock), 0, dst->stream, dst->amp, amps(dst), 0);
+    HIP_TRY(hipGetLastError());
+    return QSIM_OK;
+  }
+  std::swap(a.amp, a.other);                        // the kernel loads a.amp = src first and writes a.other = dst
+  const bool nt = pair_streams(dst, src);
+  const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, kExpMaxWg);
+  ProfileScope prof(17, (accumulate ? 48.0 : 32.0) * (double)amps(dst), dst->stream, nt);
+  if (accumulate) QSIM_WITH_NT(hipLaunchKernelGGL((k_diag_apply<NT, true>), dim3(grid), dim3(kBlock), 0, dst->stream, a));
+  else QSIM_WITH_NT(hipLaunchKernelGGL((k_diag_apply<NT, false>), dim3(grid), dim3(kBlock), 0, dst->stream, a));
+  HIP_TRY(hipGetLastError());
+  prof.done(dst->stream);
+  return QSIM_OK;
+}
+
+// out = (re, im of <bra|ket>, re, im of <bra|D|ket>): one read-only pass, the tables and the partial rows in ket's workspace.
+int qsim_overlap_diagonal(qsim_chunk* ket, const qsim_chunk* bra, int n_terms, const uint64_t* z_masks, const double* coeffs,
+                          double out[4]) {
+  const char* const what = "qsim_overlap_diagonal";
+  int rc = check_chunk(ket, what);
+  if (rc || (rc = check_chunk(bra, what))) return rc;
+  if (!out) return fail(QSIM_ERR_INVALID, "%s: null argument", what);
+  DiagArgs a;
+  char* extra = nullptr;
+  const unsigned max_grid = kExpMaxWg;
+  if ((rc = diag_prepare(ket, bra, n_terms, z_masks, coeffs, nullptr, sizeof(double) * 4 * ((u64)max_grid + 1), what, &a, &extra))) return rc;
+  const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, max_grid);
+  a.partial = reinterpret_cast<double*>(extra);
+  double* const dev_out = a.partial + 4 * (u64)grid;
+  const bool nt = pair_streams(ket, bra);
+  {
+    ProfileScope prof(18, 32.0 * (double)amps(ket), ket->stream, nt);
+    QSIM_WITH_NT(hipLaunchKernelGGL((k_diag_overlap<NT>), dim3(grid), dim3(kBlock), 0, ket->stream, a));
+    HIP_TRY(hipGetLastError());
+    prof.done(ket->stream);
+  }
+  if ((rc = sum_rows(ket, a.partial, grid, 4, dev_out))) return rc;
+  return fetch_doubles(ket, dev_out, 4, out);
 }
 }  // extern "C"

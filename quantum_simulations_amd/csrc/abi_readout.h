@@ -26,6 +26,13 @@ static int check_two_chunks(const qsim_chunk* a, const qsim_chunk* b, const char
   return QSIM_OK;
 }
 
+// Do the two chunks' allocations together exceed the Infinity Cache?  (Views of one parent share its allocation.)
+static bool pair_streams(const qsim_chunk* a, const qsim_chunk* b) {
+  u64 bytes = a->span_bytes;
+  if (a->amp != b->amp && !(a->parent && a->parent == b->parent)) bytes += b->span_bytes;
+  return bytes > tuning().mall_bytes;
+}
+
 // The checks of the four Pauli-string calls, in this order: the chunks, n, null arguments, the pair (a one-chunk call
 // passes its chunk twice: the pair checks then hold trivially), pending parts, then term by term locality and, where the
 // call has a value per term (`value`: what it is called), that it is finite.  `noun`: "term" or "rotation".

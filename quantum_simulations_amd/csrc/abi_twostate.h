@@ -1,14 +1,7 @@
 // abi_twostate.h -- C ABI: what takes two chunks: a Pauli sum applied out of place (psum_kernels.h) and the matrix
 // elements of Pauli strings between two states (ovl_kernels.h).
 // Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
-// The argument checks are check_pauli_call's (abi_readout.h), with two chunks.
-
-// Do the two chunks' allocations together exceed the Infinity Cache?  (Views of one parent share its allocation.)
-static bool pair_streams(const qsim_chunk* a, const qsim_chunk* b) {
-  u64 bytes = a->span_bytes;
-  if (a->amp != b->amp && !(a->parent && a->parent == b->parent)) bytes += b->span_bytes;
-  return bytes > tuning().mall_bytes;
-}
+// The argument checks are check_pauli_call's and the cache policy is pair_streams' (abi_readout.h), with two chunks.
 
 extern "C" {
 // The plan of qsim_plan_expectation on the host, one term table per call in dst's workspace (terms in pass order), then

@@ -1,5 +1,6 @@
 // diag_kernels.h -- diagonal Pauli sums D = sum_t c_t Z^{z_t}: the phase exp(-i gamma D) and the moments <D>, <D^2>
-// (qsim_apply_diagonal_phase, qsim_diagonal_moments).
+// (qsim_apply_diagonal_phase, qsim_diagonal_moments), and D as an operator: dst (+)= D src and <bra|ket>, <bra|D|ket>
+// (qsim_apply_diagonal_sum, qsim_overlap_diagonal).
 // Part of the single translation unit qsim_hip.hip (included there after rot_kernels.h; not a standalone header).
 //
 // E(i) = sum_t c_t (-1)^popcount(i & z_t) is the diagonal entry of D at index i.  D moves no amplitude, so a tile is the
@@ -20,17 +21,22 @@
 //   4. phase:   psi_j *= cos(gamma E_j) - i sin(gamma E_j) (diag_sincos), stored back in place (tiles partition the
 //      index space);
 //      moments: p = |psi_j|^2 into the thread's running sums of p, p E, p E^2 over its slots and tiles; at the end lane
-//      tree -> waves in wave order -> the workgroup's row of partials; k_hist_sum adds the rows in workgroup order.
+//      tree -> waves in wave order -> the workgroup's row of partials; k_hist_sum adds the rows in workgroup order;
+//      sum (k_diag_apply):       dst_j = E_j src_j, or dst_j += E_j src_j: E is a multiplier, not an angle;
+//      overlap (k_diag_overlap): q = conj(bra_j) ket_j into running sums of q and q E_j (re, im), reduced like the moments.
+//      The second operand of these two (dst when accumulating, bra) is loaded AFTER the transform: its 8 double2 are
+//      not alive next to src / ket during the rounds.
 // The cost per tile is T term reads, 11 add/sub stages and one sincos per amplitude: nearly independent of T
 // (profiles/r22_diagonal_probe.json).
 constexpr int kDiagPhase = 0, kDiagMoments = 1;
 
 struct DiagArgs {
-  double2* amp;
+  double2* amp;          // phase, moments: the chunk; sum: src; overlap: ket -- loaded before the transform
+  double2* other;        // sum: dst; overlap: bra -- touched after the transform only
   const DiagTerm* terms;
   const DiagPiece* pieces;
   const DiagJoin* joins;
-  double* partial;       // moments: [workgroup][3]
+  double* partial;       // moments: [workgroup][3]; overlap: [workgroup][4]
   u64 n_tiles;           // 2^(k - tb)
   double gamma;          // phase
   int tb;                // tile bits: min(k, kExpTileBits)
@@ -70,8 +76,9 @@ __device__ __forceinline__ void diag_round(double* W) {
 
 // cos(v), sin(v) for any finite v: the angle in turns, r = v / (2 pi) - rint(v / (2 pi)) with 1 / (2 pi) as a double-double
 // (the fma keeps the product exact before the subtraction, so |r| <= 1/2 carries an error of about 1 ulp for the
-// |v| of a cost layer), then sincospi(2 r), which has no large-argument path: with sincos(v) the kernel takes 140 VGPRs
-// and spills 18 of them at the 128 of four workgroups per CU, with this form 132 and 5.  k_diag_tile asks for the four
+// |v| of a cost layer), then sincospi(2 r), which has no large-argument path: with sincos(v) the kernel took 140 VGPRs
+// and spilled 18 of them at the 128 of four workgroups per CU, with this form 132 and 5 (round 22; with the build of W
+// and the rounds in diag_energies the compiler now reports 128 and no spill).  k_diag_tile asks for the four
 // (amdgpu_waves_per_eu): left at 132 VGPRs and three workgroups per CU the phase pass measured 4 % slower at 8 terms
 // and 26 % slower at 4096 (profiles/r22_diagonal_ab.json).
 __device__ __forceinline__ void diag_sincos(double v, double* s, double* c) {
@@ -81,12 +88,10 @@ __device__ __forceinline__ void diag_sincos(double v, double* s, double* c) {
   sincospi(2.0 * r, s, c);
 }
 
-template <bool NT, int MODE>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_tile(const DiagArgs a) {
+// Steps 2 and 3 for the tile at `base`: E(base | (tid + it * kBlock)) into e[it].  W is zero on entry once every thread
+// is past the barrier at the top (the last round of the previous tile zeroed it), and zero again on return.
+__device__ __forceinline__ void diag_energies(const DiagArgs& a, u64 base, double* W, double* slots, double* e) {
   static_assert(kExpTileBits == 11 && kExpLoads == 8, "the rounds below are bits 0-2, 3-5, 6-7 and 8-10");
-  __shared__ double W[kExpTile];
-  __shared__ double slots[kDiagMaxSlots];
-  const int S = 1 << a.tb;
   const int tid = threadIdx.x;
   typedef __attribute__((address_space(4))) const DiagTerm cterm_t;
   typedef __attribute__((address_space(4))) const DiagPiece cpiece_t;
@@ -94,50 +99,65 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
   cterm_t* const terms = (cterm_t*)(unsigned long long)a.terms;
   cpiece_t* const pieces = (cpiece_t*)(unsigned long long)a.pieces;
   cjoin_t* const joins = (cjoin_t*)(unsigned long long)a.joins;
+  __syncthreads();                                  // W is zero: every thread is past the last round of the previous tile
+  for (int p = tid; p < a.n_pieces; p += kBlock) {
+    const int first = pieces[p].first, count = pieces[p].count, slot = pieces[p].slot;
+    const unsigned zi = pieces[p].zi;
+    double v = 0.0;
+    for (int i = 0; i < count; ++i) {
+      const double c = terms[first + i].c;
+      v += (__popcll(base & terms[first + i].zo) & 1) ? -c : c;
+    }
+    if (slot < 0) W[zi] = v;
+    else slots[slot] = v;
+  }
+  if (a.n_joins) {                                  // (the same in every thread)
+    __syncthreads();
+    for (int q = tid; q < a.n_joins; q += kBlock) {
+      const int slot = joins[q].slot, count = joins[q].count;
+      double v = slots[slot];
+      for (int i = 1; i < count; ++i) v += slots[slot + i];
+      W[joins[q].zi] = v;
+    }
+  }
+  __syncthreads();
+  diag_round<0, 3>(W);
+  __syncthreads();
+  diag_round<3, 3>(W);
+  __syncthreads();
+  diag_round<6, 2>(W);
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < kExpLoads; ++it) {          // bits 8-10: the thread's own slots, read by nobody else
+    e[it] = W[tid + it * kBlock];
+    W[tid + it * kBlock] = 0.0;
+  }
+  diag_butterflies<3>(e);
+}
+
+// step 1: the thread's slots of the tile at `base` (zero above the 2^tb amplitudes of a chunk smaller than a tile)
+template <bool NT>
+__device__ __forceinline__ void diag_load(const double2* amp, u64 base, int S, double2* x) {
+#pragma unroll
+  for (int it = 0; it < kExpLoads; ++it)
+    x[it] = (int)threadIdx.x + it * kBlock < S ? ld_amp<NT>(amp + (base | (u64)((int)threadIdx.x + it * kBlock))) : make_double2(0.0, 0.0);
+}
+
+template <bool NT, int MODE>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_tile(const DiagArgs a) {
+  __shared__ double W[kExpTile];
+  __shared__ double slots[kDiagMaxSlots];
+  const int S = 1 << a.tb;
+  const int tid = threadIdx.x;
 #pragma unroll
   for (int it = 0; it < kExpLoads; ++it) W[tid + it * kBlock] = 0.0;
   double m0 = 0.0, m1 = 0.0, m2 = 0.0;
   for (u64 o = blockIdx.x; o < a.n_tiles; o += gridDim.x) {
     const u64 base = o << a.tb;
     double2 x[kExpLoads];
-#pragma unroll
-    for (int it = 0; it < kExpLoads; ++it)
-      x[it] = tid + it * kBlock < S ? ld_amp<NT>(a.amp + (base | (u64)(tid + it * kBlock))) : make_double2(0.0, 0.0);
-    __syncthreads();                                // W is zero: every thread is past the last round of the previous tile
-    for (int p = tid; p < a.n_pieces; p += kBlock) {
-      const int first = pieces[p].first, count = pieces[p].count, slot = pieces[p].slot;
-      const unsigned zi = pieces[p].zi;
-      double v = 0.0;
-      for (int i = 0; i < count; ++i) {
-        const double c = terms[first + i].c;
-        v += (__popcll(base & terms[first + i].zo) & 1) ? -c : c;
-      }
-      if (slot < 0) W[zi] = v;
-      else slots[slot] = v;
-    }
-    if (a.n_joins) {                                // (the same in every thread)
-      __syncthreads();
-      for (int q = tid; q < a.n_joins; q += kBlock) {
-        const int slot = joins[q].slot, count = joins[q].count;
-        double v = slots[slot];
-        for (int i = 1; i < count; ++i) v += slots[slot + i];
-        W[joins[q].zi] = v;
-      }
-    }
-    __syncthreads();
-    diag_round<0, 3>(W);
-    __syncthreads();
-    diag_round<3, 3>(W);
-    __syncthreads();
-    diag_round<6, 2>(W);
-    __syncthreads();
+    diag_load<NT>(a.amp, base, S, x);
     double e[kExpLoads];
-#pragma unroll
-    for (int it = 0; it < kExpLoads; ++it) {        // bits 8-10: the thread's own slots, read by nobody else
-      e[it] = W[tid + it * kBlock];
-      W[tid + it * kBlock] = 0.0;
-    }
-    diag_butterflies<3>(e);
+    diag_energies(a, base, W, slots, e);
 #pragma unroll
     for (int it = 0; it < kExpLoads; ++it) {
       if (MODE == kDiagPhase) {
@@ -168,5 +188,77 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
       for (int w = 1; w < kBlock / 64; ++w) s += red[w][tid];
       a.partial[(u64)blockIdx.x * 3 + tid] = s;
     }
+  }
+}
+
+// dst_j = E_j src_j (ACC false) or dst_j += E_j src_j (ACC true) over contiguous tiles; a.amp = src, a.other = dst.  dst
+// may be src when writing: slot j is read and written by the same thread.  Compiler's resource usage (gfx950, both NT
+// forms alike): writing 98 VGPRs, accumulating 128, overlap 112; no spill, no scratch, four workgroups per CU each.
+template <bool NT, bool ACC>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_apply(const DiagArgs a) {
+  __shared__ double W[kExpTile];
+  __shared__ double slots[kDiagMaxSlots];
+  const int S = 1 << a.tb;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int it = 0; it < kExpLoads; ++it) W[tid + it * kBlock] = 0.0;
+  for (u64 o = blockIdx.x; o < a.n_tiles; o += gridDim.x) {
+    const u64 base = o << a.tb;
+    double2 x[kExpLoads];
+    diag_load<NT>(a.amp, base, S, x);
+    double e[kExpLoads];
+    diag_energies(a, base, W, slots, e);
+    double2 y[kExpLoads];
+    if (ACC) diag_load<NT>(a.other, base, S, y);
+#pragma unroll
+    for (int it = 0; it < kExpLoads; ++it) {
+      if (tid + it * kBlock >= S) continue;
+      const double2 v = ACC ? make_double2(fma(e[it], x[it].x, y[it].x), fma(e[it], x[it].y, y[it].y))
+                            : make_double2(e[it] * x[it].x, e[it] * x[it].y);
+      st_amp<NT>(a.other + (base | (u64)(tid + it * kBlock)), v);
+    }
+  }
+}
+
+// sum_j conj(bra_j) ket_j and sum_j conj(bra_j) E_j ket_j, (re, im) each: a.amp = ket, a.other = bra (it may be ket);
+// the workgroup's row of 4 partials into a.partial, by the reduction of the moments.
+template <bool NT>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_overlap(const DiagArgs a) {
+  __shared__ double W[kExpTile];
+  __shared__ double slots[kDiagMaxSlots];
+  __shared__ double red[kBlock / 64][4];
+  const int S = 1 << a.tb;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int it = 0; it < kExpLoads; ++it) W[tid + it * kBlock] = 0.0;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (u64 o = blockIdx.x; o < a.n_tiles; o += gridDim.x) {
+    const u64 base = o << a.tb;
+    double2 x[kExpLoads];
+    diag_load<NT>(a.amp, base, S, x);
+    double e[kExpLoads];
+    diag_energies(a, base, W, slots, e);
+    double2 b[kExpLoads];
+    diag_load<NT>(a.other, base, S, b);
+#pragma unroll
+    for (int it = 0; it < kExpLoads; ++it) {        // (slots above S hold zeros in x and b)
+      const double re = fma(b[it].x, x[it].x, b[it].y * x[it].y), im = fma(b[it].x, x[it].y, -(b[it].y * x[it].x));
+      s[0] += re;
+      s[1] += im;
+      s[2] = fma(re, e[it], s[2]);
+      s[3] = fma(im, e[it], s[3]);
+    }
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    s[i] = wave_sum(s[i]);
+    if (lane == 0) red[wave][i] = s[i];
+  }
+  __syncthreads();
+  if (tid < 4) {
+    double v = red[0][tid];
+    for (int w = 1; w < kBlock / 64; ++w) v += red[w][tid];
+    a.partial[(u64)blockIdx.x * 4 + tid] = v;
   }
 }

@@ -1,5 +1,6 @@
-"""Diagonal Pauli sums D = sum_t c_t Z^{z_t}: the phase exp(-i gamma D), the moments <D>, <D^2> and QAOA layers, each
-cost layer ONE pass over the state whatever the number of terms (qsim_apply_diagonal_phase, qsim_diagonal_moments).
+"""Diagonal Pauli sums D = sum_t c_t Z^{z_t}: the phase exp(-i gamma D), the moments <D>, <D^2>, D as an operator
+(D|psi>, <bra|D|ket>), QAOA layers and their gradient, each use of D ONE pass over the state whatever the number of terms
+(qsim_apply_diagonal_phase, qsim_diagonal_moments, qsim_apply_diagonal_sum, qsim_overlap_diagonal).
 
 Convention as in `evolution`: NO factor 1/2.  exp(-i gamma D) multiplies amplitude i by exp(-i gamma E(i)), E(i) =
 sum_t c_t (-1)^popcount(i & z_t); a Z-only rotation `evolution.rotation("Z0 Z1", theta)` is the term (z, theta) with gamma
@@ -9,7 +10,10 @@ sum_t c_t (-1)^popcount(i & z_t); a Z-only rotation `evolution.rotation("Z0 Z1",
     split(obs)                                -> (the Z-only terms, the rest) as two PauliSums
     apply_phase(chunk, l2p, obs, gamma)       -> psi := exp(-i gamma D) psi through the layout
     moments(chunk, l2p, obs)                  -> (<D>, <D^2> - <D>^2) of the normalised state, one read-only pass
+    apply_sum(dst, src, l2p, obs, accumulate) -> dst := D src, or dst += D src; dst may be src when writing
+    matrix_element(ket, bra, l2p, obs)        -> (<bra|ket>, <bra|D|ket>), unnormalised, one read-only pass
     qaoa(chunk, l2p, cost, gammas, betas)     -> alternating cost and mixer layers; the HBM passes made
+    qaoa_gradient(chunk, work, l2p, cost, gammas, betas) -> (energy, dgammas, dbetas) by the adjoint method
 
 Everything here is host bookkeeping on small arrays; the amplitudes are touched by the device only.
 """
@@ -111,3 +115,67 @@ def qaoa(chunk, l2p, cost, gammas, betas) -> int:
         passes += 1 if z.size else 0
         passes += chunk.apply_pauli_rotations(mx, mz, np.full(n, float(beta)))
     return passes
+
+
+def apply_sum(dst, src, l2p, obs, accumulate: bool = False) -> int:
+    """dst := D src, or dst += D src with `accumulate`, for the diagonal Pauli sum D over LOGICAL qubits; both chunks
+    hold their states in the layout l2p (None: identity).  `dst` may be `src` when writing (psi := D psi in place).  One
+    pass whatever the number of terms; a sum without terms makes dst zero when writing and leaves it when accumulating.
+    Returns the HBM passes made (1, or 0 for a sum without terms)."""
+    if dst.k != src.k:
+        raise ValueError(f"apply_sum: chunks of {dst.k} and {src.k} index bits")
+    z, co = _physical(src, l2p, obs)
+    dst.apply_diagonal_sum(src, z, co, bool(accumulate))
+    return 1 if z.size else 0
+
+
+def matrix_element(ket, bra, l2p, obs) -> tuple[complex, complex]:
+    """(<bra|ket>, <bra|D|ket>), unnormalised, for the diagonal Pauli sum D over LOGICAL qubits, from one read-only pass
+    over both chunks (in the same layout l2p); `bra` may be `ket`."""
+    if ket.k != bra.k:
+        raise ValueError(f"matrix_element: chunks of {ket.k} and {bra.k} index bits")
+    z, co = _physical(ket, l2p, obs)
+    return ket.overlap_diagonal(bra, z, co)
+
+
+def qaoa_gradient(chunk, work, l2p, cost, gammas, betas) -> tuple[float, np.ndarray, np.ndarray]:
+    """(E, dE/dgammas, dE/dbetas) of E = <psi|C|psi>, psi = the circuit of `qaoa` applied to the state in `chunk`, by the
+    adjoint method: one forward run and one backward sweep whatever the number of layers.
+
+    Forward: `qaoa`, E from the moments pass, `work` := lambda = C psi with one diagonal pass.  Backward, for layer
+    l = p-1 .. 0, with B = sum_q X_q:
+        dbetas[l]  = 2 Im <lambda|B|psi>      (one `overlap_pauli` with the n X strings),
+        psi := exp(+i beta_l B) psi,  lambda := exp(+i beta_l B) lambda,
+        dgammas[l] = 2 Im <lambda|C|psi>      (the second output of `overlap_diagonal`, one pass),
+        psi := exp(+i gamma_l C) psi, lambda := exp(+i gamma_l C) lambda.
+    (d/dbeta exp(-i beta B) = -i B exp(-i beta B), so dE/dbeta_l = 2 Re (-i <lambda|B|psi>) with psi after layer l and
+    lambda pulled back to the same point; the same for gamma and C.)  Conventions as in `hamiltonian.adjoint_gradient`:
+    NO factor 1/2, E and the derivatives unnormalised; `chunk` holds its state again on return up to rounding, `work` (a
+    second chunk of the same size) is scratch."""
+    if chunk is work:
+        raise ValueError("qaoa_gradient: two different chunks expected, got the same one twice")
+    if chunk.k != work.k:
+        raise ValueError(f"qaoa_gradient: chunks of {chunk.k} and {work.k} index bits")
+    gammas = np.asarray(gammas, dtype=np.float64).reshape(-1)
+    betas = np.asarray(betas, dtype=np.float64).reshape(-1)
+    if gammas.shape != betas.shape:
+        raise ValueError(f"qaoa_gradient: {gammas.size} gammas, {betas.size} betas")
+    if not (np.all(np.isfinite(gammas)) and np.all(np.isfinite(betas))):
+        raise ValueError("qaoa_gradient: an angle is not finite")
+    n = chunk.k if l2p is None else len(l2p)
+    z, co = _physical(chunk, l2p, cost)
+    mx = evolution.to_physical(np.array([1 << q for q in range(n)], dtype=np.uint64), np.zeros(n, dtype=np.uint64), l2p)[0]
+    mz = np.zeros(n, dtype=np.uint64)
+    qaoa(chunk, l2p, cost, gammas, betas)
+    energy = chunk.diagonal_moments(z, co)[1]
+    work.apply_diagonal_sum(chunk, z, co, False)
+    dgammas, dbetas = np.zeros(gammas.size), np.zeros(betas.size)
+    for l in range(gammas.size - 1, -1, -1):
+        dbetas[l] = 2.0 * float(np.sum(chunk.overlap_pauli(work, mx, mz).imag))
+        back = np.full(n, -float(betas[l]))
+        chunk.apply_pauli_rotations(mx, mz, back)
+        work.apply_pauli_rotations(mx, mz, back)
+        dgammas[l] = 2.0 * chunk.overlap_diagonal(work, z, co)[1].imag
+        chunk.apply_diagonal_phase(z, co, -float(gammas[l]))
+        work.apply_diagonal_phase(z, co, -float(gammas[l]))
+    return float(energy), dgammas, dbetas

@@ -1,9 +1,11 @@
 """A Pauli sum H = sum_t c_t P_t as an OPERATOR on device states: H|psi> into a second chunk, matrix elements between
 two chunks, the energy variance and adjoint-method gradients (qsim_apply_pauli_sum, qsim_overlap_pauli).
 
-    apply(dst, src, l2p, obs)                               -> passes;  dst := H src, out of place
+    apply(dst, src, l2p, obs, fuse_diagonal)                -> passes;  dst := H src, out of place
+    plan(n_qubits, l2p, obs, fuse_diagonal)                 -> the masks of `apply` for a fixed H, made once
+    apply_planned(dst, src, plan)                           -> passes;  what `apply` does with a plan
     matrix_elements(ket, bra, l2p, obs)                     -> complex array, <bra|P_t|ket> per term (no coefficients)
-    variance(chunk, work, l2p, obs)                         -> norm2(H psi) - <H>^2, unnormalised
+    variance(chunk, work, l2p, obs, fuse_diagonal)          -> norm2(H psi) - <H>^2, unnormalised
     adjoint_gradient(chunk, work, l2p, rotations, obs)      -> (energy, grad) of <psi(theta)|H|psi(theta)>
 
 Everything here is host bookkeeping on small arrays: the chunks' logical qubit q lives on index bit l2p[q] (None:
@@ -21,6 +23,13 @@ import numpy as np
 from quantum_simulations_amd import evolution
 from quantum_simulations_amd.observable import as_pauli_sum
 
+# Z-only terms from which `apply(fuse_diagonal=True)` sends them through one diagonal pass that accumulates (48 B per
+# amplitude) instead of leaving them in the per-term passes.  MEASURED (profiles/r24_diagonal_operator_probe.json,
+# `crossover`): inside a mixed sum a Z-only term costs the per-term passes about 0.40 ms at 30 qubits and 0.10 ms at 28,
+# the extra pass 9.5 / 2.4 ms; on the Heisenberg and on the Ising chain, at both sizes, fusing loses up to 20 terms (by 2
+# to 3 % at 20) and wins from 24 on: by 0.1 to 2 % at 24, which is the break-even, by 3 to 6 % at 28, by 31 to 39 % at 64.
+DIAGONAL_MIN_TERMS = 24
+
 
 def _n_qubits(chunk, l2p) -> int:
     return chunk.k if l2p is None else len(l2p)
@@ -33,13 +42,44 @@ def _pair(a, b, what: str) -> None:
         raise ValueError(f"{what}: chunks of {a.k} and {b.k} index bits")
 
 
-def apply(dst, src, l2p, obs) -> int:
-    """dst := H src for a Pauli sum over LOGICAL qubits (observable.PauliSum or what it accepts); what dst held does not
-    matter, src is only read.  Returns the HBM passes made."""
-    _pair(dst, src, "apply")
-    obs = as_pauli_sum(obs, _n_qubits(src, l2p))
+class Plan:
+    """The arrays of one H for `apply_planned`, over PHYSICAL index bits: (x, z, coeffs) of the terms that go through
+    `apply_pauli_sum` and, when the Z-only terms take the diagonal pass, (diag_z, diag_coeffs), else None."""
+
+    def __init__(self, x, z, coeffs, diag_z=None, diag_coeffs=None):
+        self.x, self.z, self.coeffs, self.diag_z, self.diag_coeffs = x, z, coeffs, diag_z, diag_coeffs
+
+
+def plan(n_qubits: int, l2p, obs, fuse_diagonal: bool = False) -> Plan:
+    """The masks of a Pauli sum over LOGICAL qubits through the layout.  With `fuse_diagonal` the Z-only terms (the
+    identity among them: what `diagonal.split` calls the diagonal part) are set apart for one diagonal pass when there
+    are at least DIAGONAL_MIN_TERMS of them; fewer stay with the rest."""
+    obs = as_pauli_sum(obs, n_qubits)
     x, z = obs.masks(l2p)
-    return dst.apply_pauli_sum(src, x, z, obs.coeffs)
+    co = np.asarray(obs.coeffs, dtype=np.float64)
+    zonly = x == 0
+    if not fuse_diagonal or int(np.count_nonzero(zonly)) < max(int(DIAGONAL_MIN_TERMS), 1):
+        return Plan(x, z, co)
+    return Plan(x[~zonly], z[~zonly], co[~zonly], z[zonly], co[zonly])
+
+
+def apply_planned(dst, src, p: Plan) -> int:
+    """dst := H src for the H of a `plan`.  Without a diagonal part: `apply_pauli_sum`.  With one: the rest through
+    `apply_pauli_sum`, which writes, then the diagonal pass accumulates; with no rest the diagonal pass writes.  Returns
+    the HBM passes made."""
+    _pair(dst, src, "apply")
+    if p.diag_z is None:
+        return dst.apply_pauli_sum(src, p.x, p.z, p.coeffs)
+    passes = dst.apply_pauli_sum(src, p.x, p.z, p.coeffs) if p.x.size else 0
+    dst.apply_diagonal_sum(src, p.diag_z, p.diag_coeffs, bool(p.x.size))
+    return passes + 1
+
+
+def apply(dst, src, l2p, obs, fuse_diagonal: bool = False) -> int:
+    """dst := H src for a Pauli sum over LOGICAL qubits (observable.PauliSum or what it accepts); what dst held does not
+    matter, src is only read.  `fuse_diagonal`: the Z-only terms go through ONE diagonal pass whatever their number, when
+    there are at least DIAGONAL_MIN_TERMS of them (`plan`).  Returns the HBM passes made."""
+    return apply_planned(dst, src, plan(_n_qubits(src, l2p), l2p, obs, fuse_diagonal))
 
 
 def matrix_elements(ket, bra, l2p, obs) -> np.ndarray:
@@ -52,12 +92,13 @@ def matrix_elements(ket, bra, l2p, obs) -> np.ndarray:
     return ket.overlap_pauli(bra, x, z)
 
 
-def variance(chunk, work, l2p, obs) -> float:
+def variance(chunk, work, l2p, obs, fuse_diagonal: bool = False) -> float:
     """<psi|H^2|psi> - <psi|H|psi>^2 as norm2(H psi) - <H>^2, unnormalised like every readout here (for a state of norm
-    1 it is the energy variance).  `work` := H psi: a second chunk of the same size, overwritten."""
+    1 it is the energy variance).  `work` := H psi: a second chunk of the same size, overwritten.  `fuse_diagonal`: as
+    in `apply`."""
     _pair(work, chunk, "variance")
     obs = as_pauli_sum(obs, _n_qubits(chunk, l2p))
-    apply(work, chunk, l2p, obs)
+    apply(work, chunk, l2p, obs, fuse_diagonal)
     mean = chunk.expectation(obs, l2p=None if l2p is None else list(l2p))
     return work.norm2() - mean * mean
 

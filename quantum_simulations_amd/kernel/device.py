@@ -232,6 +232,29 @@ class DeviceChunk:
         _lib.check(_lib.load().qsim_diagonal_moments(self._h, int(z.size), _lib.ptr(z), _lib.ptr(co), _lib.ptr(out)))
         return float(out[0]), float(out[1]), float(out[2])
 
+    def apply_diagonal_sum(self, src: "DeviceChunk", z_masks, coeffs, accumulate: bool = False) -> None:
+        """self := D src, or self += D src with `accumulate`, for the diagonal D of `apply_diagonal_phase` (masks over
+        PHYSICAL index bits): self_i (+)= E(i) src_i.  ONE pass whatever the number of terms, enqueued on the chunk's
+        stream (qsim_apply_diagonal_sum).  `src` may be `self` when writing (psi := D psi in place); any other overlap is
+        refused.  No terms: self := 0 when writing, untouched when accumulating."""
+        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
+        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
+        if z.shape != co.shape:
+            raise ValueError(f"apply_diagonal_sum: {z.size} z masks, {co.size} coefficients")
+        _lib.check(_lib.load().qsim_apply_diagonal_sum(self._h, src._h, int(z.size), _lib.ptr(z), _lib.ptr(co), 1 if accumulate else 0))
+
+    def overlap_diagonal(self, bra: "DeviceChunk", z_masks, coeffs) -> tuple:
+        """(<bra|self>, <bra|D|self>), unnormalised, for the diagonal D of `apply_diagonal_phase` (`self` is the ket):
+        sum_i conj(bra_i) self_i and sum_i conj(bra_i) E(i) self_i from ONE read-only pass over both chunks, a fixed
+        summation order -- two calls give the same bits (qsim_overlap_diagonal).  `bra` may be `self`."""
+        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
+        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
+        if z.shape != co.shape:
+            raise ValueError(f"overlap_diagonal: {z.size} z masks, {co.size} coefficients")
+        out = np.empty(4, dtype=np.float64)
+        _lib.check(_lib.load().qsim_overlap_diagonal(self._h, bra._h, int(z.size), _lib.ptr(z), _lib.ptr(co), _lib.ptr(out)))
+        return complex(out[0], out[1]), complex(out[2], out[3])
+
     def apply_pauli_sum(self, src: "DeviceChunk", x_masks, z_masks, coeffs) -> int:
         """self := sum_t coeffs[t] P_t src, OUT OF PLACE (`self` is dst: what it held does not matter; `src` is only
         read and may not overlap it); P_t as masks of PHYSICAL index bits (x: X or Y, z: Z or Y), real finite
@@ -475,11 +498,11 @@ class DeviceChunk:
         _lib.check(_lib.load().qsim_profile_begin(self._h))
 
     def profile_end(self) -> list[dict]:
-        entries = (_lib.ProfileEntry * 16)()
+        entries = (_lib.ProfileEntry * 32)()
         n = C.c_int()
-        _lib.check(_lib.load().qsim_profile_end(self._h, 16, C.byref(n), C.cast(entries, C.c_void_p)))
+        _lib.check(_lib.load().qsim_profile_end(self._h, 32, C.byref(n), C.cast(entries, C.c_void_p)))
         out = []
-        for e in entries[: min(n.value, 16)]:
+        for e in entries[: min(n.value, 32)]:
             out.append({"kernel": e.kernel.decode(), "launches": int(e.launches),
                         "total_ms": float(e.total_ms), "algorithmic_bytes": float(e.algorithmic_bytes),
                         "hbm_bytes": float(e.hbm_bytes), "streaming_launches": int(e.streaming_launches)})

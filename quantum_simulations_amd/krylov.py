@@ -7,7 +7,8 @@ ground-state solver and Krylov time evolution in real and imaginary time, withou
 
 Everything here is host bookkeeping on small arrays, as in `hamiltonian`: the chunks' logical qubit q lives on index bit
 l2p[q] (None: identity) and the layout goes into the masks; the amplitudes are touched by the device only, through three
-chunk calls: `apply_pauli_sum` (H v, out of place), `lincomb` (w := a w + sum a_s v_s with <v|w> and |w|^2 of the result
+chunk calls: H v out of place (`hamiltonian.apply_planned`: `apply_pauli_sum`, and with `fuse_diagonal` one diagonal pass
+for the Z-only terms), `lincomb` (w := a w + sum a_s v_s with <v|w> and |w|^2 of the result
 taken in the same pass) and `norm2`.  The caller supplies the work chunks: all of the state's size, on its
 device, in its layout, and none of them the state itself.
 
@@ -19,7 +20,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from quantum_simulations_amd.observable import as_pauli_sum
+from quantum_simulations_amd import hamiltonian
 
 GROUP = 4            # sources, and bras, of one `lincomb` call
 
@@ -65,13 +66,18 @@ def _normalise(chunk, what: str) -> float:
     return norm
 
 
-def _recurrence(basis, x, z, co, scale: float, m: int, reorth: bool, breakdown: float):
+def _apply_h(w, v, h) -> None:
+    """w := H v, the one place where the solvers apply H (`h`: the plan of `_setup`)."""
+    hamiltonian.apply_planned(w, v, h)
+
+
+def _recurrence(basis, h, scale: float, m: int, reorth: bool, breakdown: float):
     """The Lanczos steps from the unit vector basis[0]: (alphas[k], betas[k], k) with betas[k - 1] the norm of the last
     residual.  basis[j + 1] := v_{j+1} for j < k (the last one only if the run did not break down)."""
     alphas, betas = [], []
     for j in range(m):
         v, w = basis[j], basis[j + 1]
-        w.apply_pauli_sum(v, x, z, co)                                            # w := H v_j, straight into its slot
+        _apply_h(w, v, h)                                                         # w := H v_j, straight into its slot
         if j:
             dots, _ = w.lincomb(1.0, [basis[j - 1]], [-betas[j - 1]], bras=[v])   # w -= beta_{j-1} v_{j-1};  <v_j|w>
         else:
@@ -97,13 +103,14 @@ def _tridiagonal(alphas, betas, k: int):
     return np.linalg.eigh(T)
 
 
-def _setup(chunk, l2p, obs):
-    obs = as_pauli_sum(obs, _n_qubits(chunk, l2p))
-    x, z = obs.masks(l2p)
-    return x, z, obs.coeffs, float(np.sum(np.abs(obs.coeffs)))
+def _setup(chunk, l2p, obs, fuse_diagonal: bool):
+    """(the plan of H for `_apply_h`, sum |c_t|)"""
+    h = hamiltonian.plan(_n_qubits(chunk, l2p), l2p, obs, fuse_diagonal)
+    scale = float(np.sum(np.abs(h.coeffs))) + (float(np.sum(np.abs(h.diag_coeffs))) if h.diag_z is not None else 0.0)
+    return h, scale
 
 
-def lanczos(chunk, work, l2p, obs, m: int, reorth: bool = True, breakdown: float = 1e-12) -> tuple:
+def lanczos(chunk, work, l2p, obs, m: int, reorth: bool = True, breakdown: float = 1e-12, fuse_diagonal: bool = False) -> tuple:
     """The Lanczos recurrence of a Pauli sum over LOGICAL qubits from v_0 = `chunk` (any norm but zero: it is normalised
     in place); `work` is a list of at least m chunks that become v_1 .. v_m.  Step j:
         w := H v_j, written straight into work[j];
@@ -113,14 +120,16 @@ def lanczos(chunk, work, l2p, obs, m: int, reorth: bool = True, breakdown: float
         v_{j+1} := w / beta_j.
     Returns (alphas, betas, k): the k x k tridiagonal matrix has alphas[0..k) on and betas[0..k-1) beside the diagonal,
     betas[k - 1] is the norm of the last residual.  k = m, or k = j + 1 when beta_j <= breakdown * sum |c_t|: the
-    vectors span an invariant subspace (work[j] is then left unnormalised)."""
+    vectors span an invariant subspace (work[j] is then left unnormalised).  `fuse_diagonal`: every H application sends
+    the Z-only terms through one diagonal pass (`hamiltonian.plan`)."""
     _check_chunks(chunk, work, m, 1, "lanczos")
-    x, z, co, scale = _setup(chunk, l2p, obs)
+    h, scale = _setup(chunk, l2p, obs, fuse_diagonal)
     _normalise(chunk, "lanczos")
-    return _recurrence([chunk] + list(work[:int(m)]), x, z, co, scale, int(m), reorth, breakdown)
+    return _recurrence([chunk] + list(work[:int(m)]), h, scale, int(m), reorth, breakdown)
 
 
-def ground_state(chunk, work, l2p, obs, m: int = 16, tol: float = 1e-8, max_restarts: int = 50, reorth: bool = True) -> tuple:
+def ground_state(chunk, work, l2p, obs, m: int = 16, tol: float = 1e-8, max_restarts: int = 50, reorth: bool = True,
+                 fuse_diagonal: bool = False) -> tuple:
     """The lowest eigenpair of a Pauli sum over LOGICAL qubits by restarted Lanczos, on the device.  On entry `chunk`
     holds the start vector (any norm but zero; it must overlap the ground state: a random state does); on return it holds
     the normalised eigenvector estimate psi.  One restart is: m Lanczos steps from psi, `numpy.linalg.eigh` of the
@@ -130,21 +139,21 @@ def ground_state(chunk, work, l2p, obs, m: int = 16, tol: float = 1e-8, max_rest
 
     Needs m + 1 chunks in all: `chunk` plus m work chunks, 16 GiB each at 30 qubits (m = 16: 272 GiB; m = 8: 144 GiB).
     Returns (energy, residual, restarts, h_applications).  ValueError: fewer than m work chunks, m < 2, a zero start
-    vector."""
+    vector.  `fuse_diagonal`: as in `lanczos`."""
     _check_chunks(chunk, work, m, 2, "ground_state")
     m = int(m)
-    x, z, co, scale = _setup(chunk, l2p, obs)
+    h, scale = _setup(chunk, l2p, obs, fuse_diagonal)
     basis = [chunk] + list(work[:m])
     _normalise(chunk, "ground_state")
     energy = residual = float("nan")
     restarts = h_applications = 0
     while restarts < max(int(max_restarts), 1):
-        alphas, betas, k = _recurrence(basis, x, z, co, scale, m, reorth, 1e-12)
+        alphas, betas, k = _recurrence(basis, h, scale, m, reorth, 1e-12)
         y = _tridiagonal(alphas, betas, k)[1][:, 0]
         n2 = _combine(chunk, y[0], basis[1:k], y[1:k], want_norm2=True)
         chunk.lincomb(1.0 / np.sqrt(n2))
         w = basis[1]
-        w.apply_pauli_sum(chunk, x, z, co)
+        _apply_h(w, chunk, h)
         energy = float(w.lincomb(1.0, bras=[chunk])[0][0].real)
         residual = float(np.sqrt(max(w.lincomb(1.0, [chunk], [-energy], want_norm2=True)[1], 0.0)))
         restarts += 1
@@ -154,27 +163,27 @@ def ground_state(chunk, work, l2p, obs, m: int = 16, tol: float = 1e-8, max_rest
     return energy, residual, restarts, h_applications
 
 
-def evolve(chunk, work, l2p, obs, t, m: int = 16, steps: int = 1) -> float:
+def evolve(chunk, work, l2p, obs, t, m: int = 16, steps: int = 1, fuse_diagonal: bool = False) -> float:
     """chunk := exp(-i t H) chunk for a Pauli sum over LOGICAL qubits, by `steps` Krylov steps of length dt = t / steps:
     m Lanczos steps from psi / |psi|, c = Y exp(-i dt Lambda) Y^T e_1 from the eigen-decomposition of the tridiagonal
     matrix on the host, and psi := |psi| sum_i c_i v_i built in place, 4 sources per pass.  `t` may be complex:
     t = -i tau is imaginary-time evolution exp(-tau H), whose result is NOT normalised (like every readout here).
     Returns the sum over the steps of |psi| beta_k |c_k|, the usual a-posteriori estimate of the l2 error.
     Needs m work chunks (see `ground_state`).  ValueError: fewer than m work chunks, m < 1, steps < 1, a time that is
-    not finite, a zero state."""
+    not finite, a zero state.  `fuse_diagonal`: as in `lanczos`."""
     _check_chunks(chunk, work, m, 1, "evolve")
     m, steps, t = int(m), int(steps), complex(t)
     if steps < 1:
         raise ValueError(f"evolve: steps = {steps}, at least one")
     if not np.isfinite(t):
         raise ValueError(f"evolve: time {t!r} is not finite")
-    x, z, co, scale = _setup(chunk, l2p, obs)
+    h, scale = _setup(chunk, l2p, obs, fuse_diagonal)
     basis = [chunk] + list(work[:m])
     dt = t / steps
     estimate = 0.0
     for _ in range(steps):
         norm = _normalise(chunk, "evolve")
-        alphas, betas, k = _recurrence(basis, x, z, co, scale, m, True, 1e-12)
+        alphas, betas, k = _recurrence(basis, h, scale, m, True, 1e-12)
         lam, Y = _tridiagonal(alphas, betas, k)
         c = norm * (Y @ (np.exp(-1j * dt * lam) * Y[0, :]))
         _combine(chunk, c[0], basis[1:k], c[1:k])

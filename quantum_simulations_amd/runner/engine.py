@@ -137,24 +137,34 @@ class SingleGpuEngine:
         self._zero = False
         return passes
 
+    def qaoa_gradient(self, cost, gammas, betas) -> tuple:
+        """(E, dE/dgammas, dE/dbetas) of E = <psi|C|psi> with psi = the QAOA circuit of `qaoa` applied to the CURRENT
+        state, by the adjoint method on the device (`diagonal.qaoa_gradient`: per layer one overlap with the n mixer
+        strings, one diagonal overlap pass and the two inverse layers on two chunks); no factor 1/2, unnormalised.  The
+        state is the same afterwards up to rounding and does not move; the engine's second chunk is overwritten."""
+        out = diagonal.qaoa_gradient(self.state, self._work_chunk(), self.l2p, cost, gammas, betas)
+        self._zero = False
+        return out
+
     def _work_chunk(self) -> DeviceChunk:
         if self._work is None:
             self._work = DeviceChunk.empty(self.n, self.state.device)
         return self._work
 
-    def apply_observable(self, obs, out: DeviceChunk | None = None) -> DeviceChunk:
+    def apply_observable(self, obs, out: DeviceChunk | None = None, fuse_diagonal: bool = False) -> DeviceChunk:
         """H|psi> for a Pauli sum over LOGICAL qubits, written on the device into `out` (a chunk of the state's size
         on its device; default: the engine's own second chunk, allocated on first use and overwritten by `variance` and
         `gradient`) IN THE STATE'S CURRENT LAYOUT `self.l2p`; the state does not move.  Returns that chunk;
-        `out.last_pauli_sum_passes` = the HBM passes made."""
+        `out.last_pauli_sum_passes` = the HBM passes made by the per-term path.  `fuse_diagonal`: the Z-only terms go
+        through one diagonal pass more (`hamiltonian.apply`)."""
         out = self._work_chunk() if out is None else out
-        hamiltonian.apply(out, self.state, self.l2p, obs)
+        hamiltonian.apply(out, self.state, self.l2p, obs, fuse_diagonal)
         return out
 
-    def variance(self, obs) -> float:
+    def variance(self, obs, fuse_diagonal: bool = False) -> float:
         """<H^2> - <H>^2 (unnormalised: norm2(H psi) - <psi|H|psi>^2) of a Pauli sum over LOGICAL qubits, on the
-        device; the engine's second chunk is overwritten."""
-        return hamiltonian.variance(self.state, self._work_chunk(), self.l2p, obs)
+        device; the engine's second chunk is overwritten.  `fuse_diagonal`: as in `apply_observable`."""
+        return hamiltonian.variance(self.state, self._work_chunk(), self.l2p, obs, fuse_diagonal)
 
     def overlap_with(self, chunk: DeviceChunk, obs=None):
         """<chunk|psi> (obs None: a complex number), or <chunk|H|psi> = sum_t c_t <chunk|P_t|psi> for a Pauli sum over
@@ -190,19 +200,22 @@ class SingleGpuEngine:
             for c in work:
                 c.close()
 
-    def ground_state(self, obs, m: int = 16, tol: float = 1e-8, max_restarts: int = 50) -> tuple:
+    def ground_state(self, obs, m: int = 16, tol: float = 1e-8, max_restarts: int = 50, fuse_diagonal: bool = False) -> tuple:
         """The lowest eigenpair of a Pauli sum over LOGICAL qubits by restarted Lanczos on the device
         (`krylov.ground_state`), started from the CURRENT state, which must overlap the ground state
         (`init_random_state` does) and is replaced by the normalised eigenvector estimate in the current layout.
         m + 1 chunks of the state's size are alive during the call: m work chunks are allocated for it and freed.
-        Returns (energy, residual |H psi - E psi|, restarts, H applications)."""
-        return self._with_krylov_chunks(m, lambda work: krylov.ground_state(self.state, work, self.l2p, obs, m, tol, max_restarts))
+        Returns (energy, residual |H psi - E psi|, restarts, H applications).  `fuse_diagonal`: as in `apply_observable`,
+        for every H application."""
+        return self._with_krylov_chunks(m, lambda work: krylov.ground_state(self.state, work, self.l2p, obs, m, tol, max_restarts,
+                                                                            fuse_diagonal=fuse_diagonal))
 
-    def evolve_krylov(self, obs, t, m: int = 16, steps: int = 1) -> float:
+    def evolve_krylov(self, obs, t, m: int = 16, steps: int = 1, fuse_diagonal: bool = False) -> float:
         """psi := exp(-i t H) psi to Krylov accuracy (`krylov.evolve`: `steps` steps of m Lanczos vectors each) for a
         Pauli sum over LOGICAL qubits, on the device through the current layout; t = -i tau gives exp(-tau H) psi,
-        unnormalised.  m work chunks are allocated for the call and freed.  Returns the a-posteriori error estimate."""
-        return self._with_krylov_chunks(m, lambda work: krylov.evolve(self.state, work, self.l2p, obs, t, m, steps))
+        unnormalised.  m work chunks are allocated for the call and freed.  Returns the a-posteriori error estimate.
+        `fuse_diagonal`: as in `apply_observable`, for every H application."""
+        return self._with_krylov_chunks(m, lambda work: krylov.evolve(self.state, work, self.l2p, obs, t, m, steps, fuse_diagonal))
 
     def reduced_density_matrix(self, qubits) -> np.ndarray:
         """Reduced density matrix (unnormalised, complex128 (2^r, 2^r)) of 1 to 6 LOGICAL qubits, bit j of a row or

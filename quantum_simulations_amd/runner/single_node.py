@@ -338,13 +338,25 @@ def qaoa(buf: HbmStateBuffer, cost, gammas, betas) -> int:
     return diagonal.qaoa(buf.state, getattr(buf, "log_to_phys", None) or None, cost, gammas, betas)
 
 
-def variance(buf: HbmStateBuffer, obs) -> float:
-    """<H^2> - <H>^2 (unnormalised: norm2(H psi) - <psi|H|psi>^2) of a Pauli sum over LOGICAL qubits on the final state of
-    `run`, on the device through the staging layout `buf.log_to_phys`; a second chunk of the state's size is allocated
+def qaoa_gradient(buf: HbmStateBuffer, cost, gammas, betas) -> tuple:
+    """(E, dE/dgammas, dE/dbetas) of E = <psi|C|psi>, psi = the QAOA circuit of `qaoa` applied to the final state of `run`,
+    by the adjoint method on the device (`diagonal.qaoa_gradient`) through the staging layout `buf.log_to_phys`; no factor
+    1/2, unnormalised.  The state is the same afterwards up to rounding; a second chunk of the state's size is allocated
     for the call and closed."""
     work = DeviceChunk.empty(buf.state.k, buf.state.device)
     try:
-        return hamiltonian.variance(buf.state, work, getattr(buf, "log_to_phys", None) or None, obs)
+        return diagonal.qaoa_gradient(buf.state, work, getattr(buf, "log_to_phys", None) or None, cost, gammas, betas)
+    finally:
+        work.close()
+
+
+def variance(buf: HbmStateBuffer, obs, fuse_diagonal: bool = False) -> float:
+    """<H^2> - <H>^2 (unnormalised: norm2(H psi) - <psi|H|psi>^2) of a Pauli sum over LOGICAL qubits on the final state of
+    `run`, on the device through the staging layout `buf.log_to_phys`; a second chunk of the state's size is allocated
+    for the call and closed.  `fuse_diagonal`: the Z-only terms of H go through one diagonal pass (`hamiltonian.apply`)."""
+    work = DeviceChunk.empty(buf.state.k, buf.state.device)
+    try:
+        return hamiltonian.variance(buf.state, work, getattr(buf, "log_to_phys", None) or None, obs, fuse_diagonal)
     finally:
         work.close()
 
@@ -373,18 +385,21 @@ def _with_krylov_chunks(buf: HbmStateBuffer, m: int, call):
             c.close()
 
 
-def ground_state(buf: HbmStateBuffer, obs, m: int = 16, tol: float = 1e-8, max_restarts: int = 50) -> tuple:
+def ground_state(buf: HbmStateBuffer, obs, m: int = 16, tol: float = 1e-8, max_restarts: int = 50, fuse_diagonal: bool = False) -> tuple:
     """The lowest eigenpair of a Pauli sum over LOGICAL qubits by restarted Lanczos (`krylov.ground_state`), started from
     the final state of `run` and left there, normalised, in the staging layout `buf.log_to_phys`; m work chunks of the
-    state's size are allocated for the call and closed.  Returns (energy, residual, restarts, H applications)."""
-    return _with_krylov_chunks(buf, m, lambda work, l2p: krylov.ground_state(buf.state, work, l2p, obs, m, tol, max_restarts))
+    state's size are allocated for the call and closed.  Returns (energy, residual, restarts, H applications).
+    `fuse_diagonal`: as in `variance`, for every H application."""
+    return _with_krylov_chunks(buf, m, lambda work, l2p: krylov.ground_state(buf.state, work, l2p, obs, m, tol, max_restarts,
+                                                                             fuse_diagonal=fuse_diagonal))
 
 
-def evolve_krylov(buf: HbmStateBuffer, obs, t, m: int = 16, steps: int = 1) -> float:
+def evolve_krylov(buf: HbmStateBuffer, obs, t, m: int = 16, steps: int = 1, fuse_diagonal: bool = False) -> float:
     """exp(-i t H) applied to the final state of `run` to Krylov accuracy (`krylov.evolve`; t = -i tau: exp(-tau H),
     unnormalised) for a Pauli sum over LOGICAL qubits, on the device through the staging layout `buf.log_to_phys`; m work
-    chunks of the state's size are allocated for the call and closed.  Returns the a-posteriori error estimate."""
-    return _with_krylov_chunks(buf, m, lambda work, l2p: krylov.evolve(buf.state, work, l2p, obs, t, m, steps))
+    chunks of the state's size are allocated for the call and closed.  Returns the a-posteriori error estimate.
+    `fuse_diagonal`: as in `variance`, for every H application."""
+    return _with_krylov_chunks(buf, m, lambda work, l2p: krylov.evolve(buf.state, work, l2p, obs, t, m, steps, fuse_diagonal))
 
 
 def reduced_density_matrix(buf: HbmStateBuffer, qubits) -> np.ndarray:
