@@ -563,7 +563,11 @@ int qsim_sample_locate(uint64_t n_blocks, const double* block_cdf, uint64_t n_sh
 int qsim_sample_block_bits(void);   /* log2 of the block length of qsim_sample, for tests and hosts */
 /* max_i |amp_i - expected_i| for closed-form states, evaluated on the device:
  * kind 0: GHZ (1/sqrt2 at local index 0 of the first chunk and at the last index of the
- *         last), kind 1: GHZ+QFT  2^-(n+1)/2 (1 + exp(-2 pi i y / 2^n)), y = base + i.  */
+ *         last), kind 1: GHZ+QFT  2^-(n+1)/2 (1 + exp(-2 pi i y / 2^n)), y = base + i.
+ * The result is not finite (NaN or +inf) whenever an amplitude of the chunk is not finite: the
+ * maximum keeps a NaN, on the device and on the host, so `err < tol` is false for such a chunk.
+ * base_index is a multiple of the chunk length, and the chunk lies inside a state of
+ * n_total_qubits qubits at that base; anything else fails with QSIM_ERR_INVALID.          */
 int qsim_max_abs_err_closed_form(qsim_chunk* c, int kind, int n_total_qubits,
                                  uint64_t base_index, double* out);
 /* Same for a staged layout: logical qubit q sits at physical index bit log_to_phys[q]

@@ -465,6 +465,8 @@ int qsim_max_abs_err_closed_form_perm(qsim_chunk* c, int kind, int n_total_qubit
   if (rc) return rc;
   if (!out || (kind != 0 && kind != 1) || n_total_qubits < c->k || n_total_qubits > 52)
     return fail(QSIM_ERR_INVALID, "qsim_max_abs_err_closed_form: bad arguments");
+  if (base_index & (amps(c) - 1)) return fail(QSIM_ERR_INVALID, "qsim_max_abs_err_closed_form: base_index must be a multiple of the chunk length");
+  if ((base_index + amps(c) - 1) >> n_total_qubits) return fail(QSIM_ERR_INVALID, "qsim_max_abs_err_closed_form: the chunk does not fit a state of %d qubits at that base", n_total_qubits);
   BitPerm perm;
   if ((rc = bit_perm_from(log_to_phys, n_total_qubits, &perm, "qsim_max_abs_err_closed_form"))) return rc;
   if ((rc = ensure_scratch(c))) return rc;

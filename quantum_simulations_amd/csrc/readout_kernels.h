@@ -9,9 +9,12 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+// The maximum that keeps a NaN: fmax and std::max drop a NaN operand, and a checker built on them calls a chunk of NaNs
+// exact.  Once r is NaN no comparison is true any more, so it stays.
+__host__ __device__ __forceinline__ double max_keep_nan(double r, double v) { return (v > r || v != v) ? v : r; }
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  for (int off = 32; off > 0; off >>= 1) v = max_keep_nan(v, __shfl_xor(v, off, 64));
   return v;
 }
 
@@ -23,7 +26,7 @@ __device__ __forceinline__ void block_reduce_store(double v, double* out) {
   __syncthreads();
   if (threadIdx.x == 0) {
     double r = part[0];
-    for (int w = 1; w < kBlock / 64; ++w) r = MAX ? fmax(r, part[w]) : r + part[w];
+    for (int w = 1; w < kBlock / 64; ++w) r = MAX ? max_keep_nan(r, part[w]) : r + part[w];
     out[blockIdx.x] = r;
   }
 }
@@ -189,7 +192,7 @@ __global__ __launch_bounds__(kBlock) void k_closed_form_err(const double2* p, u6
       ei = amp * s;
     }
     const double2 v = p[i];
-    worst = fmax(worst, hypot(v.x - er, v.y - ei));
+    worst = max_keep_nan(worst, hypot(v.x - er, v.y - ei));
   }
   block_reduce_store<true>(worst, partial);
 }
@@ -283,7 +286,7 @@ static int reduce_partials(qsim_chunk* c, unsigned grid, int width, bool max, do
     double worst = 0;
     for (unsigned b = 0; b < grid; ++b) {
       const double v = host[(size_t)width * b + w];
-      if (max) worst = std::max(worst, v);
+      if (max) worst = max_keep_nan(worst, v);
       else total += v;
     }
     out[w] = max ? worst : (double)total;

@@ -469,7 +469,10 @@ class DeviceChunk:
 
     def max_abs_err_closed_form(self, kind: str, n_total: int, base_index: int = 0,
                                 log_to_phys=None) -> float:
-        """max |amp - closed form| over this chunk; `log_to_phys` maps a staged layout back."""
+        """max |amp - closed form| over this chunk; `log_to_phys` maps a staged layout back.  The result is not finite
+        (NaN or +inf) whenever an amplitude of the chunk is not finite, so `err < tol` is false for such a chunk.
+        `base_index` is a multiple of the chunk length and the chunk lies inside a state of `n_total` qubits at that
+        base (ValueError otherwise)."""
         out = C.c_double()
         code = {"ghz": 0, "ghz_qft": 1}[kind]
         perm = None if log_to_phys is None else np.asarray(log_to_phys, dtype=np.int32)

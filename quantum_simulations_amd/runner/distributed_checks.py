@@ -12,6 +12,12 @@ import numpy as np
 from quantum_simulations_amd.circuit.staging import permute_state
 
 
+def _inf_unless_finite(err: float) -> float:
+    """A non-finite local error as +inf: what a MAX over ranks (and Python's max) does with a NaN is not defined, +inf
+    survives any of them."""
+    return err if np.isfinite(err) else float("inf")
+
+
 class ChecksMixin:
     """For `DistributedEngine`: the shard, the layout (`l2p`), `plan` / `execute`, `_bring_local` and the collectives are there."""
 
@@ -79,16 +85,17 @@ class ChecksMixin:
 
     def closed_form_error(self, kind: str) -> float:
         """max over ALL 2^n amplitudes of |amp - closed form| ("ghz" / "ghz_qft"),
-        evaluated on every shard in its current (staged) layout and max-reduced over ranks."""
+        evaluated on every shard in its current (staged) layout and max-reduced over ranks.  Not finite on every rank
+        whenever an amplitude of any shard is not finite."""
         self._flush_local()
         local = self.backend.closed_form_error(kind, self.n, self.rank << self.k, self.l2p)
-        return self.max_over_ranks(local)
+        return self.max_over_ranks(_inf_unless_finite(local))
 
     def closed_form_sample_error(self, kind: str, windows: int = 16, window: int = 256, seed: int = 7) -> float:
         """The sampled HOST check next to `closed_form_error`: `windows` runs of `window` amplitudes
         of every shard (its first and last run and random ones) are downloaded and compared on the host with the closed
         forms of SURVEY 8c written out in numpy -- an implementation that shares nothing with the device reduction;
-        max over the samples of all ranks."""
+        max over the samples of all ranks.  Not finite on every rank whenever a sampled amplitude is not finite."""
         self._flush_local()
         size = 1 << self.k
         window = min(window, size)
@@ -108,7 +115,7 @@ class ChecksMixin:
                 want = 2.0 ** (-(self.n + 1) / 2) * (1.0 + np.exp(-2j * np.pi * (y.astype(np.float64) / 2.0 ** self.n)))
             else:
                 raise ValueError("kind must be 'ghz' or 'ghz_qft'")
-            worst = max(worst, float(np.max(np.abs(got - want))))
+            worst = max(worst, _inf_unless_finite(float(np.max(np.abs(got - want)))))
         return self.max_over_ranks(worst)
 
     # ---- amplitude-level check of states too large to gather ------------------------------
