@@ -213,6 +213,12 @@ int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int
 int qsim_rewrite_ops(int n_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, int32_t* out_nq,
                      int32_t* out_qubits, double* out_mats, int out_capacity, int32_t* n_out, int32_t* need_tile);
 
+/* The pass images of qsim_plan_ops* as they reach the device: qsim_apply_ops* rewrite every unconditional real 2x2 record
+ * [[m0, m1], [m2, m3]] with |m0| == |m3| and |m1| == |m2| (RY and its products with X, Y, Z) into a unit-diagonal butterfly
+ * record -- the larger of m0, m1 leaves the matrix and joins the factor of the pass -- before they launch a pass.  The same
+ * rewrite on n_images planned images, in place; *n_rewritten (may be NULL): the records rewritten.  Host only. */
+int qsim_lower_pass_images(void* images, int n_images, int32_t* n_rewritten);
+
 /* The measured price of the fused pass's gate engine, as the caller hands it to the priced planning calls (the shipped
  * table is runner/engine_cost_model.json; the library reads nothing from a file or the environment): entry
  * QSIM_ENGINE_COST_x = microseconds one record of that kind adds to a pass of 2^FIT_QUBITS amplitudes once the pass is
@@ -225,7 +231,7 @@ enum { QSIM_ENGINE_COST_FIXED_US = 0, QSIM_ENGINE_COST_GROUP, QSIM_ENGINE_COST_D
        QSIM_ENGINE_COST_HAD1, QSIM_ENGINE_COST_SWAP1, QSIM_ENGINE_COST_ASWAP1, QSIM_ENGINE_COST_ANTI1, QSIM_ENGINE_COST_PHASE,
        QSIM_ENGINE_COST_PHASE_NEG, QSIM_ENGINE_COST_PHASE_I, QSIM_ENGINE_COST_DIAGR, QSIM_ENGINE_COST_DENSE2,
        QSIM_ENGINE_COST_PRED_LANE, QSIM_ENGINE_COST_PRED_OUTER, QSIM_ENGINE_COST_REG_CTRL, QSIM_ENGINE_COST_DIRECT_END,
-       QSIM_ENGINE_COST_FIT_QUBITS, QSIM_ENGINE_COST_COUNT };
+       QSIM_ENGINE_COST_FIT_QUBITS, QSIM_ENGINE_COST_UNIT1, QSIM_ENGINE_COST_COUNT };
 /* Pass time = max(memory time of the tile, engine time of the records): the placement (qsim_apply_ops_placed,
  * qsim_plan_ops_placed) of the op list over the n_tiles named passes under the caller's prices.  pass_memory_us[p]: what
  * the tile of pass p costs without gates (the tile-cost model of runner/tile_layout.py); engine_costs: the engine table.

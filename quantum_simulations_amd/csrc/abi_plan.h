@@ -62,6 +62,22 @@ int qsim_plan_ops_placed(int n_local_qubits, int n_ops, const int32_t* nq, const
                          out_capacity_bytes, n_passes);
 }
 
+// What run_fused does to planned pass images before it launches them (tile_groups.h lower_unit_real): the unconditional real
+// 2x2 records of the unit-diagonal family become OPC_UNIT1 and their factors go into a matrix or the OPC_SCALE record of
+// the pass.  In place, n_images images of QSIM_PASS_IMAGE_BYTES; *n_rewritten (optional): records rewritten.  Host only.
+int qsim_lower_pass_images(void* images, int n_images, int32_t* n_rewritten) {
+  if (n_images < 0 || (n_images && !images)) return fail(QSIM_ERR_INVALID, "qsim_lower_pass_images: bad arguments");
+  int total = 0;
+  for (int i = 0; i < n_images; ++i) {
+    TileArgs a;
+    std::memcpy(&a, (char*)images + (size_t)i * sizeof a, sizeof a);
+    total += lower_unit_real(&a);
+    std::memcpy((char*)images + (size_t)i * sizeof a, &a, sizeof a);
+  }
+  if (n_rewritten) *n_rewritten = total;
+  return QSIM_OK;
+}
+
 // The searching pass builder (tile_search.h): the tiles of a plan of the op list with as few passes as a beam search of
 // width `beam` finds (<= 0: the default width), never more than qsim_plan_ops needs.  out_masks[p] = the high tile bits of
 // pass p (capacity out_capacity masks; may be NULL to count only); handed to qsim_plan_ops_tiled / qsim_apply_ops_tiled

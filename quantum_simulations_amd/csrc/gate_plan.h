@@ -55,6 +55,7 @@ struct Tuning {
   int tile_sink_swaps = 1;   // X / CNOT that nothing later in their group touches: swap LDS addresses at write-back (OPC_ASWAP1)
   int tile_group_search = 1; // register groups: try every triple of pending target bits, not only first come
   int tile_had = QSIM_TILE_HAD_DEFAULT;          // uncontrolled c [[1,1],[1,-1]] as add/sub butterflies + one scale per pass (OPC_HAD1 / OPC_SCALE)
+  int tile_unit = 1;         // unconditional real 2x2 with |m0| == |m3|, |m1| == |m2| (RY and its products with X, Y, Z) as unit-diagonal butterflies: OPC_REAL1 -> OPC_UNIT1 on the way to the device (lower_unit_real)
   int dense_form = 1;        // (probe build) qsim_apply_fused_k, k = 3, 4: 1 = k_dense_mfma2 (round 5: whole amplitudes per lane), 0 = the round-4 kernels chosen by dense_mfma; QSIM_DENSE_FORM
   int dense_pf = -1;         // (probe build) k_dense_mfma2's PF (0 none, 1 conditional, 2 unconditional next-group request); QSIM_DENSE_PF
   int dense_groups = 0;      // (probe build) column groups per wave, k <= 4 (product: 4); QSIM_DENSE_GROUPS
@@ -82,6 +83,7 @@ struct Tuning {
     if (const char* e = getenv("QSIM_TILE_SPECIAL")) tile_special = atoi(e);
     if (const char* e = getenv("QSIM_TILE_MERGE_DIAG")) tile_merge_diag = atoi(e);
     if (const char* e = getenv("QSIM_TILE_HAD")) tile_had = atoi(e);
+    if (const char* e = getenv("QSIM_TILE_UNIT")) tile_unit = atoi(e);
     if (const char* e = getenv("QSIM_TILE_GROUP_SEARCH")) tile_group_search = atoi(e);
     if (const char* e = getenv("QSIM_TILE_SINK_SWAPS")) tile_sink_swaps = atoi(e);
     if (const char* e = getenv("QSIM_TILE_DIRECT")) tile_direct = atoi(e);

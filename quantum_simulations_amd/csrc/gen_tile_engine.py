@@ -60,8 +60,8 @@ SWAP_MOV64 = os.environ.get("QS_GEN_SWAP", "") == "mov64"
 OPC = dict(NOP=0, DENSE1=1, SWAP1=10, ANTI1=19, PHASE=28, DENSE2=36, REAL1=45, YLIKE1=54,
            PHASE_NEG=63, PHASE_I=71, PHASE_NI=79, DIAGR=87,
            PRED_OUTER=91, PRED_LANE=92, GROUP=93, GROUP_FIRST=94, END=95, HAD1=96, SCALE=105, ASWAP1=106,
-           GROUP_DIRECT=115, END_DIRECT=116, PRED_OUTER_ZERO=117)
-NENT = 118
+           GROUP_DIRECT=115, END_DIRECT=116, PRED_OUTER_ZERO=117, UNIT1=118)
+NENT = 130
 
 BANK = {"A": 36, "B": 52}                # s32 (the ABI stack pointer) is reserved: banks start at s36
 E = 68                                   # overflow bank s[68:83]
@@ -163,6 +163,38 @@ def body_had(a, bank, pairs):
         bx, by, _ = X(pb)
         a(f"v_fma_f64 {ax}, 2.0, {ax}, -{bx}")
         a(f"v_fma_f64 {ay}, 2.0, {ay}, -{by}")
+
+
+def body_unit(a, bank, pairs, form_a, neg):
+    """real 2x2 with |m0| == |m3| and |m1| == |m2| after its larger entry s went into the pass factor (OPC_SCALE, as the
+    Hadamard's): p, q = doubles 0, 1 of the record, |p|, |q| <= 1, sigma = +-1 is a negate modifier.
+      form D (s = m0): x_a' = x_a + p x_b, x_b' = q x_a + sigma x_b
+      form A (s = m1): x_a' = p x_a + x_b, x_b' = sigma x_a + q x_b
+    One FMA per output component; x_a' goes through a temporary because x_b' needs the old x_a."""
+    p, q = M(bank, 0), M(bank, 1)
+    sg = "-" if neg else ""
+    for i, (pa, pb) in enumerate(pairs):
+        ax, ay, _ = X(pa)
+        bx, by, _ = X(pb)
+        if form_a:
+            a(f"v_fma_f64 {T(2 * i)}, {p}, {ax}, {bx}")
+            a(f"v_fma_f64 {T(2 * i + 1)}, {p}, {ay}, {by}")
+        else:
+            a(f"v_fma_f64 {T(2 * i)}, {p}, {bx}, {ax}")
+            a(f"v_fma_f64 {T(2 * i + 1)}, {p}, {by}, {ay}")
+    for pa, pb in pairs:
+        ax, ay, _ = X(pa)
+        bx, by, _ = X(pb)
+        if form_a:
+            a(f"v_fma_f64 {bx}, {q}, {bx}, {sg}{ax}")
+            a(f"v_fma_f64 {by}, {q}, {by}, {sg}{ay}")
+        else:
+            a(f"v_fma_f64 {bx}, {q}, {ax}, {sg}{bx}")
+            a(f"v_fma_f64 {by}, {q}, {ay}, {sg}{by}")
+    for i, (pa, pb) in enumerate(pairs):
+        ax, ay, _ = X(pa)
+        a(f"v_mov_b64 {ax}, {T(2 * i)}")
+        a(f"v_mov_b64 {ay}, {T(2 * i + 1)}")
 
 
 def body_scale(a, bank):
@@ -385,6 +417,12 @@ def gate_cases():
         for var in range(8):
             cases[OPC[fam] + var] = (f"{fam.lower()}_{var}", lambda a, bank, body=body, var=var: body(a, bank, PHASE_REGS[var]))
     cases[OPC["SCALE"]] = ("scale", body_scale)
+    for j in range(3):                     # entry = UNIT1 + 4 * target register + 2 * (form A) + (sigma = -1)
+        for form_a in (0, 1):
+            for neg in (0, 1):
+                cases[OPC["UNIT1"] + 4 * j + 2 * form_a + neg] = (
+                    f"unit1_{j}{'a' if form_a else 'd'}{'n' if neg else 'p'}",
+                    lambda a, bank, j=j, form_a=form_a, neg=neg: body_unit(a, bank, PAIRS[j], form_a, neg))
     for var in range(4):
         cases[OPC["DIAGR"] + var] = (f"diagr_{var}", lambda a, bank, var=var: body_diagr(a, bank, var))
     for ja in range(3):

@@ -325,7 +325,7 @@ static void rw_frame_sweep(const std::vector<RwOp>& in, bool backward, std::vect
 }
 
 // ---- (d) a diagonal 1q gate into a dense 1q gate on its qubit ------------------------------------------------------------------
-static double rw_record_us(const EngineCosts& ec, const RwOp& o) { return ec.of_family(op_shape(o.f).family); }
+static double rw_record_us(const EngineCosts& ec, const RwOp& o) { return ec.of_family(priced_family(o.f)); }
 // one sweep; true: something was merged (a host that turned complex takes further diagonals in for nothing: sweep again)
 static bool rw_merge_diagonals(std::vector<RwOp>* list, int n_qubits, const EngineCosts& ec) {
   std::vector<RwOp>& ops = *list;

@@ -448,9 +448,7 @@ struct GroupEmitter {
     TileDesc* host = nullptr;
     for (TileGroup& g : *out)
       for (TileDesc& d : g.gates) {
-        const bool fam = (d.opcode >= OPC_REAL1 && d.opcode < OPC_REAL1 + 3) || (d.opcode >= OPC_DENSE1 && d.opcode < OPC_DENSE1 + 3) ||
-                         (d.opcode >= OPC_ANTI1 && d.opcode < OPC_ANTI1 + 3);      // variants 0..2: no register control
-        if (fam && !d.blk_mask && !d.outer_mask && !host) host = &d;
+        if (factor_host_doubles(d.opcode) && !d.blk_mask && !d.outer_mask && !host) host = &d;
       }
     if (host) {
       for (int e = 0; e < host->nd; ++e) host->m[e] *= pass_scale;
@@ -464,3 +462,66 @@ struct GroupEmitter {
     }
   }
 };
+
+// ---- OPC_REAL1 -> OPC_UNIT1 on the way to the device ------------------------------------------------------------------
+// A planned pass image keeps its real 2x2 records as OPC_REAL1 (a multiply and an FMA per output component).  Before
+// run_fused launches (and caches) an image, every UNCONDITIONAL one -- case in header dword 0, so no predicate; variant
+// 0..2, so no register control: every amplitude goes through its matrix -- that unit_real_of accepts is rewritten in
+// place into OPC_UNIT1: same record size, doubles p, q | s, 0.  The product of the factors s goes where the Hadamard
+// factors of the pass went (GroupEmitter::apply_scale): into the matrix of an unconditional dense / real / anti-diagonal
+// record.  A pass without another such record keeps its LAST qualifying record as OPC_REAL1 and folds the factor into it:
+// an OPC_SCALE record is priced as a phase record, and OPC_UNIT1 + OPC_SCALE above OPC_REAL1.  (A pass that has an
+// OPC_SCALE record has no unconditional real 2x2 -- apply_scale would have used it -- so there is nothing to rewrite.)
+// Returns the number of records rewritten.
+static int lower_unit_real(TileArgs* a) {
+  if (!tuning().tile_unit || !tuning().tile_special) return 0;
+  unsigned char* const base = reinterpret_cast<unsigned char*>(a);
+  auto get32 = [&](int at) { uint32_t v; std::memcpy(&v, base + at, 4); return v; };
+  auto put32 = [&](int at, uint32_t v) { std::memcpy(base + at, &v, 4); };
+  std::vector<int> unit;              // offsets of the records to rewrite
+  int host = -1, host_next = 0;
+  for (int off = kTileStreamOff;;) {
+    // (an unconditional record carries its case in header dword 0; a predicated one OPC_PRED_*)
+    const int entry = (int)(get32(off) / 4), next = (int)get32(off + 4);
+    if (entry == OPC_END || entry == OPC_END_DIRECT) break;
+    if (next <= off || next + kEndRecordBytes > kTileArgBytes) return 0;     // (not a stream serialize_pass wrote)
+    if (factor_host_doubles(entry)) {
+      double m[4];
+      for (int e = 0; e < 4; ++e) std::memcpy(&m[e], base + record_double_at(off, next, 4, e), 8);
+      if (entry >= OPC_REAL1 && entry < OPC_REAL1 + 3 && unit_real_of(m)) unit.push_back(off);
+      else if (host < 0) { host = off; host_next = next; }
+    }
+    off = next;
+  }
+  if (host < 0) {
+    if (unit.size() < 2) return 0;
+    host = unit.back();
+    host_next = (int)get32(host + 4);
+    unit.pop_back();
+  }
+  double factor = 1.0;
+  for (int off : unit) {
+    double m[4];
+    const int next = (int)get32(off + 4);
+    for (int e = 0; e < 4; ++e) std::memcpy(&m[e], base + record_double_at(off, next, 4, e), 8);
+    UnitReal u;
+    unit_real_of(m, &u);
+    factor *= u.s;
+    const uint32_t J = get32(off) / 4 - OPC_REAL1;
+    const uint32_t entry = OPC_UNIT1 + 4 * J + 2 * (u.form_a ? 1u : 0u) + (u.neg ? 1u : 0u);
+    put32(off, 4 * entry);
+    put32(off + 12, (4 * entry) << 16);
+    const double out[4] = {u.p, u.q, u.s, 0.0};
+    for (int e = 0; e < 4; ++e) std::memcpy(base + record_double_at(off, next, 4, e), &out[e], 8);
+  }
+  if (unit.empty()) return 0;
+  const int host_nd = factor_host_doubles((int)(get32(host) / 4));
+  for (int e = 0; e < host_nd; ++e) {
+    double v;
+    unsigned char* at = base + record_double_at(host, host_next, host_nd, e);
+    std::memcpy(&v, at, 8);
+    v *= factor;
+    std::memcpy(at, &v, 8);
+  }
+  return (int)unit.size();
+}

@@ -67,7 +67,14 @@ enum : uint8_t {
   OPC_GROUP_DIRECT = QS_ENT_GROUP_DIRECT,   // first group = the layout the kernel loaded the tile in (TileArgs::lay_in):
                                       // x0..x7 arrive in registers, no LDS read
   OPC_END_DIRECT = QS_ENT_END_DIRECT, // last group = the layout the kernel stores in (lay_out): no LDS write-back
-  OPC_PRED_OUTER_ZERO = QS_ENT_PRED_OUTER_ZERO   // gate with index bits outside the tile that must all be 0
+  OPC_PRED_OUTER_ZERO = QS_ENT_PRED_OUTER_ZERO,  // gate with index bits outside the tile that must all be 0
+  OPC_UNIT1 = QS_ENT_UNIT1            // +4*J + 2*form + sign (no control, no predicate): a real 2x2 with |m0| == |m3| and
+                                      // |m1| == |m2| (RY and its products with X, Y, Z) without its larger entry s, which
+                                      // joins the pass factor like the Hadamard's: one FMA per output component
+                                      // form D (s = m0): a' = a + p b, b' = q a +- b;  form A (s = m1): a' = p a + b,
+                                      // b' = +-a + q b          (4: p q | s 0 -- the engine reads p and q only)
+                                      // Never planned: lower_unit_real (tile_groups.h) rewrites OPC_REAL1 records into it
+                                      // on the way to the device.
 };
 // 1q variant: 0..2 = target register bit J, no register control; 3 + 2*J + k = control on the
 // k-th of the two other register bits (ascending)
@@ -400,7 +407,22 @@ struct TileGroup {
   std::vector<TileDesc> gates;
 };
 
-static inline int desc_bytes(int nd) { return 16 + ((8 * nd + 15) & ~15); }
+constexpr int kRecordHeaderBytes = 16;
+constexpr int kRecordHeadDoubles = 6;      // matrix doubles that follow the header; the rest ENDS at the next record
+static inline int desc_bytes(int nd) { return kRecordHeaderBytes + ((8 * nd + 15) & ~15); }
+// byte offset (from the start of the kernel arguments) of matrix double e of a 1q / phase record of nd doubles that starts
+// at `off` and whose successor starts at `next`: what serialize_pass writes and lower_unit_real reads
+static inline int record_double_at(int off, int next, int nd, int e) {
+  return e < kRecordHeadDoubles ? off + kRecordHeaderBytes + 8 * e : next - 8 * (nd - e);
+}
+// matrix doubles of the 1q record families a pass factor can be folded into (complex 2x2, real 2x2, anti-diagonal), by case
+// entry; 0: not such a case.  Variants 0..2 only: no register control -- with no predicate either, every amplitude goes
+// through the matrix (GroupEmitter::apply_scale, lower_unit_real)
+static inline int factor_host_doubles(int opcode) {
+  if (opcode >= OPC_DENSE1 && opcode < OPC_DENSE1 + 3) return 8;
+  if ((opcode >= OPC_REAL1 && opcode < OPC_REAL1 + 3) || (opcode >= OPC_ANTI1 && opcode < OPC_ANTI1 + 3)) return 4;
+  return 0;
+}
 static inline int desc_bytes(const TileDesc& d) { return desc_bytes(d.nd); }
 constexpr int kGroupRecordBytes = 48;
 constexpr int kEndRecordBytes = 16;
@@ -471,9 +493,7 @@ static int serialize_pass(const std::vector<TileGroup>& groups, TileArgs* a) {
       if (d.opcode >= OPC_DENSE2 && d.opcode < OPC_DENSE2 + 9) {
         std::memcpy(base + off + bytes - 256, d.m, 256);
       } else {
-        const int head = d.nd < 6 ? d.nd : 6;
-        std::memcpy(base + off + 16, d.m, 8 * (size_t)head);
-        if (d.nd > 6) std::memcpy(base + off + bytes - 8 * (d.nd - 6), d.m + 6, 8 * (size_t)(d.nd - 6));
+        for (int e = 0; e < d.nd; ++e) std::memcpy(base + record_double_at(off, off + bytes, d.nd, e), &d.m[e], 8);
       }
       off += bytes;
       ++nrec;

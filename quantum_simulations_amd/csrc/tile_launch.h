@@ -317,6 +317,7 @@ static int run_fused(qsim_chunk* c, const std::vector<FusedOp>& ops, const RawOp
   }
   std::vector<CachedPass> made;
   const int rc = plan_fused(c->k, ops, n_passes, [&](TileArgs& a, int T, double alg_bytes, bool first, bool last) {
+    lower_unit_real(&a);
     if (cacheable) made.push_back(CachedPass{a, T, alg_bytes});      // (before buffers and layouts go in)
     prepare_planned(c, a, T, first, last, io);
     return sink(a, T, alg_bytes, last);

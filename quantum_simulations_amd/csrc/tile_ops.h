@@ -156,6 +156,35 @@ static int op_cost(const FusedOp& o) {
 }
 constexpr int kRecordCost = 8;                 // a record's fetch + dispatch, in the same unit
 
+// A real 2x2 [[m0, m1], [m2, m3]] as a unit-diagonal butterfly (OPC_UNIT1): |m0| == |m3| and |m1| == |m2| bitwise -- RY and
+// what the rewrite makes of it with an X, Y or Z -- and not the Hadamard shape, which OPC_HAD1 has.  The larger of m0, m1 is
+// taken out as s (it joins the pass factor); the ratios that stay have magnitude <= 1 and the fourth one is +-1 EXACTLY:
+//   form D, |m0| >= |m1|: s = m0, p = m1 / m0, q = m2 / m0, sigma = m3 / m0   a' = a + p b,  b' = q a + sigma b
+//   form A, otherwise:    s = m1, p = m0 / m1, q = m3 / m1, sigma = m2 / m1   a' = p a + b,  b' = sigma a + q b
+struct UnitReal { bool form_a, neg; double s, p, q; };
+static bool unit_real_of(const double m[4], UnitReal* u = nullptr) {
+  if (std::fabs(m[0]) != std::fabs(m[3]) || std::fabs(m[1]) != std::fabs(m[2])) return false;
+  if (m[0] == m[1] && m[0] == m[2] && m[0] == -m[3]) return false;
+  const bool form_a = !(std::fabs(m[0]) >= std::fabs(m[1]));
+  const double s = form_a ? m[1] : m[0];
+  if (s == 0 || !std::isfinite(s)) return false;
+  if (u) {
+    u->form_a = form_a;
+    u->s = s;
+    u->p = (form_a ? m[0] : m[1]) / s;
+    u->q = (form_a ? m[3] : m[2]) / s;
+    u->neg = std::signbit(form_a ? m[2] : m[3]) != std::signbit(s);
+  }
+  return true;
+}
+// The family an uncontrolled op's record is PRICED as: what reaches the device (lower_unit_real, tile_groups.h).
+static int priced_family(const FusedOp& o) {
+  const int fam = op_shape(o).family;
+  if (fam != OPC_REAL1 || !tuning().tile_unit || o.control >= 0) return fam;
+  const double m[4] = {o.m[0].x, o.m[1].x, o.m[2].x, o.m[3].x};
+  return unit_real_of(m) ? OPC_UNIT1 : fam;
+}
+
 // The MEASURED price of the gate engine (runner/engine_cost_model.json, fitted by tools/fit_engine_cost_model.py to one-pass
 // probes on MI355X): microseconds a record of each kind adds to a pass of the fitted state size once the pass is past the
 // knee -- the engine time a pass hides under its memory time.  Handed in by the caller (QSIM_ENGINE_COST_* of
@@ -167,6 +196,7 @@ struct EngineCosts {
       case OPC_DENSE1: return v[QSIM_ENGINE_COST_DENSE1];
       case OPC_REAL1: return v[QSIM_ENGINE_COST_REAL1];
       case OPC_HAD1: return v[QSIM_ENGINE_COST_HAD1];
+      case OPC_UNIT1: return v[QSIM_ENGINE_COST_UNIT1];
       case OPC_SWAP1: return v[QSIM_ENGINE_COST_SWAP1];
       case OPC_ASWAP1: return v[QSIM_ENGINE_COST_ASWAP1];
       case OPC_ANTI1: case OPC_YLIKE1: return v[QSIM_ENGINE_COST_ANTI1];
@@ -181,14 +211,20 @@ struct EngineCosts {
   // family of a written record's case entry (families are runs of entries: the last base at or below it)
   static int family_of_entry(int opcode) {
     static const int bases[] = {OPC_DENSE1, OPC_SWAP1, OPC_ANTI1, OPC_PHASE, OPC_DENSE2, OPC_REAL1, OPC_YLIKE1, OPC_PHASE_NEG,
-                                OPC_PHASE_I, OPC_PHASE_NI, OPC_DIAGR, OPC_HAD1, OPC_SCALE, OPC_ASWAP1};
+                                OPC_PHASE_I, OPC_PHASE_NI, OPC_DIAGR, OPC_HAD1, OPC_SCALE, OPC_ASWAP1, OPC_UNIT1};
     int best = OPC_DENSE1;
     for (int b : bases) if (b <= opcode && b > best) best = b;
     return best;
   }
+  // an unconditional real 2x2 of the unit-diagonal family reaches the device as OPC_UNIT1 (lower_unit_real) ...
+  static bool lowers_to_unit(const TileDesc& d) {
+    return tuning().tile_unit && tuning().tile_special && d.opcode >= OPC_REAL1 && d.opcode < OPC_REAL1 + 3 && !d.blk_mask && !d.outer_mask &&
+           unit_real_of(d.m);
+  }
   // microseconds of one written record at the fitted state size
   double of_record(const TileDesc& d) const {
-    const int fam = family_of_entry(d.opcode);
+    int fam = family_of_entry(d.opcode);
+    if (lowers_to_unit(d)) fam = OPC_UNIT1;
     const bool one_q = fam == OPC_DENSE1 || fam == OPC_SWAP1 || fam == OPC_ANTI1 || fam == OPC_REAL1 || fam == OPC_YLIKE1 || fam == OPC_ASWAP1;
     return of_family(fam) * (d.blk_mask ? v[QSIM_ENGINE_COST_PRED_LANE] : 1.0) * (d.outer_mask ? v[QSIM_ENGINE_COST_PRED_OUTER] : 1.0) *
            ((one_q && d.opcode - fam >= 3) ? v[QSIM_ENGINE_COST_REG_CTRL] : 1.0);
@@ -198,10 +234,16 @@ struct EngineCosts {
     double us = v[QSIM_ENGINE_COST_FIXED_US];
     if (!groups.empty() && tuning().tile_direct)          // (full tiles: an end above the line bits skips its LDS trip)
       us += v[QSIM_ENGINE_COST_DIRECT_END] * ((groups.front().s[0] >= kTileLow) + (groups.back().s[0] >= kTileLow));
+    bool host = false, unit = false;     // ... except one that has to carry the factors: a pass with no other record to fold them into
     for (const TileGroup& g : groups) {
       us += v[QSIM_ENGINE_COST_GROUP];
-      for (const TileDesc& d : g.gates) us += of_record(d);
+      for (const TileDesc& d : g.gates) {
+        us += of_record(d);
+        if (lowers_to_unit(d)) unit = true;
+        else if (factor_host_doubles(d.opcode) && !d.blk_mask && !d.outer_mask) host = true;
+      }
     }
+    if (unit && !host) us += v[QSIM_ENGINE_COST_REAL1] - v[QSIM_ENGINE_COST_UNIT1];
     return us * std::ldexp(1.0, k - (int)v[QSIM_ENGINE_COST_FIT_QUBITS]);
   }
 };

@@ -233,7 +233,7 @@ static int plan_balance(int k, const std::vector<FusedOp>& ops_in, const std::ve
   for (size_t p = 0; p + 1 < n_pass; ++p)
     for (size_t i = n_ops; i-- > 0 && slack[p] < 0;) {
       if (pass_of[i] != (int32_t)p || window[i] <= (int32_t)p) continue;
-      const double us = ec.of_family(op_shape(ops[i]).family) * scale;
+      const double us = ec.of_family(priced_family(ops[i])) * scale;
       size_t to = p;
       for (size_t q = p + 1; q <= (size_t)window[i]; ++q) if (to == p || slack[q] > slack[to]) to = q;
       if (slack[to] < us) continue;

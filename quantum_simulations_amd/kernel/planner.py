@@ -1,5 +1,5 @@
 """The host planner of libqsim_hip.so in Python: what the pass builder would do with an op list, without a device
-(csrc/abi_plan.h: qsim_plan_ops, qsim_plan_ops_tiled, qsim_plan_ops_placed, qsim_plan_balance, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass,
+(csrc/abi_plan.h: qsim_plan_ops, qsim_lower_pass_images, qsim_plan_ops_tiled, qsim_plan_ops_placed, qsim_plan_balance, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass,
 qsim_rewrite_ops_priced; csrc/tile_launch.h: qsim_tiles_per_workgroup; csrc/abi_rotation.h: qsim_plan_pauli_rotations).
 
 A thin binding.  `ops` is [(qubits, U), ...] or the tuple `pack_ops` returns (`device.as_packed`).  Return codes become
@@ -71,6 +71,15 @@ def plan_ops(n: int, ops, tiles=None, earliest=None) -> np.ndarray:
             _lib.check(rc)
             return images[:count]
         room *= 2
+
+
+def lower_images(images) -> tuple:
+    """(the images as the device gets them, records rewritten): qsim_lower_pass_images on a copy of planned images -- the
+    unconditional real 2x2 records of the unit-diagonal family as OPC_UNIT1, their factors folded into the pass."""
+    out = np.ascontiguousarray(images, dtype=PASS_IMAGE).copy()
+    count = C.c_int32()
+    _lib.check(_lib.load().qsim_lower_pass_images(ptr(out), len(out), C.byref(count)))
+    return out, count.value
 
 
 def pass_count(n: int, ops, tiles=None, earliest=None) -> int:

@@ -17,7 +17,7 @@ import numpy as np
 _MODEL_PATH = Path(__file__).resolve().parent / "engine_cost_model.json"
 # QSIM_ENGINE_COST_* (include/qsim_hip.h), in order
 ENTRIES = ("fixed_us", "group", "dense1", "real1", "had1", "swap1", "aswap1", "anti1", "phase", "phase_neg", "phase_i", "diagr",
-           "dense2", "pred_lane", "pred_outer", "reg_ctrl", "direct_end", "fit_qubits")
+           "dense2", "pred_lane", "pred_outer", "reg_ctrl", "direct_end", "fit_qubits", "unit1")
 _table: np.ndarray | None = None
 
 

@@ -90,7 +90,12 @@ def main():
              "had1": c["HAD1"], "swap1": c["SWAP1"], "aswap1": c["ASWAP1"], "anti1": round(c["REAL1"] * 40 / 32, 2),
              "phase": c["PHASE"], "phase_neg": c["PHASE_NEG"], "phase_i": c["PHASE_I"], "diagr": c["DIAGR"],
              "dense2": round(c["DENSE1"] * 144 / 68, 2), "pred_lane": factor["lane"], "pred_outer": factor["outer"],
-             "reg_ctrl": factor["regctrl"], "direct_end": c["direct_end"]}
+             "reg_ctrl": factor["regctrl"], "direct_end": c["direct_end"],
+             # (the samples count records in planned images, where a unit-diagonal real 2x2 is still REAL1: its price is
+             # REAL1's times the ratio of the two one-pass slopes, measured with the lowering on and off: 0.75 - 0.78)
+             # TODO: fit it as a family of its own (sample with the lowering off for REAL1 and on for UNIT1); 0.75 is the
+             # lower end of profiles/r26a_ab_unit_real.txt section 1 (tools/gate_cost_probe.py, lowering on / off)
+             "unit1": round(c["REAL1"] * 0.75, 2)}
     calibration = None
     ratios = []
     for path in sys.argv[4:]:
