@@ -21,12 +21,12 @@ from __future__ import annotations
 
 import numpy as np
 
-from quantum_simulations_amd import evolution
+from quantum_simulations_amd.evolution import check_pair, n_qubits, to_physical
 from quantum_simulations_amd.observable import PauliSum
 
 
-def _as_sum(obs, n_qubits=None) -> PauliSum:
-    return obs if isinstance(obs, PauliSum) else PauliSum(obs, n_qubits=n_qubits)
+def _as_sum(obs, n=None) -> PauliSum:
+    return obs if isinstance(obs, PauliSum) else PauliSum(obs, n_qubits=n)
 
 
 def _from_masks(x, z, coeffs, n_qubits: int) -> PauliSum:
@@ -65,9 +65,26 @@ def split(obs) -> tuple[PauliSum, PauliSum]:
 
 
 def _physical(chunk, l2p, obs) -> tuple[np.ndarray, np.ndarray]:
-    n = chunk.k if l2p is None else len(l2p)
-    z, co = diagonal_part(_as_sum(obs, n))
-    return evolution.to_physical(np.zeros_like(z), z, l2p)[1], co
+    z, co = diagonal_part(_as_sum(obs, n_qubits(chunk, l2p)))
+    return to_physical(np.zeros_like(z), z, l2p)[1], co
+
+
+def _angles(gammas, betas, what: str) -> tuple[np.ndarray, np.ndarray]:
+    """The validated (gammas, betas) of `qaoa` and `qaoa_gradient`: float64, flat, one beta per gamma, all finite."""
+    gammas = np.asarray(gammas, dtype=np.float64).reshape(-1)
+    betas = np.asarray(betas, dtype=np.float64).reshape(-1)
+    if gammas.shape != betas.shape:
+        raise ValueError(f"{what}: {gammas.size} gammas, {betas.size} betas")
+    if not (np.all(np.isfinite(gammas)) and np.all(np.isfinite(betas))):
+        raise ValueError(f"{what}: an angle is not finite")
+    return gammas, betas
+
+
+def _mixer_masks(chunk, l2p) -> tuple[np.ndarray, np.ndarray]:
+    """(x, z) masks over PHYSICAL index bits of the mixer strings X_q, one per logical qubit."""
+    n = n_qubits(chunk, l2p)
+    mx = to_physical(np.array([1 << q for q in range(n)], dtype=np.uint64), np.zeros(n, dtype=np.uint64), l2p)[0]
+    return mx, np.zeros(n, dtype=np.uint64)
 
 
 def apply_phase(chunk, l2p, obs, gamma) -> int:
@@ -99,21 +116,14 @@ def qaoa(chunk, l2p, cost, gammas, betas) -> int:
     `DeviceChunk.apply_pauli_rotations`.  NO factor 1/2 anywhere: the mixer on a qubit is the gate RX(2 beta), and a
     cost term c Z_a Z_b contributes exp(-i gamma c Z_a Z_b) = RZZ(2 gamma c).  `cost`: a diagonal Pauli sum over LOGICAL
     qubits.  The state does not move.  Returns the HBM passes made."""
-    gammas = np.asarray(gammas, dtype=np.float64).reshape(-1)
-    betas = np.asarray(betas, dtype=np.float64).reshape(-1)
-    if gammas.shape != betas.shape:
-        raise ValueError(f"qaoa: {gammas.size} gammas, {betas.size} betas")
-    if not (np.all(np.isfinite(gammas)) and np.all(np.isfinite(betas))):
-        raise ValueError("qaoa: an angle is not finite")
-    n = chunk.k if l2p is None else len(l2p)
+    gammas, betas = _angles(gammas, betas, "qaoa")
     z, co = _physical(chunk, l2p, cost)
-    mx = evolution.to_physical(np.array([1 << q for q in range(n)], dtype=np.uint64), np.zeros(n, dtype=np.uint64), l2p)[0]
-    mz = np.zeros(n, dtype=np.uint64)
+    mx, mz = _mixer_masks(chunk, l2p)
     passes = 0
     for gamma, beta in zip(gammas, betas):
         chunk.apply_diagonal_phase(z, co, float(gamma))
         passes += 1 if z.size else 0
-        passes += chunk.apply_pauli_rotations(mx, mz, np.full(n, float(beta)))
+        passes += chunk.apply_pauli_rotations(mx, mz, np.full(mx.size, float(beta)))
     return passes
 
 
@@ -152,27 +162,17 @@ def qaoa_gradient(chunk, work, l2p, cost, gammas, betas) -> tuple[float, np.ndar
     lambda pulled back to the same point; the same for gamma and C.)  Conventions as in `hamiltonian.adjoint_gradient`:
     NO factor 1/2, E and the derivatives unnormalised; `chunk` holds its state again on return up to rounding, `work` (a
     second chunk of the same size) is scratch."""
-    if chunk is work:
-        raise ValueError("qaoa_gradient: two different chunks expected, got the same one twice")
-    if chunk.k != work.k:
-        raise ValueError(f"qaoa_gradient: chunks of {chunk.k} and {work.k} index bits")
-    gammas = np.asarray(gammas, dtype=np.float64).reshape(-1)
-    betas = np.asarray(betas, dtype=np.float64).reshape(-1)
-    if gammas.shape != betas.shape:
-        raise ValueError(f"qaoa_gradient: {gammas.size} gammas, {betas.size} betas")
-    if not (np.all(np.isfinite(gammas)) and np.all(np.isfinite(betas))):
-        raise ValueError("qaoa_gradient: an angle is not finite")
-    n = chunk.k if l2p is None else len(l2p)
+    check_pair(chunk, work, "qaoa_gradient")
+    gammas, betas = _angles(gammas, betas, "qaoa_gradient")
     z, co = _physical(chunk, l2p, cost)
-    mx = evolution.to_physical(np.array([1 << q for q in range(n)], dtype=np.uint64), np.zeros(n, dtype=np.uint64), l2p)[0]
-    mz = np.zeros(n, dtype=np.uint64)
+    mx, mz = _mixer_masks(chunk, l2p)
     qaoa(chunk, l2p, cost, gammas, betas)
     energy = chunk.diagonal_moments(z, co)[1]
     work.apply_diagonal_sum(chunk, z, co, False)
     dgammas, dbetas = np.zeros(gammas.size), np.zeros(betas.size)
     for l in range(gammas.size - 1, -1, -1):
         dbetas[l] = 2.0 * float(np.sum(chunk.overlap_pauli(work, mx, mz).imag))
-        back = np.full(n, -float(betas[l]))
+        back = np.full(mx.size, -float(betas[l]))
         chunk.apply_pauli_rotations(mx, mz, back)
         work.apply_pauli_rotations(mx, mz, back)
         dgammas[l] = 2.0 * chunk.overlap_diagonal(work, z, co)[1].imag

@@ -80,6 +80,19 @@ def trotter_rotations(obs, t, steps: int = 1, order: int = 1) -> tuple[np.ndarra
     return np.tile(x, steps), np.tile(z, steps), np.tile(th, steps)
 
 
+def n_qubits(chunk, l2p) -> int:
+    """Logical qubits of a chunk in the layout l2p (None: identity); with `check_pair`, shared by the physics modules."""
+    return chunk.k if l2p is None else len(l2p)
+
+
+def check_pair(a, b, what: str) -> None:
+    """The two chunks of a call: different objects of the same size."""
+    if a is b:
+        raise ValueError(f"{what}: two different chunks expected, got the same one twice")
+    if a.k != b.k:
+        raise ValueError(f"{what}: chunks of {a.k} and {b.k} index bits")
+
+
 def to_physical(x, z, l2p) -> tuple[np.ndarray, np.ndarray]:
     """Masks over logical qubits -> masks over PHYSICAL index bits: logical qubit q lives on bit l2p[q] (None: identity)."""
     x = np.asarray(x, dtype=np.uint64).reshape(-1)
@@ -174,5 +187,4 @@ def apply_rotations(chunk, l2p, rotations, fuse_diagonal: bool = False) -> int:
 def evolve(chunk, l2p, obs, t, steps: int = 1, order: int = 1, fuse_diagonal: bool = False) -> int:
     """`trotter_rotations(obs, t, steps, order)` applied to the chunk through its layout (`fuse_diagonal`: as in
     `apply_rotations`).  Returns the HBM passes made."""
-    n = chunk.k if l2p is None else len(l2p)
-    return apply_rotations(chunk, l2p, trotter_rotations(as_pauli_sum(obs, n), t, steps, order), fuse_diagonal)
+    return apply_rotations(chunk, l2p, trotter_rotations(as_pauli_sum(obs, n_qubits(chunk, l2p)), t, steps, order), fuse_diagonal)

@@ -31,17 +31,6 @@ from quantum_simulations_amd.observable import as_pauli_sum
 DIAGONAL_MIN_TERMS = 24
 
 
-def _n_qubits(chunk, l2p) -> int:
-    return chunk.k if l2p is None else len(l2p)
-
-
-def _pair(a, b, what: str) -> None:
-    if a is b:
-        raise ValueError(f"{what}: two different chunks expected, got the same one twice")
-    if a.k != b.k:
-        raise ValueError(f"{what}: chunks of {a.k} and {b.k} index bits")
-
-
 class Plan:
     """The arrays of one H for `apply_planned`, over PHYSICAL index bits: (x, z, coeffs) of the terms that go through
     `apply_pauli_sum` and, when the Z-only terms take the diagonal pass, (diag_z, diag_coeffs), else None."""
@@ -67,7 +56,7 @@ def apply_planned(dst, src, p: Plan) -> int:
     """dst := H src for the H of a `plan`.  Without a diagonal part: `apply_pauli_sum`.  With one: the rest through
     `apply_pauli_sum`, which writes, then the diagonal pass accumulates; with no rest the diagonal pass writes.  Returns
     the HBM passes made."""
-    _pair(dst, src, "apply")
+    evolution.check_pair(dst, src, "apply")
     if p.diag_z is None:
         return dst.apply_pauli_sum(src, p.x, p.z, p.coeffs)
     passes = dst.apply_pauli_sum(src, p.x, p.z, p.coeffs) if p.x.size else 0
@@ -79,7 +68,7 @@ def apply(dst, src, l2p, obs, fuse_diagonal: bool = False) -> int:
     """dst := H src for a Pauli sum over LOGICAL qubits (observable.PauliSum or what it accepts); what dst held does not
     matter, src is only read.  `fuse_diagonal`: the Z-only terms go through ONE diagonal pass whatever their number, when
     there are at least DIAGONAL_MIN_TERMS of them (`plan`).  Returns the HBM passes made."""
-    return apply_planned(dst, src, plan(_n_qubits(src, l2p), l2p, obs, fuse_diagonal))
+    return apply_planned(dst, src, plan(evolution.n_qubits(src, l2p), l2p, obs, fuse_diagonal))
 
 
 def matrix_elements(ket, bra, l2p, obs) -> np.ndarray:
@@ -87,7 +76,7 @@ def matrix_elements(ket, bra, l2p, obs) -> np.ndarray:
     coefficient; `bra` may be `ket`."""
     if ket.k != bra.k:
         raise ValueError(f"matrix_elements: chunks of {ket.k} and {bra.k} index bits")
-    obs = as_pauli_sum(obs, _n_qubits(ket, l2p))
+    obs = as_pauli_sum(obs, evolution.n_qubits(ket, l2p))
     x, z = obs.masks(l2p)
     return ket.overlap_pauli(bra, x, z)
 
@@ -96,8 +85,8 @@ def variance(chunk, work, l2p, obs, fuse_diagonal: bool = False) -> float:
     """<psi|H^2|psi> - <psi|H|psi>^2 as norm2(H psi) - <H>^2, unnormalised like every readout here (for a state of norm
     1 it is the energy variance).  `work` := H psi: a second chunk of the same size, overwritten.  `fuse_diagonal`: as
     in `apply`."""
-    _pair(work, chunk, "variance")
-    obs = as_pauli_sum(obs, _n_qubits(chunk, l2p))
+    evolution.check_pair(work, chunk, "variance")
+    obs = as_pauli_sum(obs, evolution.n_qubits(chunk, l2p))
     apply(work, chunk, l2p, obs, fuse_diagonal)
     mean = chunk.expectation(obs, l2p=None if l2p is None else list(l2p))
     return work.norm2() - mean * mean
@@ -116,11 +105,11 @@ def adjoint_gradient(chunk, work, l2p, rotations, obs) -> tuple[float, np.ndarra
     that is one overlap and two single-rotation passes per parameter.  (dE/dtheta_j = 2 Re <psi|H R_{n-1} .. R_{j+1}
     (-i P_j) R_j .. R_0|psi_0> = 2 Re (-i <lambda|P_j|psi>).)  On return `chunk` holds psi_0 again up to rounding and
     `work` is scratch.  E and the gradient are unnormalised, like every readout here."""
-    _pair(work, chunk, "adjoint_gradient")
+    evolution.check_pair(work, chunk, "adjoint_gradient")
     x, z, th = evolution.as_rotation_arrays(rotations)
     if not np.all(np.isfinite(th)):
         raise ValueError("adjoint_gradient: an angle is not finite")
-    obs = as_pauli_sum(obs, _n_qubits(chunk, l2p))
+    obs = as_pauli_sum(obs, evolution.n_qubits(chunk, l2p))
     px, pz = evolution.to_physical(x, z, l2p)
     chunk.apply_pauli_rotations(px, pz, th)
     energy = chunk.expectation(obs, l2p=None if l2p is None else list(l2p))

@@ -20,6 +20,18 @@ def _mat_ptr(U: np.ndarray, dim: int):
     return m, _lib.ptr(m)
 
 
+_TERM_ARRAYS = {"x": (np.uint64, "x masks"), "z": (np.uint64, "z masks"), "coeffs": (np.float64, "coefficients"), "angles": (np.float64, "angles")}
+
+
+def _term_arrays(call: str, **arrays) -> list:
+    """The per-term arguments of a Pauli call (keywords of _TERM_ARRAYS, in the order given), each contiguous in its dtype
+    and flat; ValueError "<call>: N x masks, N z masks, ..." unless they are all of one length."""
+    out = [np.ascontiguousarray(a, dtype=_TERM_ARRAYS[kind][0]).reshape(-1) for kind, a in arrays.items()]
+    if len({a.size for a in out}) > 1:
+        raise ValueError(f"{call}: " + ", ".join(f"{a.size} {_TERM_ARRAYS[kind][1]}" for kind, a in zip(arrays, out)))
+    return out
+
+
 def pack_ops(ops) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """[(qubits, U), ...] -> (nq int32[n], qubits int32[2n], mats float64[32n])."""
     n = len(ops)
@@ -199,11 +211,7 @@ class DeviceChunk:
         of this chunk (x: X or Y, z: Z or Y).  No factor 1/2: exp(-i theta P) = cos(theta) I - i sin(theta) P
         (qsim_apply_pauli_rotations: up to 1024 consecutive rotations per read-modify-write pass, enqueued on the chunk's
         stream).  Returns the passes made, also kept in `self.last_rotation_passes`."""
-        x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
-        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
-        th = np.ascontiguousarray(thetas, dtype=np.float64).reshape(-1)
-        if not x.shape == z.shape == th.shape:
-            raise ValueError(f"apply_pauli_rotations: {x.size} x masks, {z.size} z masks, {th.size} angles")
+        x, z, th = _term_arrays("apply_pauli_rotations", x=x_masks, z=z_masks, angles=thetas)
         passes = C.c_int(0)
         _lib.check(_lib.load().qsim_apply_pauli_rotations(self._h, int(x.size), _lib.ptr(x), _lib.ptr(z), _lib.ptr(th), C.byref(passes)))
         self.last_rotation_passes = passes.value
@@ -214,20 +222,14 @@ class DeviceChunk:
         of this chunk (0: the identity): psi_i *= exp(-i gamma E(i)), E(i) = sum_t coeffs[t] (-1)^popcount(i & z_t).  No
         factor 1/2.  ONE read-modify-write pass whatever the number of terms (at most 16384), enqueued on the chunk's
         stream (qsim_apply_diagonal_phase); no terms: nothing is launched."""
-        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
-        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
-        if z.shape != co.shape:
-            raise ValueError(f"apply_diagonal_phase: {z.size} z masks, {co.size} coefficients")
+        z, co = _term_arrays("apply_diagonal_phase", z=z_masks, coeffs=coeffs)
         _lib.check(_lib.load().qsim_apply_diagonal_phase(self._h, int(z.size), _lib.ptr(z), _lib.ptr(co), float(gamma)))
 
     def diagonal_moments(self, z_masks, coeffs) -> tuple:
         """(sum |psi_i|^2, sum |psi_i|^2 E(i), sum |psi_i|^2 E(i)^2), unnormalised, for the diagonal D of
         `apply_diagonal_phase`: ONE read-only pass whatever the number of terms, a fixed summation order -- two calls give
         the same bits (qsim_diagonal_moments).  No terms: (norm2, 0, 0)."""
-        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
-        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
-        if z.shape != co.shape:
-            raise ValueError(f"diagonal_moments: {z.size} z masks, {co.size} coefficients")
+        z, co = _term_arrays("diagonal_moments", z=z_masks, coeffs=coeffs)
         out = np.empty(3, dtype=np.float64)
         _lib.check(_lib.load().qsim_diagonal_moments(self._h, int(z.size), _lib.ptr(z), _lib.ptr(co), _lib.ptr(out)))
         return float(out[0]), float(out[1]), float(out[2])
@@ -237,20 +239,14 @@ class DeviceChunk:
         PHYSICAL index bits): self_i (+)= E(i) src_i.  ONE pass whatever the number of terms, enqueued on the chunk's
         stream (qsim_apply_diagonal_sum).  `src` may be `self` when writing (psi := D psi in place); any other overlap is
         refused.  No terms: self := 0 when writing, untouched when accumulating."""
-        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
-        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
-        if z.shape != co.shape:
-            raise ValueError(f"apply_diagonal_sum: {z.size} z masks, {co.size} coefficients")
+        z, co = _term_arrays("apply_diagonal_sum", z=z_masks, coeffs=coeffs)
         _lib.check(_lib.load().qsim_apply_diagonal_sum(self._h, src._h, int(z.size), _lib.ptr(z), _lib.ptr(co), 1 if accumulate else 0))
 
     def overlap_diagonal(self, bra: "DeviceChunk", z_masks, coeffs) -> tuple:
         """(<bra|self>, <bra|D|self>), unnormalised, for the diagonal D of `apply_diagonal_phase` (`self` is the ket):
         sum_i conj(bra_i) self_i and sum_i conj(bra_i) E(i) self_i from ONE read-only pass over both chunks, a fixed
         summation order -- two calls give the same bits (qsim_overlap_diagonal).  `bra` may be `self`."""
-        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
-        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
-        if z.shape != co.shape:
-            raise ValueError(f"overlap_diagonal: {z.size} z masks, {co.size} coefficients")
+        z, co = _term_arrays("overlap_diagonal", z=z_masks, coeffs=coeffs)
         out = np.empty(4, dtype=np.float64)
         _lib.check(_lib.load().qsim_overlap_diagonal(self._h, bra._h, int(z.size), _lib.ptr(z), _lib.ptr(co), _lib.ptr(out)))
         return complex(out[0], out[1]), complex(out[2], out[3])
@@ -260,11 +256,7 @@ class DeviceChunk:
         read and may not overlap it); P_t as masks of PHYSICAL index bits (x: X or Y, z: Z or Y), real finite
         coefficients (qsim_apply_pauli_sum: the first pass writes, the later ones accumulate, enqueued on the chunk's
         stream).  No terms: self := 0.  Returns the passes made, also kept in `self.last_pauli_sum_passes`."""
-        x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
-        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
-        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
-        if not x.shape == z.shape == co.shape:
-            raise ValueError(f"apply_pauli_sum: {x.size} x masks, {z.size} z masks, {co.size} coefficients")
+        x, z, co = _term_arrays("apply_pauli_sum", x=x_masks, z=z_masks, coeffs=coeffs)
         passes = C.c_int(0)
         _lib.check(_lib.load().qsim_apply_pauli_sum(self._h, src._h, int(x.size), _lib.ptr(x), _lib.ptr(z), _lib.ptr(co), C.byref(passes)))
         self.last_pauli_sum_passes = passes.value
@@ -274,10 +266,7 @@ class DeviceChunk:
         """<bra|P_t|self> of Pauli strings given as masks of PHYSICAL index bits (`self` is the ket), unnormalised,
         complex128 (qsim_overlap_pauli: read-only passes over both chunks, a fixed summation order -- two calls give the
         same bits).  `bra` may be `self`.  `self.last_overlap_passes` = the passes that ran."""
-        x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
-        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
-        if x.shape != z.shape:
-            raise ValueError(f"overlap_pauli: {x.size} x masks, {z.size} z masks")
+        x, z = _term_arrays("overlap_pauli", x=x_masks, z=z_masks)
         out = np.empty(x.size, dtype=np.complex128)
         passes = C.c_int(0)
         _lib.check(_lib.load().qsim_overlap_pauli(self._h, bra._h, int(x.size), _lib.ptr(x), _lib.ptr(z), _lib.ptr(out), C.byref(passes)))
@@ -436,10 +425,7 @@ class DeviceChunk:
         """<psi|P_t|psi> of Pauli strings given as masks of PHYSICAL index bits of this chunk (x: X or Y, z: Z or Y),
         unnormalised (qsim_expectation_pauli: read-only passes on the device, a fixed summation order -- two calls give
         the same bits).  `self.last_expectation_passes` = the passes that ran."""
-        x = np.ascontiguousarray(x_masks, dtype=np.uint64).reshape(-1)
-        z = np.ascontiguousarray(z_masks, dtype=np.uint64).reshape(-1)
-        if x.shape != z.shape:
-            raise ValueError(f"expectation_pauli: {x.size} x masks, {z.size} z masks")
+        x, z = _term_arrays("expectation_pauli", x=x_masks, z=z_masks)
         out = np.empty(x.size, dtype=np.float64)
         passes = C.c_int(0)
         _lib.check(_lib.load().qsim_expectation_pauli(self._h, int(x.size), _lib.ptr(x), _lib.ptr(z), _lib.ptr(out), C.byref(passes)))
@@ -517,7 +503,6 @@ class DeviceChunk:
     def unpack_half(self, bit: int, value: int, buf: "DeviceChunk") -> None:
         _lib.check(_lib.load().qsim_unpack_half(self._h, bit, value, buf._h))
 
-
     def pack_bits(self, bits, pattern: int, buf: "DeviceChunk", buf_offset: int = 0) -> None:
         b = np.asarray(bits, dtype=np.int32)
         _lib.check(_lib.load().qsim_pack_bits(self._h, len(b), _lib.ptr(b), int(pattern), buf._h, int(buf_offset)))
@@ -525,6 +510,7 @@ class DeviceChunk:
     def unpack_bits(self, bits, pattern: int, buf: "DeviceChunk", buf_offset: int = 0) -> None:
         b = np.asarray(bits, dtype=np.int32)
         _lib.check(_lib.load().qsim_unpack_bits(self._h, len(b), _lib.ptr(b), int(pattern), buf._h, int(buf_offset)))
+
     def pack_all(self, bits, buf: "DeviceChunk", skip_pattern: int = -1, piece: int = 0, n_pieces: int = 1) -> None:
         """Every slab of the all-to-all re-layout in one pass (qsim_pack_all); `piece` of `n_pieces`
         = the same contiguous sub-range of every slab."""

@@ -21,12 +21,9 @@ from __future__ import annotations
 import numpy as np
 
 from quantum_simulations_amd import hamiltonian
+from quantum_simulations_amd.evolution import n_qubits
 
 GROUP = 4            # sources, and bras, of one `lincomb` call
-
-
-def _n_qubits(chunk, l2p) -> int:
-    return chunk.k if l2p is None else len(l2p)
 
 
 def _check_chunks(chunk, work, m: int, least: int, what: str) -> None:
@@ -105,7 +102,7 @@ def _tridiagonal(alphas, betas, k: int):
 
 def _setup(chunk, l2p, obs, fuse_diagonal: bool):
     """(the plan of H for `_apply_h`, sum |c_t|)"""
-    h = hamiltonian.plan(_n_qubits(chunk, l2p), l2p, obs, fuse_diagonal)
+    h = hamiltonian.plan(n_qubits(chunk, l2p), l2p, obs, fuse_diagonal)
     scale = float(np.sum(np.abs(h.coeffs))) + (float(np.sum(np.abs(h.diag_coeffs))) if h.diag_z is not None else 0.0)
     return h, scale
 

@@ -1,5 +1,5 @@
 """Readout of a chunk whose LOGICAL qubit q lives on index bit l2p[q] (None: identity): the three calls that
-`SingleGpuEngine` and `single_node` share.  The state does not move: the layout goes into the masks, the qubit lists
+`state_calls.StateCalls` makes for `SingleGpuEngine` and `single_node`.  The state does not move: the layout goes into the masks, the qubit lists
 and the sampled indices (`observable.PauliSum.masks`, `sampling.to_logical`)."""
 from __future__ import annotations
 

@@ -1,0 +1,158 @@
+"""The layout search of a single-GPU plan, on the host only: which index bit every logical qubit lives on
+(`choose_plan_layout`, with `priced_variant` and `pass_memory_us`), and the SWAPs between two layouts (`layout_swaps`).
+`runner/engine.py` plans with these (`SingleGpuEngine.plan_batches`) and imports their names: callers find them there too."""
+from __future__ import annotations
+
+import numpy as np
+
+from quantum_simulations_amd.kernel import planner
+
+
+def layout_swaps(cur, want, n: int) -> list:
+    """Index-bit pairs whose SWAPs, applied in order, take a state from layout `cur` to layout `want` (logical qubit q on
+    index bit layout[q]; None = identity): at most n - 1 of them."""
+    cur = list(cur) if cur is not None else list(range(n))
+    want = list(want) if want is not None else list(range(n))
+    at = {p: q for q, p in enumerate(cur)}              # index bit -> the logical qubit on it
+    swaps = []
+    for q in range(n):
+        a, b = cur[q], want[q]
+        if a != b:
+            other = at[b]                               # the qubit sitting where q has to go
+            swaps.append((a, b))
+            at[a], at[b] = other, q
+            cur[other], cur[q] = a, b
+    return swaps
+
+
+def _count_passes(n: int, batches, layouts: np.ndarray, threads: int) -> np.ndarray:
+    """Fused passes of the batches under each layout (rows of `layouts`: qubit -> index bit), planned on the host."""
+    total = np.zeros(len(layouts), dtype=np.int64)
+    for ops in batches:                                     # (a single op is not planned: one pass)
+        total += planner.count_layouts(n, ops, layouts, threads) if len(ops) >= 2 else len(ops)
+    return total
+
+
+def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 20260504, n_finalists: int = 4,
+                       all_finalists: bool = False, beam: int = 0, engine_costs=None, priced_batches=None):
+    """(l2p, tile masks per batch on the chosen index bits, info) for the op lists `batches` (logical qubits).  The three
+    qubits on the line bits belong to every tile, so they decide how many passes a plan needs; which index bits the OTHER
+    qubits live on does not (a relabelling of the bits >= 3 maps every valid pass sequence to a valid one).  So: for the
+    identity and `n_candidates` random line-qubit triples the library's searching pass builder (qsim_plan_search, beam
+    width `beam`, 0 = its default) plans the batches, in parallel on the host; the triples that need the fewest passes
+    are kept and their other qubits placed by the tile-cost model (runner/tile_layout.py).  Host only.  all_finalists: the
+    list of up to n_finalists minimum-pass layouts, best model cost first (the engine may time them on the device).
+    engine_costs (the table of runner/engine_cost.py; None: pricing off): a pass is priced max(memory model of its tile,
+    engine time of its records); `priced_variant` then chooses between `batches` and `priced_batches` (the same lists
+    under rule (d) of the rewrite, optional) and places the ops that need no tile: info gains `planned` (the op lists to
+    run, on their index bits), `placed` (their placements, per batch) and the modelled split (`model_split_ms`), and the
+    finalists rank by that total instead of the memory model alone."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+
+    from quantum_simulations_amd import _lib
+    from quantum_simulations_amd.runner import tile_layout
+    rng = np.random.default_rng(seed)
+    layouts = np.tile(np.arange(n, dtype=np.int32), (n_candidates + 1, 1))
+    for row in layouts[1:]:
+        for bit, q in enumerate(int(x) for x in rng.choice(n, size=3, replace=False)):
+            j = int(np.flatnonzero(row == bit)[0])          # the qubit on `bit` trades places with q
+            row[j], row[q] = row[q], bit
+    try:
+        threads = len(os.sched_getaffinity(0))
+    except AttributeError:
+        threads = os.cpu_count() or 1
+    threads = max(1, min(16, threads))
+    _lib.load()
+
+    def relabelled(lay):
+        return [[([int(lay[q]) for q in qs], U) for qs, U in ops] for ops in batches]
+
+    def search(lay):                                        # (the library call releases the interpreter lock)
+        none = np.zeros(0, dtype=np.uint64)
+        return [planner.search_tiles(n, ops, beam) if len(ops) >= 2 else none for ops in relabelled(lay)]
+    with ThreadPoolExecutor(threads) as pool:
+        found = list(pool.map(search, layouts))
+    short = sum(len(ops) for ops in batches if len(ops) < 2)                    # (a single op is not searched: one pass)
+    counts = np.array([short + sum(len(ms) for ms in f) for f in found], dtype=np.int64)
+    best = int(counts.min())
+    finalists = [int(i) for i in np.flatnonzero(counts == best)][:max(1, n_finalists)]   # (the identity first when it ties)
+    greedy_identity = int(_count_passes(n, batches, layouts[:1], 1)[0])
+    out = []
+    for f in finalists:
+        first = [int(x) for x in layouts[f]]
+        moved = relabelled(first)
+        masks = found[f]
+        tiles = [[b for b in range(tile_layout.LOW, n) if (int(m) >> b) & 1] for ms in masks for m in ms]
+        second, cost0, cost1 = min((tile_layout.choose_layout(tiles, n, seed=s) for s in range(1, 9)), key=lambda r: r[2])
+        final_masks = [np.array([sum(1 << second[b] for b in range(n) if (int(m) >> b) & 1) for m in ms], dtype=np.uint64) for ms in masks]
+        # The pass count does not depend on the placement, but the records of a pass are written in the order of its tile
+        # bits, and a pass at the edge of its record budget may hold one op fewer in another order: a placement that would
+        # grow the plan at execution time is dropped for the one the search ran on.
+        replanned = sum(planner.pass_count(n, [([second[b] for b in qs], U) for qs, U in ops], ms) if len(ops) >= 2 else len(ops)
+                        for ops, ms in zip(moved, final_masks))
+        if replanned != best:
+            second, final_masks, cost1 = list(range(n)), [np.array(ms, dtype=np.uint64) for ms in masks], cost0
+        l2p = [second[first[q]] for q in range(n)]
+        info = {"passes_identity": greedy_identity, "passes_chosen": best, "candidates": n_candidates + 1,
+                "candidates_by_passes": {int(c): int((counts == c).sum()) for c in np.unique(counts)},
+                "passes_identity_searched": int(counts[0]), "beam": int(beam) if beam > 0 else "default",
+                "model_ms": (round(cost0, 3), round(cost1, 3))}
+        if engine_costs is not None:
+            def on_bits(lists):
+                return [[([l2p[q] for q in qs], U) for qs, U in ops] for ops in lists]
+            # info["planned"]: the op lists the plan runs (on their index bits), info["placed"]: their placements
+            info["planned"], info["placed"], info["model_split_ms"] = priced_variant(
+                n, on_bits(batches), None if priced_batches is None else on_bits(priced_batches), final_masks, engine_costs)
+            info["passes_chosen"] = info["model_split_ms"]["pass_count"]       # (a list under rule (d) may finish a pass early)
+        out.append((l2p, final_masks, info))
+    out.sort(key=lambda r: r[2]["model_split_ms"]["passes"] if "model_split_ms" in r[2] else r[2]["model_ms"][1])
+    return out if all_finalists else out[0]
+
+
+def pass_memory_us(n: int, masks) -> np.ndarray:
+    """Microseconds the tile-cost model (runner/tile_layout.py) gives every pass of the tiles `masks` without its gates, on
+    2^n amplitudes (the model's own state size scaled to n)."""
+    from quantum_simulations_amd.runner import tile_layout
+    model = tile_layout.model_for(n)
+    scale = 2.0 ** (n - min(tile_layout._load_models(), key=lambda k: (abs(k - n), k)))
+    return np.array([tile_layout.tile_cost(model, [b for b in range(tile_layout.LOW, n) if (int(m) >> b) & 1]) * scale * 1e3 for m in masks])
+
+
+def priced_variant(n: int, batches, priced_batches, masks, engine_costs) -> tuple:
+    """(batches kept, placement per batch, model split): the cheaper of the plans the SAME tiles `masks` (one mask array
+    per batch; the batches already on their index bits) give -- `batches` run first come, which is the plan with the
+    pricing off, against `priced_batches` (the same lists under rule (d) of the rewrite; may be None) and `batches`
+    themselves with their ops that need no tile placed by `planner.balance`.  A candidate is taken when it needs no more
+    passes than the unpriced plan and the model prices it lower, so a priced plan never has a pass more and is never
+    modelled dearer.  The split (milliseconds summed over the passes): `memory` (the tile model), `engine` (the records by
+    the table), `passes` (sum of max(memory, engine)), `passes_unpriced` (the same of the unpriced plan); `pass_count`,
+    `moved_ops` (placed later than first come) and `rule_d_ops` (ops rule (d) removed; 0: `batches` kept)."""
+    mems = [pass_memory_us(n, ms) for ms in masks]
+
+    def price(lists, place):
+        tot = {"memory": 0.0, "engine": 0.0, "passes": 0.0, "pass_count": 0, "moved_ops": 0}
+        placed = []
+        for ops, ms, mem in zip(lists, masks, mems):
+            if len(ops) < 2 or not len(ms):                 # (a single op is not planned: one pass, not priced)
+                placed.append(None)
+                tot["pass_count"] += len(ops)
+                continue
+            earliest, before, after = planner.balance(n, ops, ms, mem, engine_costs, place)
+            placed.append(earliest if earliest is not None and earliest.any() else None)
+            tot["memory"] += mem.sum() / 1e3
+            tot["engine"] += after.sum() / 1e3
+            tot["passes"] += np.maximum(mem, after).sum() / 1e3
+            tot["pass_count"] += planner.pass_count(n, ops, ms, placed[-1])
+            tot["moved_ops"] += 0 if placed[-1] is None else int((placed[-1] > 0).sum())
+        return tot, placed
+
+    def shown(tot, **more):
+        return dict({k: (round(float(v), 6) if isinstance(v, float) else int(v)) for k, v in tot.items()}, **more)
+    plain, none_placed = price(batches, False)
+    for lists in ([priced_batches] if priced_batches is not None else []) + [batches]:
+        tot, placed = price(lists, True)
+        if tot["pass_count"] <= plain["pass_count"] and tot["passes"] < plain["passes"]:
+            removed = sum(len(a) - len(b) for a, b in zip(batches, lists))
+            return lists, placed, shown(tot, passes_unpriced=round(float(plain["passes"]), 6), rule_d_ops=removed)
+    return batches, none_placed, shown(plain, passes_unpriced=round(float(plain["passes"]), 6), rule_d_ops=0)

@@ -23,23 +23,32 @@ from pathlib import Path
 
 import numpy as np
 
-from quantum_simulations_amd import diagonal, evolution, hamiltonian, krylov, readout
 from quantum_simulations_amd.circuit.fusion import batch_levels, split_by_locality
 from quantum_simulations_amd.circuit.io import levelize, validate_circuit_dict
 from quantum_simulations_amd.circuit.staging import atlas_stages, permute_state
 from quantum_simulations_amd.kernel import gpu_nonlocal
 from quantum_simulations_amd.kernel.device import DeviceChunk
+from quantum_simulations_amd.state_calls import StateCalls
 
 KERNELS = ("hip", "scalar", "batched")  # the reference's names select the same HIP module here
 
 
-class HbmStateBuffer:
-    """Final state of a run: the HBM allocation + its chunk windows."""
+class HbmStateBuffer(StateCalls):
+    """Final state of a run: the HBM allocation + its chunk windows; `StateCalls` through the layout `log_to_phys` (set by `run`)."""
 
     def __init__(self, state: DeviceChunk, chunks: list[DeviceChunk], n_qubits: int,
                  chunk_size: int, work_dir: Path | None):
         self.state, self.chunks = state, chunks
         self.n_qubits, self.chunk_size, self.work_dir = n_qubits, chunk_size, work_dir
+
+    @property
+    def l2p(self):
+        return getattr(self, "log_to_phys", None) or None
+
+    def apply_observable(self, obs, out=None, fuse_diagonal: bool = False):
+        if out is None:                     # (the buffer keeps no second chunk that could be handed back)
+            raise ValueError("apply_observable: a buffer has no second chunk of its own; pass `out`")
+        return super().apply_observable(obs, out, fuse_diagonal)
 
     def close(self) -> None:
         for c in self.chunks:
@@ -304,116 +313,65 @@ def _apply_nonlocal(data: dict, qs: list[int], U: np.ndarray, k: int) -> None:
                                        data[cb | (1 << pa) | (1 << pb)], U)
 
 
+# ---- the state calls on the final state of `run`: methods of `state_calls.StateCalls` (one docstring each, there) -------------
 def expectation(buf: HbmStateBuffer, obs) -> float:
-    """<psi|H|psi> (unnormalised) of a Pauli sum over LOGICAL qubits on the final state of `run`, evaluated on the
-    device through the staging layout `buf.log_to_phys` (nothing is downloaded or permuted)."""
-    return readout.expectation(buf.state, getattr(buf, "log_to_phys", None) or None, obs)
+    """`StateCalls.expectation` on the final state of `run`."""
+    return buf.expectation(obs)
 
 
 def evolve(buf: HbmStateBuffer, obs, t, steps: int = 1, order: int = 1, fuse_diagonal: bool = False) -> int:
-    """exp(-i t H) applied to the final state of `run` by a product formula of Pauli rotations
-    (`evolution.trotter_rotations`: order 1 or 2, `steps` steps; H a Pauli sum over LOGICAL qubits), on the device
-    through the staging layout `buf.log_to_phys` (nothing is downloaded or permuted).  `fuse_diagonal`: runs of Z-only
-    rotations go through one diagonal phase pass each (`evolution.apply_rotations`).  Returns the HBM passes made."""
-    return evolution.evolve(buf.state, getattr(buf, "log_to_phys", None) or None, obs, t, steps, order, fuse_diagonal)
+    """`StateCalls.evolve` on the final state of `run`."""
+    return buf.evolve(obs, t, steps, order, fuse_diagonal)
 
 
 def apply_diagonal_phase(buf: HbmStateBuffer, obs, gamma) -> int:
-    """exp(-i gamma D) applied to the final state of `run` for a diagonal Pauli sum D (Z and identity only) over LOGICAL
-    qubits: ONE pass on the device whatever the number of terms, through the staging layout `buf.log_to_phys`; no factor
-    1/2 (`diagonal.apply_phase`).  Returns the HBM passes made."""
-    return diagonal.apply_phase(buf.state, getattr(buf, "log_to_phys", None) or None, obs, gamma)
+    """`StateCalls.apply_diagonal_phase` on the final state of `run`."""
+    return buf.apply_diagonal_phase(obs, gamma)
 
 
 def diagonal_moments(buf: HbmStateBuffer, obs) -> tuple:
-    """(<D>, <D^2> - <D>^2) of a diagonal Pauli sum over LOGICAL qubits in the normalised final state of `run`, from one
-    read-only pass on the device through the staging layout (`diagonal.moments`)."""
-    return diagonal.moments(buf.state, getattr(buf, "log_to_phys", None) or None, obs)
+    """`StateCalls.diagonal_moments` on the final state of `run`."""
+    return buf.diagonal_moments(obs)
 
 
 def qaoa(buf: HbmStateBuffer, cost, gammas, betas) -> int:
-    """QAOA layers applied to the final state of `run`: per layer exp(-i gamma_l C) for the diagonal cost C over LOGICAL
-    qubits (one pass), then exp(-i beta_l X_q) on every qubit, through the staging layout; no factor 1/2
-    (`diagonal.qaoa`).  Returns the HBM passes made."""
-    return diagonal.qaoa(buf.state, getattr(buf, "log_to_phys", None) or None, cost, gammas, betas)
+    """`StateCalls.qaoa` on the final state of `run`."""
+    return buf.qaoa(cost, gammas, betas)
 
 
 def qaoa_gradient(buf: HbmStateBuffer, cost, gammas, betas) -> tuple:
-    """(E, dE/dgammas, dE/dbetas) of E = <psi|C|psi>, psi = the QAOA circuit of `qaoa` applied to the final state of `run`,
-    by the adjoint method on the device (`diagonal.qaoa_gradient`) through the staging layout `buf.log_to_phys`; no factor
-    1/2, unnormalised.  The state is the same afterwards up to rounding; a second chunk of the state's size is allocated
-    for the call and closed."""
-    work = DeviceChunk.empty(buf.state.k, buf.state.device)
-    try:
-        return diagonal.qaoa_gradient(buf.state, work, getattr(buf, "log_to_phys", None) or None, cost, gammas, betas)
-    finally:
-        work.close()
+    """`StateCalls.qaoa_gradient` on the final state of `run`; its second chunk lives for the call."""
+    return buf.qaoa_gradient(cost, gammas, betas)
 
 
 def variance(buf: HbmStateBuffer, obs, fuse_diagonal: bool = False) -> float:
-    """<H^2> - <H>^2 (unnormalised: norm2(H psi) - <psi|H|psi>^2) of a Pauli sum over LOGICAL qubits on the final state of
-    `run`, on the device through the staging layout `buf.log_to_phys`; a second chunk of the state's size is allocated
-    for the call and closed.  `fuse_diagonal`: the Z-only terms of H go through one diagonal pass (`hamiltonian.apply`)."""
-    work = DeviceChunk.empty(buf.state.k, buf.state.device)
-    try:
-        return hamiltonian.variance(buf.state, work, getattr(buf, "log_to_phys", None) or None, obs, fuse_diagonal)
-    finally:
-        work.close()
+    """`StateCalls.variance` on the final state of `run`; its second chunk lives for the call."""
+    return buf.variance(obs, fuse_diagonal)
 
 
 def gradient(buf: HbmStateBuffer, rotations, obs) -> tuple:
-    """(E, dE/dtheta) of E = <psi(theta)|H|psi(theta)>, psi(theta) = the rotation list (every entry its own parameter,
-    exp(-i theta P) without a factor 1/2) applied to the final state of `run`, by the adjoint method on the device
-    (`hamiltonian.adjoint_gradient`) through the staging layout `buf.log_to_phys`.  The state is the same afterwards up to
-    rounding; a second chunk of the state's size is allocated for the call and closed."""
-    work = DeviceChunk.empty(buf.state.k, buf.state.device)
-    try:
-        return hamiltonian.adjoint_gradient(buf.state, work, getattr(buf, "log_to_phys", None) or None, rotations, obs)
-    finally:
-        work.close()
-
-
-def _with_krylov_chunks(buf: HbmStateBuffer, m: int, call):
-    """call(work, l2p) with `m` chunks of the state's size, allocated for the call and closed."""
-    work = []
-    try:
-        for _ in range(max(int(m), 0)):
-            work.append(DeviceChunk.empty(buf.state.k, buf.state.device))
-        return call(work, getattr(buf, "log_to_phys", None) or None)
-    finally:
-        for c in work:
-            c.close()
+    """`StateCalls.gradient` on the final state of `run`; its second chunk lives for the call."""
+    return buf.gradient(rotations, obs)
 
 
 def ground_state(buf: HbmStateBuffer, obs, m: int = 16, tol: float = 1e-8, max_restarts: int = 50, fuse_diagonal: bool = False) -> tuple:
-    """The lowest eigenpair of a Pauli sum over LOGICAL qubits by restarted Lanczos (`krylov.ground_state`), started from
-    the final state of `run` and left there, normalised, in the staging layout `buf.log_to_phys`; m work chunks of the
-    state's size are allocated for the call and closed.  Returns (energy, residual, restarts, H applications).
-    `fuse_diagonal`: as in `variance`, for every H application."""
-    return _with_krylov_chunks(buf, m, lambda work, l2p: krylov.ground_state(buf.state, work, l2p, obs, m, tol, max_restarts,
-                                                                             fuse_diagonal=fuse_diagonal))
+    """`StateCalls.ground_state` from the final state of `run`, which is left normalised in the staging layout."""
+    return buf.ground_state(obs, m, tol, max_restarts, fuse_diagonal)
 
 
 def evolve_krylov(buf: HbmStateBuffer, obs, t, m: int = 16, steps: int = 1, fuse_diagonal: bool = False) -> float:
-    """exp(-i t H) applied to the final state of `run` to Krylov accuracy (`krylov.evolve`; t = -i tau: exp(-tau H),
-    unnormalised) for a Pauli sum over LOGICAL qubits, on the device through the staging layout `buf.log_to_phys`; m work
-    chunks of the state's size are allocated for the call and closed.  Returns the a-posteriori error estimate.
-    `fuse_diagonal`: as in `variance`, for every H application."""
-    return _with_krylov_chunks(buf, m, lambda work, l2p: krylov.evolve(buf.state, work, l2p, obs, t, m, steps, fuse_diagonal))
+    """`StateCalls.evolve_krylov` on the final state of `run`."""
+    return buf.evolve_krylov(obs, t, m, steps, fuse_diagonal)
 
 
 def reduced_density_matrix(buf: HbmStateBuffer, qubits) -> np.ndarray:
-    """Reduced density matrix (unnormalised, complex128 (2^r, 2^r)) of 1 to 6 LOGICAL qubits of the final state of `run`,
-    bit j of a row or column index = qubit qubits[j], evaluated on the device through the staging layout
-    `buf.log_to_phys` (nothing is downloaded or permuted)."""
-    return readout.reduced_density_matrix(buf.state, getattr(buf, "log_to_phys", None) or None, qubits)
+    """`StateCalls.reduced_density_matrix` of the final state of `run`."""
+    return buf.reduced_density_matrix(qubits)
 
 
 def sample(buf: HbmStateBuffer, shots: int, seed: int = 0, qubits=None) -> np.ndarray:
-    """`shots` samples of the final state of `run`, drawn on the device through the staging layout `buf.log_to_phys`
-    (nothing is downloaded or permuted; `sampling.draw(shots, seed)` gives the uniforms): LOGICAL basis-state indices as
-    uint64, or with `qubits` the marginal values (bit j = qubit qubits[j])."""
-    return readout.sample(buf.state, getattr(buf, "log_to_phys", None) or None, shots, seed, qubits)
+    """`StateCalls.sample` of the final state of `run`."""
+    return buf.sample(shots, seed, qubits)
 
 
 def collect_state(buf: HbmStateBuffer, apply_permutation: bool = False,
