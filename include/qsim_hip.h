@@ -492,6 +492,19 @@ int qsim_apply_diagonal_sum(qsim_chunk* dst, const qsim_chunk* src, int n_terms,
                             int accumulate);
 int qsim_overlap_diagonal(qsim_chunk* ket, const qsim_chunk* bra, int n_terms, const uint64_t* z_masks, const double* coeffs,
                           double out[4]);
+/* The values of the single Z strings, out[t] = sum_i |psi_i|^2 (-1)^popcount(i & z_masks[t]): <psi|Z^{z_t}|psi>,
+ * unnormalised, in input order, without coefficients; z_masks[t] is a mask of physical local index bits, 0 gives
+ * sum |psi_i|^2.  Nothing is merged: equal masks may repeat and get equal bits.  Read-only.  Per tile of 2^11 contiguous
+ * amplitudes ONE unscaled Walsh-Hadamard transform of the tile's |psi|^2 in LDS holds every Z string; a term reads its
+ * entry (the part of z inside the tile) and takes the sign of the part outside.  A pass over the chunk (16 B per
+ * amplitude) serves 2048 terms, so a call makes ceil(n_terms / 2048) passes; *n_passes = that number (n_passes may be
+ * null).  Every sum runs in a fixed order that depends on the term list and the chunk size only: a thread adds its
+ * terms' values over its workgroup's tiles in tile order, the per-workgroup rows are added by the fixed reduction of the
+ * other readout calls, no atomics -- two calls give the same bits.  The records and the rows go into the chunk's
+ * workspace; the call blocks until out is written.  n_terms == 0 launches nothing and sets *n_passes = 0.  A bit of z
+ * >= log2(chunk) fails with QSIM_ERR_NONLOCAL; n_terms < 0 or > 16384, a null argument and slab pieces pending on the
+ * chunk with QSIM_ERR_INVALID. */
+int qsim_expectation_z_terms(qsim_chunk* c, int n_terms, const uint64_t* z_masks, double* out, int* n_passes);
 /* The pass plan of qsim_apply_pauli_rotations (pure function, no GPU), ORDER PRESERVING: pass_of[t] = the pass that
  * applies rotation t, non-decreasing in t; tile_masks[p] = the tile bits of pass p (they contain the line bits 0..2 and
  * the x of each of its rotations, min(n_local_qubits, 11) bits), 0 for a wide pass.  tile_masks needs room for n

@@ -124,6 +124,7 @@ SIGNATURES = {
     "qsim_diagonal_moments": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "qsim_apply_diagonal_sum": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
     "qsim_overlap_diagonal": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
+    "qsim_expectation_z_terms": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(C.c_int)]),
     "qsim_apply_pauli_sum": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_overlap_pauli": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_lincomb": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P]),

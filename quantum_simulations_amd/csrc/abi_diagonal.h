@@ -1,6 +1,7 @@
 // abi_diagonal.h -- C ABI: diagonal Pauli sums D = sum_t c_t Z^{z_t} on a chunk: the phase exp(-i gamma D) in place, the
 // moments sum |psi|^2 (1, E, E^2) read-only, and D as an operator between two chunks, dst (+)= D src and <bra|D|ket>,
-// each ONE pass whatever the number of terms (diag_kernels.h).
+// each ONE pass whatever the number of terms, and the values of the single terms <Z^{z_t}>, one read-only pass per 2048
+// terms (diag_kernels.h).
 // Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
 
 // What the four calls share: the checks (the chunk, then check_diag_args, then pending parts; with a second chunk
@@ -135,5 +136,46 @@ int qsim_overlap_diagonal(qsim_chunk* ket, const qsim_chunk* bra, int n_terms, c
   }
   if ((rc = sum_rows(ket, a.partial, grid, 4, dev_out))) return rc;
   return fetch_doubles(ket, dev_out, 4, out);
+}
+
+// out[t] = sum_i |psi_i|^2 (-1)^popcount(i & z_masks[t]), in input order: one read-only pass per kDiagValuesPerPass
+// terms.  The workspace holds the records of the whole list | the n_terms sums | the rows of ONE pass, [workgroup][terms
+// of the pass]: the passes run one after the other on the chunk's stream and share the rows; the sums cross once.
+int qsim_expectation_z_terms(qsim_chunk* c, int n_terms, const uint64_t* z_masks, double* out, int* n_passes) {
+  const char* const what = "qsim_expectation_z_terms";
+  int rc = check_chunk(c, what);
+  if (rc || (rc = check_diag_value_args(c->k, n_terms, z_masks, out, what)) || (rc = require_no_parts(c, what))) return rc;
+  if (n_passes) *n_passes = 0;
+  if (n_terms == 0) return QSIM_OK;
+  DiagValueArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.amp = c->amp;
+  a.tb = std::min(c->k, kExpTileBits);
+  a.n_tiles = 1ull << (c->k - a.tb);
+  DiagValueTable d;
+  diag_value_table(a.tb, n_terms, z_masks, &d);
+  static_assert(sizeof(DiagValueTerm) == 16, "16-byte records");
+  const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, kExpMaxWg);
+  const u64 out_off = 16 * (u64)n_terms, row_off = out_off + 8 * (u64)n_terms;
+  if ((rc = ensure_work(c, row_off + 8 * (u64)grid * (u64)std::min(n_terms, kDiagValuesPerPass)))) return rc;
+  char* const base = static_cast<char*>(c->work);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(base, d.terms.data(), (size_t)out_off, hipMemcpyHostToDevice, c->stream));
+  double* const dev_out = reinterpret_cast<double*>(base + out_off);
+  a.partial = reinterpret_cast<double*>(base + row_off);
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  for (const DiagValuePass& p : d.passes) {
+    a.terms = reinterpret_cast<const DiagValueTerm*>(base) + p.first;
+    a.n_terms = p.count;
+    {
+      ProfileScope prof(19, 16.0 * (double)amps(c), c->stream, nt);
+      QSIM_WITH_NT(hipLaunchKernelGGL((k_diag_term_values<NT>), dim3(grid), dim3(kBlock), 0, c->stream, a));
+      HIP_TRY(hipGetLastError());
+      prof.done(c->stream);
+    }
+    if ((rc = sum_rows(c, a.partial, grid, p.count, dev_out + p.first))) return rc;
+  }
+  if (n_passes) *n_passes = (int)d.passes.size();
+  return fetch_doubles(c, dev_out, (u64)n_terms, out);
 }
 }  // extern "C"

@@ -1,6 +1,7 @@
 // diag_kernels.h -- diagonal Pauli sums D = sum_t c_t Z^{z_t}: the phase exp(-i gamma D) and the moments <D>, <D^2>
 // (qsim_apply_diagonal_phase, qsim_diagonal_moments), and D as an operator: dst (+)= D src and <bra|ket>, <bra|D|ket>
-// (qsim_apply_diagonal_sum, qsim_overlap_diagonal).
+// (qsim_apply_diagonal_sum, qsim_overlap_diagonal), and the values of the single terms <Z^{z_t}> (qsim_expectation_z_terms,
+// k_diag_term_values below).
 // Part of the single translation unit qsim_hip.hip (included there after rot_kernels.h; not a standalone header).
 //
 // E(i) = sum_t c_t (-1)^popcount(i & z_t) is the diagonal entry of D at index i.  D moves no amplitude, so a tile is the
@@ -189,6 +190,82 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
       a.partial[(u64)blockIdx.x * 3 + tid] = s;
     }
   }
+}
+
+// The values of the single terms, out[t] = sum_i |psi_i|^2 (-1)^popcount(i & z_t) (qsim_expectation_z_terms): the
+// transpose of k_diag_tile.  There the terms are scattered into a spectrum and the transform gives E over the tile; here
+// the tile's probabilities p_j = |psi_j|^2 are transformed and every term GATHERS its value at zi, with the outer sign
+// (-1)^popcount(base & zo) (diag_plan.h).  Per tile: the thread's kExpLoads amplitudes -> p in registers, bits 8-10 of
+// the transform on the thread's own slots tid + r * kBlock, p into the 16 KiB LDS array, bits 0-2, 3-5, 6-7 through LDS
+// (the stages commute, so the register round comes first here), then one LDS read and one __popcll per term of the
+// thread.  A pass serves at most kDiagValuesPerPass terms: term i of the pass belongs to thread i % kBlock, slot
+// i / kBlock, whose (zi, zo) and running sum stay in registers over the workgroup's tiles; at the end the sums go
+// straight into the workgroup's row of a.partial ([workgroup][a.n_terms]) -- no reduction inside the workgroup -- and
+// k_hist_sum adds the rows in its fixed order.  No atomics; the state is only read.  Slots above 2^tb are zero
+// (diag_load) and zi < 2^tb, so a chunk smaller than a tile needs no other code.
+// Compiler's resource usage (gfx950, both NT forms alike): 96 VGPRs, 72 SGPRs, no spill, no scratch, 16 KiB of LDS: four
+// workgroups per CU as asked for (amdgpu_waves_per_eu), like the siblings.
+constexpr int kDiagValueSlots = kDiagValuesPerPass / kBlock;
+static_assert(kDiagValuesPerPass % kBlock == 0, "a pass's terms are dealt to the threads in whole slots");
+
+struct DiagValueArgs {
+  const double2* amp;
+  const DiagValueTerm* terms;   // the pass's records
+  double* partial;              // [workgroup][n_terms]
+  u64 n_tiles;                  // 2^(k - tb)
+  int tb;                       // tile bits: min(k, kExpTileBits)
+  int n_terms;                  // terms of this pass, 1 .. kDiagValuesPerPass
+};
+
+template <bool NT>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_term_values(const DiagValueArgs a) {
+  static_assert(kExpTileBits == 11 && kExpLoads == 8, "the rounds below are bits 8-10, 0-2, 3-5 and 6-7");
+  __shared__ double P[kExpTile];
+  const int S = 1 << a.tb;
+  const int tid = threadIdx.x;
+  const int n_slots = (a.n_terms + kBlock - 1) / kBlock;   // (the same in every thread)
+  unsigned zi[kDiagValueSlots];
+  u64 zo[kDiagValueSlots];
+  double acc[kDiagValueSlots];
+#pragma unroll
+  for (int s = 0; s < kDiagValueSlots; ++s) {
+    const int t = tid + s * kBlock;
+    const bool mine = t < a.n_terms;                 // (a thread without a term in a slot gathers P[0]; nothing is written)
+    zi[s] = mine ? a.terms[t].zi : 0u;
+    zo[s] = mine ? a.terms[t].zo : 0ull;
+    acc[s] = 0.0;
+  }
+  for (u64 o = blockIdx.x; o < a.n_tiles; o += gridDim.x) {
+    const u64 base = o << a.tb;
+    double p[kExpLoads];
+    {
+      double2 x[kExpLoads];
+      diag_load<NT>(a.amp, base, S, x);
+#pragma unroll
+      for (int it = 0; it < kExpLoads; ++it) p[it] = fma(x[it].x, x[it].x, x[it].y * x[it].y);
+    }
+    diag_butterflies<3>(p);                          // bits 8-10
+    __syncthreads();                                 // the gathers of the previous tile are done
+#pragma unroll
+    for (int it = 0; it < kExpLoads; ++it) P[tid + it * kBlock] = p[it];
+    __syncthreads();
+    diag_round<0, 3>(P);
+    __syncthreads();
+    diag_round<3, 3>(P);
+    __syncthreads();
+    diag_round<6, 2>(P);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < kDiagValueSlots; ++s)
+      if (s < n_slots) {
+        const double v = P[zi[s]];
+        acc[s] += (__popcll(base & zo[s]) & 1) ? -v : v;
+      }
+  }
+  double* const row = a.partial + (u64)blockIdx.x * (u64)a.n_terms;
+#pragma unroll
+  for (int s = 0; s < kDiagValueSlots; ++s)
+    if (tid + s * kBlock < a.n_terms) row[tid + s * kBlock] = acc[s];
 }
 
 // dst_j = E_j src_j (ACC false) or dst_j += E_j src_j (ACC true) over contiguous tiles; a.amp = src, a.other = dst.  dst

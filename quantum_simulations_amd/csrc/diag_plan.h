@@ -1,6 +1,6 @@
 // diag_plan.h -- host side of the diagonal Pauli sums (diag_kernels.h, abi_diagonal.h): the argument checks and the
-// tables k_diag_tile reads.  Pure C++, no device call and no HIP type: tools/diag_plan_check.cpp compiles this file
-// alone, with stubs for fail() and the error codes, under the host sanitizers.
+// tables k_diag_tile and k_diag_term_values read.  Pure C++, no device call and no HIP type: tools/diag_plan_check.cpp
+// compiles this file alone, with stubs for fail() and the error codes, under the host sanitizers.
 // Part of the single translation unit qsim_hip.hip (included there before diag_kernels.h; not a standalone header).
 //
 // D = sum_t c_t Z^{z_t}, z_t a mask of physical index bits (0: the identity).  A tile is the 2^tb amplitudes on the
@@ -87,5 +87,55 @@ static void diag_table(int tb, int n, const uint64_t* z_masks, const double* coe
       d->pieces.push_back(pc);
     }
     first = end;
+  }
+}
+
+// ---- the values of the single terms, <Z^{z_t}> = sum_i |psi_i|^2 (-1)^popcount(i & z_t) (qsim_expectation_z_terms,
+// k_diag_term_values): the transpose of the table above.  With p_l = |psi_{base | l}|^2 over a tile,
+//   sum_l p_l (-1)^popcount((base | l) & z) = (-1)^popcount(base & zo) WHT(p)[zi]:
+// ONE transform of the tile's probabilities holds every Z string, a term is a gather at zi and the outer sign.  A pass
+// over the state serves kDiagValuesPerPass terms, in INPUT order (nothing is sorted or merged: duplicates are served
+// twice and get equal bits): pass p holds the terms p * kDiagValuesPerPass ..., and term i of a pass belongs to thread
+// i % kBlock, register slot i / kBlock, for the whole launch.  The record carries no coefficient.
+constexpr int kDiagValuesPerPass = 2048;
+struct DiagValueTerm {   // 16 bytes, in input order
+  u64 zo;                // z outside the tile (physical bits): the outer sign
+  unsigned zi;           // z inside the tile: the index into the transformed probabilities
+  unsigned pad_;
+};
+struct DiagValuePass {
+  int first, count;      // terms first .. first + count - 1 of the list, 1 <= count <= kDiagValuesPerPass
+};
+struct DiagValueTable {
+  std::vector<DiagValueTerm> terms;
+  std::vector<DiagValuePass> passes;
+};
+
+// The checks of qsim_expectation_z_terms after the chunk's own, in the order of check_diag_args: n_terms, null
+// arguments, then term by term locality.
+static int check_diag_value_args(int k, int n_terms, const uint64_t* z_masks, const double* out, const char* what) {
+  if (n_terms < 0) return fail(QSIM_ERR_INVALID, "%s: n_terms = %d", what, n_terms);
+  if (n_terms > kDiagMaxTerms) return fail(QSIM_ERR_INVALID, "%s: %d terms in one call, at most %d", what, n_terms, kDiagMaxTerms);
+  if (n_terms > 0 && (!z_masks || !out)) return fail(QSIM_ERR_INVALID, "%s: null argument", what);
+  const u64 all = k >= 64 ? ~0ull : (1ull << k) - 1;
+  for (int t = 0; t < n_terms; ++t)
+    if (z_masks[t] & ~all)
+      return fail(QSIM_ERR_NONLOCAL, "%s: term %d acts on index bit %d >= log2(chunk_size)=%d", what, t,
+                  63 - __builtin_clzll(z_masks[t] & ~all), k);
+  return QSIM_OK;
+}
+
+// the records and the passes of a checked call on tiles of tb bits
+static void diag_value_table(int tb, int n, const uint64_t* z_masks, DiagValueTable* d) {
+  const u64 inner = (1ull << tb) - 1;
+  d->terms.resize((size_t)n);
+  for (int t = 0; t < n; ++t) {
+    DiagValueTerm r = {z_masks[t] & ~inner, (unsigned)(z_masks[t] & inner), 0u};
+    d->terms[(size_t)t] = r;
+  }
+  d->passes.clear();
+  for (int first = 0; first < n; first += kDiagValuesPerPass) {
+    DiagValuePass p = {first, std::min(kDiagValuesPerPass, n - first)};
+    d->passes.push_back(p);
   }
 }

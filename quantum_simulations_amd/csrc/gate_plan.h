@@ -147,8 +147,9 @@ static const char* const kClassNames[] = {
     "k_sample_block_sums shot sampling, pass A", "k_sample_resolve shot sampling, pass B",
     "k_rdm reduced density matrix", "k_rot Pauli rotations", "k_psum Pauli-sum action",
     "k_ovl two-state overlaps", "k_lincomb linear combination", "k_diag diagonal Pauli sum",
-    "k_diag_apply diagonal Pauli sum applied", "k_diag_overlap diagonal matrix element"};
-constexpr int kNumClasses = 19;
+    "k_diag_apply diagonal Pauli sum applied", "k_diag_overlap diagonal matrix element",
+    "k_diag_term_values per-term Z expectations"};
+constexpr int kNumClasses = 20;
 
 static hipEvent_t prof_event_locked() {
   if (!g_prof_pool.empty()) {

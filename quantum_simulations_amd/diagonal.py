@@ -1,6 +1,7 @@
 """Diagonal Pauli sums D = sum_t c_t Z^{z_t}: the phase exp(-i gamma D), the moments <D>, <D^2>, D as an operator
 (D|psi>, <bra|D|ket>), QAOA layers and their gradient, each use of D ONE pass over the state whatever the number of terms
-(qsim_apply_diagonal_phase, qsim_diagonal_moments, qsim_apply_diagonal_sum, qsim_overlap_diagonal).
+(qsim_apply_diagonal_phase, qsim_diagonal_moments, qsim_apply_diagonal_sum, qsim_overlap_diagonal), and the values of
+the single terms <Z^{z_t}>, all of them from one Walsh-Hadamard pass (qsim_expectation_z_terms).
 
 Convention as in `evolution`: NO factor 1/2.  exp(-i gamma D) multiplies amplitude i by exp(-i gamma E(i)), E(i) =
 sum_t c_t (-1)^popcount(i & z_t); a Z-only rotation `evolution.rotation("Z0 Z1", theta)` is the term (z, theta) with gamma
@@ -10,6 +11,8 @@ sum_t c_t (-1)^popcount(i & z_t); a Z-only rotation `evolution.rotation("Z0 Z1",
     split(obs)                                -> (the Z-only terms, the rest) as two PauliSums
     apply_phase(chunk, l2p, obs, gamma)       -> psi := exp(-i gamma D) psi through the layout
     moments(chunk, l2p, obs)                  -> (<D>, <D^2> - <D>^2) of the normalised state, one read-only pass
+    term_values(chunk, l2p, obs)              -> <psi|Z^{z_t}|psi> per term, unnormalised, one read-only pass per 2048 terms
+    correlations(chunk, l2p, qubits, connected) -> (<Z_a>, <Z_a Z_b>) of the normalised state from one such call
     apply_sum(dst, src, l2p, obs, accumulate) -> dst := D src, or dst += D src; dst may be src when writing
     matrix_element(ket, bra, l2p, obs)        -> (<bra|ket>, <bra|D|ket>), unnormalised, one read-only pass
     qaoa(chunk, l2p, cost, gammas, betas)     -> alternating cost and mixer layers; the HBM passes made
@@ -67,6 +70,45 @@ def split(obs) -> tuple[PauliSum, PauliSum]:
 def _physical(chunk, l2p, obs) -> tuple[np.ndarray, np.ndarray]:
     z, co = diagonal_part(_as_sum(obs, n_qubits(chunk, l2p)))
     return to_physical(np.zeros_like(z), z, l2p)[1], co
+
+
+def term_values(chunk, l2p, obs) -> np.ndarray:
+    """<psi|Z^{z_t}|psi> of every term of a diagonal Pauli sum over LOGICAL qubits: float64, in the sum's own term order,
+    WITHOUT the coefficients and unnormalised (the identity gives sum |psi|^2); terms are not merged.  One read-only
+    pass per 2048 terms (`DeviceChunk.expectation_z_terms`); the layout goes into the masks, the state does not move.
+    A term with an X or a Y raises ValueError, as in `diagonal_part`."""
+    obs = _as_sum(obs, n_qubits(chunk, l2p))
+    for t, x in enumerate(obs.x):
+        if x:
+            raise ValueError(f"term {t} ({obs.labels()[t]}) is not diagonal: it carries X or Y")
+    z = np.array(obs.z, dtype=np.uint64)
+    return chunk.expectation_z_terms(to_physical(np.zeros_like(z), z, l2p)[1])
+
+
+def correlations(chunk, l2p, qubits=None, connected: bool = True) -> tuple[np.ndarray, np.ndarray]:
+    """(z, zz) of the NORMALISED state: z[a] = <Z_qa>, shape (m,), and zz[a, b] = <Z_qa Z_qb>, shape (m, m), over the
+    LOGICAL qubits `qubits` (None: all of them, in order).  With `connected`, zz[a, b] - z[a] z[b].  zz is symmetric; its
+    diagonal is 1, or 1 - z[a]^2 with `connected`.  Everything comes from ONE `expectation_z_terms` call on the identity,
+    the m singles and the m (m - 1) / 2 pairs."""
+    n = n_qubits(chunk, l2p)
+    qubits = list(range(n)) if qubits is None else [int(q) for q in qubits]
+    if len(set(qubits)) != len(qubits) or any(q < 0 or q >= n for q in qubits):
+        raise ValueError(f"correlations: qubits {qubits} are not distinct qubits of a {n}-qubit state")
+    m = len(qubits)
+    pairs = [(a, b) for a in range(m) for b in range(a + 1, m)]
+    masks = [0] + [1 << q for q in qubits] + [(1 << qubits[a]) | (1 << qubits[b]) for a, b in pairs]
+    masks = np.array(masks, dtype=np.uint64)
+    v = chunk.expectation_z_terms(to_physical(np.zeros_like(masks), masks, l2p)[1])
+    norm2 = float(v[0])
+    if not norm2 > 0.0:
+        raise ValueError(f"correlations: sum |psi|^2 = {norm2}")
+    z = np.asarray(v[1:1 + m], dtype=np.float64) / norm2
+    zz = np.eye(m, dtype=np.float64)
+    for (a, b), value in zip(pairs, v[1 + m:]):
+        zz[a, b] = zz[b, a] = float(value) / norm2
+    if connected:
+        zz -= np.outer(z, z)
+    return z, zz
 
 
 def _angles(gammas, betas, what: str) -> tuple[np.ndarray, np.ndarray]:

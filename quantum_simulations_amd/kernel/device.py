@@ -20,6 +20,8 @@ def _mat_ptr(U: np.ndarray, dim: int):
     return m, _lib.ptr(m)
 
 
+Z_TERMS_PER_CALL = 16384   # terms of one qsim_expectation_z_terms call (kDiagMaxTerms)
+
 _TERM_ARRAYS = {"x": (np.uint64, "x masks"), "z": (np.uint64, "z masks"), "coeffs": (np.float64, "coefficients"), "angles": (np.float64, "angles")}
 
 
@@ -250,6 +252,23 @@ class DeviceChunk:
         out = np.empty(4, dtype=np.float64)
         _lib.check(_lib.load().qsim_overlap_diagonal(self._h, bra._h, int(z.size), _lib.ptr(z), _lib.ptr(co), _lib.ptr(out)))
         return complex(out[0], out[1]), complex(out[2], out[3])
+
+    def expectation_z_terms(self, z_masks) -> np.ndarray:
+        """<psi|Z^{z_t}|psi> = sum_i |psi_i|^2 (-1)^popcount(i & z_t) of every Z string of the list, unnormalised, float64,
+        in list order; the masks over PHYSICAL index bits of this chunk (0: sum |psi_i|^2).  Nothing is merged: equal
+        masks get equal bits.  One read-only pass per 2048 terms whatever they are (qsim_expectation_z_terms: one
+        Walsh-Hadamard transform of |psi|^2 per tile serves them all; a fixed summation order -- two calls give the same
+        bits).  A list of more than 16384 masks is cut into calls of that many here.  `self.last_z_terms_passes` = the
+        passes that ran (0 for an empty list: nothing is launched)."""
+        (z,) = _term_arrays("expectation_z_terms", z=z_masks)
+        out = np.empty(z.size, dtype=np.float64)
+        self.last_z_terms_passes = 0
+        for first in range(0, max(z.size, 1), Z_TERMS_PER_CALL):     # (an empty list still makes the call: its checks run)
+            part, res = z[first:first + Z_TERMS_PER_CALL], out[first:first + Z_TERMS_PER_CALL]
+            passes = C.c_int(0)
+            _lib.check(_lib.load().qsim_expectation_z_terms(self._h, int(part.size), _lib.ptr(part), _lib.ptr(res), C.byref(passes)))
+            self.last_z_terms_passes += passes.value
+        return out
 
     def apply_pauli_sum(self, src: "DeviceChunk", x_masks, z_masks, coeffs) -> int:
         """self := sum_t coeffs[t] P_t src, OUT OF PLACE (`self` is dst: what it held does not matter; `src` is only

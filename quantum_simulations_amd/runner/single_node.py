@@ -314,9 +314,9 @@ def _apply_nonlocal(data: dict, qs: list[int], U: np.ndarray, k: int) -> None:
 
 
 # ---- the state calls on the final state of `run`: methods of `state_calls.StateCalls` (one docstring each, there) -------------
-def expectation(buf: HbmStateBuffer, obs) -> float:
+def expectation(buf: HbmStateBuffer, obs, per_term=False, fuse_diagonal=False):
     """`StateCalls.expectation` on the final state of `run`."""
-    return buf.expectation(obs)
+    return buf.expectation(obs, per_term, fuse_diagonal)
 
 
 def evolve(buf: HbmStateBuffer, obs, t, steps: int = 1, order: int = 1, fuse_diagonal: bool = False) -> int:

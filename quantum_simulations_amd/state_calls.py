@@ -47,9 +47,12 @@ class StateCalls:
             yield work
 
     # ---- readout: the state is only read -----------------------------------------------------------------------------
-    def expectation(self, obs) -> float:
-        """<psi|H|psi> (unnormalised) of a Pauli sum over LOGICAL qubits (observable.PauliSum or what it accepts)."""
-        return readout.expectation(self.state, self.l2p, obs)
+    def expectation(self, obs, per_term=False, fuse_diagonal=False):
+        """<psi|H|psi> (unnormalised) of a Pauli sum over LOGICAL qubits (observable.PauliSum or what it accepts); with
+        `per_term` the array of <psi|P_t|psi> in term order.  `fuse_diagonal`: the Z-only terms go through one
+        Walsh-Hadamard pass (`readout.expectation`).  The per-term Z values and the ZZ correlators of the state are
+        `diagonal.term_values` / `diagonal.correlations` on (`self.state`, `self.l2p`)."""
+        return readout.expectation(self.state, self.l2p, obs, per_term, fuse_diagonal)
 
     def diagonal_moments(self, obs) -> tuple:
         """(<D>, <D^2> - <D>^2) of a diagonal Pauli sum over LOGICAL qubits in the NORMALISED state, one read-only pass."""

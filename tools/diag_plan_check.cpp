@@ -1,6 +1,7 @@
 // Stand-alone host check of quantum_simulations_amd/csrc/diag_plan.h: the argument checks, the sort by inner mask, the
 // segment cut into pieces and joins -- and, on top of the tables, a host restatement of what k_diag_tile does with them
-// per tile (pieces, joins, unscaled Walsh-Hadamard transform) against the direct sum.  No GPU, no HIP.  Meant for the
+// per tile (pieces, joins, unscaled Walsh-Hadamard transform) against the direct sum; the same for the per-term values
+// (diag_value_table, a host restatement of k_diag_term_values and the row sum).  No GPU, no HIP.  Meant for the
 // host sanitizers:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/diag_plan_check.cpp -o diag_plan_check && ./diag_plan_check
 // Exit status 0 and a last line "diag_plan_check: ok" mean that every case passed.
@@ -122,6 +123,106 @@ static void check_energies(int k, const std::vector<uint64_t>& z, const std::vec
   }
 }
 
+// ---- the per-term values (qsim_expectation_z_terms): the records and passes of diag_value_table
+static void check_value_table(int tb, int n, const std::vector<uint64_t>& z, const DiagValueTable& d) {
+  const u64 inner = (1ull << tb) - 1;
+  CHECK((int)d.terms.size() == n);
+  for (int t = 0; t < n; ++t) {                     // input order, nothing merged: record t is term t
+    const DiagValueTerm& r = d.terms[(size_t)t];
+    CHECK(r.zi <= inner && (r.zo & inner) == 0 && ((u64)r.zi | r.zo) == z[(size_t)t] && r.pad_ == 0);
+  }
+  CHECK((int)d.passes.size() == (n + kDiagValuesPerPass - 1) / kDiagValuesPerPass);
+  int next = 0;
+  for (const DiagValuePass& p : d.passes) {
+    CHECK(p.first == next && p.count >= 1 && p.count <= kDiagValuesPerPass);
+    next += p.count;
+  }
+  CHECK(next == n);
+  for (size_t i = 0; i + 1 < d.passes.size(); ++i) CHECK(d.passes[i].count == kDiagValuesPerPass);   // only the last one is short
+}
+
+// what k_diag_term_values and the row sum compute for one pass: per tile the unscaled transform of p = |psi|^2 (zero
+// above 2^tb), a gather at zi with the outer sign, added over the tiles o = wg, wg + grid, ... of a "workgroup", then the
+// rows in workgroup order
+static std::vector<double> value_pass_model(int k, const std::vector<double>& p, const DiagValueTable& d, const DiagValuePass& ps, unsigned grid) {
+  const int tb = std::min(k, kExpTileBits);
+  const u64 n_tiles = 1ull << (k - tb);
+  std::vector<std::vector<double>> rows(grid, std::vector<double>((size_t)ps.count, 0.0));
+  std::vector<double> P(1u << kExpTileBits);
+  for (unsigned wg = 0; wg < grid; ++wg)
+    for (u64 o = wg; o < n_tiles; o += grid) {
+      const u64 base = o << tb;
+      for (size_t j = 0; j < P.size(); ++j) P[j] = j < (1ull << tb) ? p[(size_t)(base | j)] : 0.0;
+      for (int s : {8, 9, 10, 0, 1, 2, 3, 4, 5, 6, 7})   // the kernel's order of the stages
+        for (size_t i = 0; i < P.size(); ++i)
+          if (!((i >> s) & 1)) {
+            const double a = P[i], b = P[i | (1u << s)];
+            P[i] = a + b;
+            P[i | (1u << s)] = a - b;
+          }
+      for (int i = 0; i < ps.count; ++i) {
+        const DiagValueTerm& r = d.terms[(size_t)(ps.first + i)];
+        CHECK(r.zi < P.size());
+        const double v = P[r.zi];
+        rows[wg][(size_t)i] += (__builtin_popcountll(base & r.zo) & 1) ? -v : v;
+      }
+    }
+  std::vector<double> out((size_t)ps.count, 0.0);
+  for (unsigned wg = 0; wg < grid; ++wg)
+    for (int i = 0; i < ps.count; ++i) out[(size_t)i] += rows[wg][(size_t)i];
+  return out;
+}
+
+static void check_values(std::mt19937_64& rng, double* worst, int* cases) {
+  struct Case { int k, n; int kind; unsigned grid; };   // kind 0: random masks, 1: inner part 0, 2: singles, pairs, identity and duplicates
+  const Case list[] = {{1, 3, 0, 1024}, {5, 40, 0, 1024}, {10, 70, 2, 1024}, {11, 300, 0, 1024}, {12, 2047, 0, 1024}, {12, 2048, 0, 1024},
+                       {12, 2049, 0, 1024}, {13, 120, 2, 3}, {14, 4100, 0, 5}, {16, 600, 2, 8}, {16, 64, 1, 7}, {12, 0, 0, 1024}};
+  std::uniform_real_distribution<double> uni(0.0, 1.0);
+  for (const Case& cs : list) {
+    const int tb = std::min(cs.k, kExpTileBits);
+    const u64 all = (1ull << cs.k) - 1, inner = (1ull << tb) - 1;
+    std::vector<uint64_t> z;
+    if (cs.kind == 2) {
+      z.push_back(0);
+      for (int a = 0; a < cs.k; ++a) z.push_back(1ull << a);
+      for (int a = 0; a < cs.k; ++a)
+        for (int b = a + 1; b < cs.k; ++b) z.push_back((1ull << a) | (1ull << b));
+      z.push_back(all);
+      z.push_back(z[3]);                            // duplicates: equal bits expected
+      z.push_back(0);
+      while ((int)z.size() < cs.n) z.push_back(rng() & all);
+    } else {
+      for (int t = 0; t < cs.n; ++t) z.push_back(cs.kind == 1 ? (rng() & all & ~inner) : (rng() & all));
+    }
+    const int n = (int)z.size();
+    double out_stub = 0.0;
+    CHECK(check_diag_value_args(cs.k, n, z.data(), &out_stub, "check") == QSIM_OK);
+    DiagValueTable d;
+    diag_value_table(tb, n, z.data(), &d);
+    check_value_table(tb, n, z, d);
+    std::vector<double> p((size_t)1 << cs.k);
+    double total = 0.0;
+    for (double& v : p) { v = uni(rng); total += v; }
+    for (double& v : p) v /= total;                 // weights of a unit-norm state
+    const unsigned grid = (unsigned)std::min<u64>(1ull << (cs.k - tb), cs.grid);
+    std::vector<double> got;
+    for (const DiagValuePass& ps : d.passes) {
+      const std::vector<double> part = value_pass_model(cs.k, p, d, ps, grid);
+      got.insert(got.end(), part.begin(), part.end());
+    }
+    CHECK((int)got.size() == n);
+    const int step = n > 400 ? 7 : 1;               // (a long list: every seventh term and both sides of every pass boundary)
+    for (int t = 0; t < n && t < (int)got.size(); ++t) {
+      if (t % step && (t % kDiagValuesPerPass) > 1 && (t % kDiagValuesPerPass) < kDiagValuesPerPass - 2) continue;
+      long double want = 0;
+      for (u64 i = 0; i <= all; ++i) want += (__builtin_popcountll(i & z[(size_t)t]) & 1) ? -(long double)p[(size_t)i] : (long double)p[(size_t)i];
+      *worst = std::max(*worst, std::fabs((double)(got[(size_t)t] - want)));
+    }
+    if (cs.kind == 2) CHECK(std::memcmp(&got[3], &got[(size_t)(1 + cs.k + cs.k * (cs.k - 1) / 2 + 1)], sizeof(double)) == 0);
+    ++*cases;
+  }
+}
+
 int main() {
   std::mt19937_64 rng(12345);
   std::uniform_real_distribution<double> coef(-1.0, 1.0);
@@ -182,6 +283,29 @@ int main() {
   }
   const uint64_t top[1] = {1ull << 63};
   CHECK(check_diag_args(64, 1, top, c2, &g, "f") == QSIM_OK);
+
+  // the per-term values: tables, the host model of the pass against the direct sum, the argument checks
+  double worst_value = 0.0;
+  int value_cases = 0;
+  check_values(rng, &worst_value, &value_cases);
+  std::printf("%d lists of single terms: records and passes consistent; host model of the pass against the direct sum: max |value - want| = %.3e\n",
+              value_cases, worst_value);
+  CHECK(worst_value < 1e-12);                       // the bound of the device tests, on weights of total 1
+  double o2[2] = {0.0, 0.0};
+  CHECK(check_diag_value_args(14, 2, z2, o2, "f") == QSIM_OK);
+  CHECK(check_diag_value_args(14, 0, nullptr, nullptr, "f") == QSIM_OK);
+  CHECK(check_diag_value_args(14, -1, z2, o2, "f") == QSIM_ERR_INVALID && g_err == "f: n_terms = -1");
+  CHECK(check_diag_value_args(14, kDiagMaxTerms + 1, z2, o2, "f") == QSIM_ERR_INVALID);   // (refused before anything is read)
+  CHECK(g_err.find("16385 terms in one call, at most 16384") != std::string::npos);
+  CHECK(check_diag_value_args(14, 2, nullptr, o2, "f") == QSIM_ERR_INVALID && g_err == "f: null argument");
+  CHECK(check_diag_value_args(14, 2, z2, nullptr, "f") == QSIM_ERR_INVALID && g_err == "f: null argument");
+  CHECK(check_diag_value_args(14, -1, nullptr, nullptr, "f") == QSIM_ERR_INVALID && g_err == "f: n_terms = -1");   // n_terms before null
+  for (u64 bad : {1ull << 14, 1ull << 15, 1ull << 63}) {
+    const uint64_t zb[2] = {1, bad};
+    CHECK(check_diag_value_args(14, 2, zb, o2, "f") == QSIM_ERR_NONLOCAL);
+    CHECK(g_err.find("term 1 acts on index bit") != std::string::npos && g_err.find("log2(chunk_size)=14") != std::string::npos);
+  }
+  CHECK(check_diag_value_args(64, 1, top, o2, "f") == QSIM_OK);
   if (g_failed) { std::printf("diag_plan_check: %d checks FAILED\n", g_failed); return 1; }
   std::printf("diag_plan_check: ok\n");
   return 0;
