@@ -107,15 +107,14 @@ int qsim_lincomb(qsim_chunk* dst, const double dst_coeff[2], int n_src, const qs
 #endif
   {
     const double bytes = 16.0 * (double)((rd ? 1 : 0) + n_src + nb + (wr ? 1 : 0)) * (double)a.n;
-    ProfileScope prof(15, bytes, dst->stream, nt);
+    ProfileScope prof(kClsLincomb, bytes, dst->stream, nt);
 #ifdef QSIM_PROBES
     if (items == 2) QSIM_WITH_NT((launch_lincomb<NT, 2>(rd, wr, n_src, nb, grid, dst->stream, a)));
     else
 #endif
     QSIM_WITH_NT(launch_lincomb<NT>(rd, wr, n_src, nb, grid, dst->stream, a));
-    HIP_TRY(hipGetLastError());
-    prof.done(dst->stream);
   }
+  HIP_TRY(hipGetLastError());
   if (!a.width) return QSIM_OK;                     // enqueued on dst's stream like the gate calls
   if ((rc = sum_rows(dst, a.partial, grid, a.width, dev_out))) return rc;
   double res[kLcMaxWidth];

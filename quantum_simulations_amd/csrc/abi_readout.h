@@ -157,16 +157,15 @@ int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out)
   double* dev_out = partial + ((u64)grid << 8);
   const bool nt = c->span_bytes > tuning().mall_bytes;
   {
-    ProfileScope prof(8, 16.0 * (double)amps(c), c->stream, nt);
+    ProfileScope prof(kClsHist, 16.0 * (double)amps(c), c->stream, nt);
     switch (n_item) {
       case 0: QSIM_WITH_NT(hipLaunchKernelGGL((k_hist<0, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a)); break;
       case 1: QSIM_WITH_NT(hipLaunchKernelGGL((k_hist<1, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a)); break;
       case 2: QSIM_WITH_NT(hipLaunchKernelGGL((k_hist<2, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a)); break;
       default: QSIM_WITH_NT(hipLaunchKernelGGL((k_hist<3, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a)); break;
     }
-    HIP_TRY(hipGetLastError());
-    prof.done(c->stream);
   }
+  HIP_TRY(hipGetLastError());
   if ((rc = sum_rows(c, partial, grid, nbins, dev_out))) return rc;
   return fetch_doubles(c, dev_out, (u64)nbins, out);
 }
@@ -261,7 +260,7 @@ int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, dou
   HIP_TRY(hipSetDevice(c->device));
   const bool nt = c->span_bytes > tuning().mall_bytes;
   {
-    ProfileScope prof(11, 16.0 * (double)amps(c), c->stream, nt);
+    ProfileScope prof(kClsRdm, 16.0 * (double)amps(c), c->stream, nt);
 #define QSIM_RDM_LAUNCH(KERNEL, R) QSIM_WITH_NT(hipLaunchKernelGGL((KERNEL<R, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a));
 #ifdef QSIM_PROBES
     if (tuning().rdm_form == 1 && r >= 4) {
@@ -277,9 +276,8 @@ int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, dou
       default: QSIM_RDM_LAUNCH(k_rdm_mfma, 6) break;
     }
 #undef QSIM_RDM_LAUNCH
-    HIP_TRY(hipGetLastError());
-    prof.done(c->stream);
   }
+  HIP_TRY(hipGetLastError());
   if ((rc = sum_rows(c, a.partial, grid, dd, dev_out))) return rc;
   std::vector<double> tri((size_t)dd);
   if ((rc = fetch_doubles(c, dev_out, (u64)dd, tri.data()))) return rc;
@@ -339,11 +337,10 @@ int qsim_sample(qsim_chunk* c, uint64_t n_shots, const double* randnums, uint64_
   HIP_TRY(hipSetDevice(c->device));
   const bool nt = c->span_bytes > tuning().mall_bytes;
   {
-    ProfileScope prof(9, 16.0 * (double)n, c->stream, nt);
+    ProfileScope prof(kClsSampleSums, 16.0 * (double)n, c->stream, nt);
     QSIM_WITH_NT(hipLaunchKernelGGL((k_sample_block_sums<NT>), grid_for(n_blocks), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, dev_sums));
-    HIP_TRY(hipGetLastError());
-    prof.done(c->stream);
   }
+  HIP_TRY(hipGetLastError());
   std::vector<double> cdf(n_blocks);
   if ((rc = fetch_doubles(c, dev_sums, n_blocks, cdf.data()))) return rc;
   *n_passes = 1;
@@ -370,11 +367,10 @@ int qsim_sample(qsim_chunk* c, uint64_t n_shots, const double* randnums, uint64_
   HIP_TRY(hipMemcpyAsync(dev_hit, hit.data(), sizeof(u64) * n_hit, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(dev_first, first.data(), sizeof(unsigned) * (n_hit + 1), hipMemcpyHostToDevice, c->stream));
   {
-    ProfileScope prof(10, 16.0 * (double)std::min<u64>(n, n_hit << kSampleBlockBits), c->stream, nt);
+    ProfileScope prof(kClsSampleResolve, 16.0 * (double)std::min<u64>(n, n_hit << kSampleBlockBits), c->stream, nt);
     QSIM_WITH_NT(hipLaunchKernelGGL((k_sample_resolve<NT>), grid_for(n_hit), dim3(kBlock), 0, c->stream, (const double2*)c->amp, n, n_blocks, (const u64*)dev_hit, (const unsigned*)dev_first, n_hit, dev_slot));
-    HIP_TRY(hipGetLastError());
-    prof.done(c->stream);
   }
+  HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(slot.data(), dev_slot, sizeof(u64) * n_shots, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (u64 j = 0; j < n_shots; ++j) out_indices[order[j]] = slot[j];

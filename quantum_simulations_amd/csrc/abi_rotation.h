@@ -27,33 +27,34 @@ int qsim_apply_pauli_rotations(qsim_chunk* c, int n, const uint64_t* x_masks, co
   const int np = (int)pp.plan.tile.size();
   for (int q = 0; q < np; ++q) {
     const int first = pp.first[(size_t)q];
-    ProfileScope prof(12, bytes, c->stream, nt);
-    if (pp.wide_term[(size_t)q] >= 0) {
-      const PauliTerm e = pp.entry(first);
-      const int t = pp.wide_term[(size_t)q];
-      RotWideArgs w;
-      std::memset(&w, 0, sizeof w);
-      w.amp = c->amp;
-      w.half = amps(c) >> 1;
-      w.x = x_masks[t];
-      w.z = z_masks[t];
-      w.h = 63 - __builtin_clzll(w.x);
-      w.c = e.f0;
-      w.fr = e.f1;
-      w.fi = e.f2;
-      QSIM_WITH_NT(hipLaunchKernelGGL((k_rot_wide<NT>), dim3(pauli_wide_grid(w.half)), dim3(kBlock), 0, c->stream, w));
-    } else {
-      RotArgs a;
-      std::memset(&a, 0, sizeof a);
-      a.amp = c->amp;
-      a.terms = pp.at(c->work, first);
-      a.w = tile_walk(c->k, pp.plan.tile[(size_t)q]);
-      a.n_terms = pp.plan.count[(size_t)q];
-      const unsigned grid = (unsigned)std::min<u64>(a.w.n_tiles, kExpMaxWg);
-      QSIM_WITH_NT(hipLaunchKernelGGL((k_rot_tile<NT>), dim3(grid), dim3(kBlock), 0, c->stream, a));
+    {
+      ProfileScope prof(kClsRot, bytes, c->stream, nt);
+      if (pp.wide_term[(size_t)q] >= 0) {
+        const PauliTerm e = pp.entry(first);
+        const int t = pp.wide_term[(size_t)q];
+        RotWideArgs w;
+        std::memset(&w, 0, sizeof w);
+        w.amp = c->amp;
+        w.half = amps(c) >> 1;
+        w.x = x_masks[t];
+        w.z = z_masks[t];
+        w.h = 63 - __builtin_clzll(w.x);
+        w.c = e.f0;
+        w.fr = e.f1;
+        w.fi = e.f2;
+        QSIM_WITH_NT(hipLaunchKernelGGL((k_rot_wide<NT>), dim3(pauli_wide_grid(w.half)), dim3(kBlock), 0, c->stream, w));
+      } else {
+        RotArgs a;
+        std::memset(&a, 0, sizeof a);
+        a.amp = c->amp;
+        a.terms = pp.at(c->work, first);
+        a.w = tile_walk(c->k, pp.plan.tile[(size_t)q]);
+        a.n_terms = pp.plan.count[(size_t)q];
+        const unsigned grid = (unsigned)std::min<u64>(a.w.n_tiles, kExpMaxWg);
+        QSIM_WITH_NT(hipLaunchKernelGGL((k_rot_tile<NT>), dim3(grid), dim3(kBlock), 0, c->stream, a));
+      }
     }
     HIP_TRY(hipGetLastError());
-    prof.done(c->stream);
   }
   *n_passes = np;
   return QSIM_OK;

@@ -31,35 +31,36 @@ int qsim_apply_pauli_sum(qsim_chunk* dst, const qsim_chunk* src, int n_terms, co
   for (int q = 0; q < np; ++q) {
     const bool acc = q > 0;
     const double bytes = (acc ? 48.0 : 32.0) * (double)amps(dst);
-    ProfileScope prof(13, bytes, dst->stream, nt);
-    if (pp.wide_term[(size_t)q] >= 0) {
-      const int t = pp.wide_term[(size_t)q];
-      PsumWideArgs w;
-      std::memset(&w, 0, sizeof w);
-      w.dst = dst->amp;
-      w.src = src->amp;
-      w.n = amps(dst);
-      w.x = x_masks[t];
-      w.z = z_masks[t];
-      w.gr = pp.entry(pp.first[(size_t)q]).f0;
-      w.gi = pp.entry(pp.first[(size_t)q]).f1;
-      const unsigned grid = pauli_wide_grid(w.n);
-      if (acc) QSIM_WITH_NT(hipLaunchKernelGGL((k_psum_wide<NT, true>), dim3(grid), dim3(kBlock), 0, dst->stream, w));
-      else QSIM_WITH_NT(hipLaunchKernelGGL((k_psum_wide<NT, false>), dim3(grid), dim3(kBlock), 0, dst->stream, w));
-    } else {
-      PsumArgs a;
-      std::memset(&a, 0, sizeof a);
-      a.dst = dst->amp;
-      a.src = src->amp;
-      a.terms = pp.at(dst->work, pp.first[(size_t)q]);
-      a.w = tile_walk(k, pp.plan.tile[(size_t)q]);
-      a.n_terms = pp.plan.count[(size_t)q];
-      const unsigned grid = (unsigned)std::min<u64>(a.w.n_tiles, kExpMaxWg);
-      if (acc) QSIM_WITH_NT(hipLaunchKernelGGL((k_psum_tile<NT, true>), dim3(grid), dim3(kBlock), 0, dst->stream, a));
-      else QSIM_WITH_NT(hipLaunchKernelGGL((k_psum_tile<NT, false>), dim3(grid), dim3(kBlock), 0, dst->stream, a));
+    {
+      ProfileScope prof(kClsPsum, bytes, dst->stream, nt);
+      if (pp.wide_term[(size_t)q] >= 0) {
+        const int t = pp.wide_term[(size_t)q];
+        PsumWideArgs w;
+        std::memset(&w, 0, sizeof w);
+        w.dst = dst->amp;
+        w.src = src->amp;
+        w.n = amps(dst);
+        w.x = x_masks[t];
+        w.z = z_masks[t];
+        w.gr = pp.entry(pp.first[(size_t)q]).f0;
+        w.gi = pp.entry(pp.first[(size_t)q]).f1;
+        const unsigned grid = pauli_wide_grid(w.n);
+        if (acc) QSIM_WITH_NT(hipLaunchKernelGGL((k_psum_wide<NT, true>), dim3(grid), dim3(kBlock), 0, dst->stream, w));
+        else QSIM_WITH_NT(hipLaunchKernelGGL((k_psum_wide<NT, false>), dim3(grid), dim3(kBlock), 0, dst->stream, w));
+      } else {
+        PsumArgs a;
+        std::memset(&a, 0, sizeof a);
+        a.dst = dst->amp;
+        a.src = src->amp;
+        a.terms = pp.at(dst->work, pp.first[(size_t)q]);
+        a.w = tile_walk(k, pp.plan.tile[(size_t)q]);
+        a.n_terms = pp.plan.count[(size_t)q];
+        const unsigned grid = (unsigned)std::min<u64>(a.w.n_tiles, kExpMaxWg);
+        if (acc) QSIM_WITH_NT(hipLaunchKernelGGL((k_psum_tile<NT, true>), dim3(grid), dim3(kBlock), 0, dst->stream, a));
+        else QSIM_WITH_NT(hipLaunchKernelGGL((k_psum_tile<NT, false>), dim3(grid), dim3(kBlock), 0, dst->stream, a));
+      }
     }
     HIP_TRY(hipGetLastError());
-    prof.done(dst->stream);
   }
   *n_passes = np;
   return QSIM_OK;
@@ -78,36 +79,37 @@ int qsim_overlap_pauli(qsim_chunk* ket, const qsim_chunk* bra, int n_terms, cons
   const bool nt = pair_streams(ket, bra);
   const double bytes = 32.0 * (double)amps(ket);
   const auto launch = [&](int q, const PauliTerm* terms, double* partial, unsigned* rows) {
-    ProfileScope prof(14, bytes, ket->stream, nt);
-    if (pp.wide_term[(size_t)q] >= 0) {
-      const int t = pp.wide_term[(size_t)q];
-      OvlWideArgs w;
-      std::memset(&w, 0, sizeof w);
-      w.bra = bra->amp;
-      w.ket = ket->amp;
-      w.partial = partial;
-      w.n = amps(ket);
-      w.x = x_masks[t];
-      w.z = z_masks[t];
-      w.gr = pp.entry(pp.first[(size_t)q]).f0;
-      w.gi = pp.entry(pp.first[(size_t)q]).f1;
-      *rows = pauli_wide_grid(w.n);
-      QSIM_WITH_NT(hipLaunchKernelGGL((k_ovl_wide<NT>), dim3(*rows), dim3(kBlock), 0, ket->stream, w));
-    } else {
-      OvlArgs a;
-      std::memset(&a, 0, sizeof a);
-      a.bra = bra->amp;
-      a.ket = ket->amp;
-      a.terms = terms;
-      a.partial = partial;
-      a.w = tile_walk(ket->k, pp.plan.tile[(size_t)q]);
-      a.n_terms = pp.plan.count[(size_t)q];
-      a.slices = pauli_slices(a.n_terms);
-      *rows = (unsigned)std::min<u64>(a.w.n_tiles, kOvlMaxWg);
-      QSIM_WITH_NT(hipLaunchKernelGGL((k_ovl_tile<NT>), dim3(*rows), dim3(kBlock), 0, ket->stream, a));
+    {
+      ProfileScope prof(kClsOvl, bytes, ket->stream, nt);
+      if (pp.wide_term[(size_t)q] >= 0) {
+        const int t = pp.wide_term[(size_t)q];
+        OvlWideArgs w;
+        std::memset(&w, 0, sizeof w);
+        w.bra = bra->amp;
+        w.ket = ket->amp;
+        w.partial = partial;
+        w.n = amps(ket);
+        w.x = x_masks[t];
+        w.z = z_masks[t];
+        w.gr = pp.entry(pp.first[(size_t)q]).f0;
+        w.gi = pp.entry(pp.first[(size_t)q]).f1;
+        *rows = pauli_wide_grid(w.n);
+        QSIM_WITH_NT(hipLaunchKernelGGL((k_ovl_wide<NT>), dim3(*rows), dim3(kBlock), 0, ket->stream, w));
+      } else {
+        OvlArgs a;
+        std::memset(&a, 0, sizeof a);
+        a.bra = bra->amp;
+        a.ket = ket->amp;
+        a.terms = terms;
+        a.partial = partial;
+        a.w = tile_walk(ket->k, pp.plan.tile[(size_t)q]);
+        a.n_terms = pp.plan.count[(size_t)q];
+        a.slices = pauli_slices(a.n_terms);
+        *rows = (unsigned)std::min<u64>(a.w.n_tiles, kOvlMaxWg);
+        QSIM_WITH_NT(hipLaunchKernelGGL((k_ovl_tile<NT>), dim3(*rows), dim3(kBlock), 0, ket->stream, a));
+      }
     }
     HIP_TRY(hipGetLastError());
-    prof.done(ket->stream);
     return QSIM_OK;
   };
   return pauli_reduce_call(ket, pp, 2, kOvlMaxWg, launch, out_re_im, n_passes);

@@ -335,7 +335,7 @@ static int apply_dense_block(qsim_chunk* c, int k, const int32_t* qubits, const 
     a.mat = reinterpret_cast<const double2*>(c->scratch);
     a.count = amps(c) >> k;
     for (int i = 0; i < 4; ++i) { a.bit[i] = i < k ? qubits[i] : 0; a.pos[i] = i < k ? sorted[i] : 0; }
-    ProfileScope prof(7, 32.0 * (double)amps(c), c->stream, nt);
+    ProfileScope prof(kClsDense, 32.0 * (double)amps(c), c->stream, nt);
     if (c->k >= k + 4 && ((tuning().dense_mfma >> (k - 3)) & 1)) {
       DenseMfmaArgs d;
       d.amp = reinterpret_cast<double*>(c->amp);
@@ -353,61 +353,59 @@ static int apply_dense_block(qsim_chunk* c, int k, const int32_t* qubits, const 
       if (k == 3) QSIM_WITH_NT(hipLaunchKernelGGL((k_dense<3, NT>), grid_for(blocks), dim3(kBlock), 0, c->stream, a));
       else QSIM_WITH_NT(hipLaunchKernelGGL((k_dense<4, NT>), grid_for(blocks), dim3(kBlock), 0, c->stream, a));
     }
-    prof.done(c->stream);
-    HIP_TRY(hipGetLastError());
-    return QSIM_OK;
-  }
+  } else
 #endif
-  ProfileScope prof(7, 32.0 * (double)amps(c), c->stream, nt);
-  if (c->k >= k + 4) {
-    DenseMfma2Args d;
-    d.amp = c->amp;
-    d.mat = reinterpret_cast<const double2*>(c->scratch);
-    d.col_blocks = amps(c) >> (k + 4);
-    d.consec_log2 = 0;
-    d.skew = 0;
-    for (int i = 0; i < 6; ++i) {
-      d.pos[i] = i < k ? sorted[i] : 0;
-      d.to_caller[i] = 0;
-      for (int q = 0; q < k; ++q) if (i < k && qubits[q] == sorted[i]) d.to_caller[i] = q;
-    }
-    // k <= 4: a wave takes four CONSECUTIVE column groups (the matrix image costs a few loads per wave; 64 columns = 1 KiB
-    // contiguous per pattern over its four steps: -3 / -5 % against groups strided through the region, the worst
-    // placements -8 / -13 %); k = 5, 6: resident workgroups that walk the column groups (the image is built once per
-    // workgroup in LDS: 32 / 128 KiB) -- for k = 5 TWO per CU, not the four that fit: fewer bytes in flight suit the
-    // memory system better (-9 %; one per CU is as good, three and four are not).  profiles/r05q_dense_knob_scans.txt
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-    int pf = -1, groups = 4, wgs_per_cu = 2, consec_log2 = k <= 4 ? 2 : 0;       // (pf: the product's choice per k, kDensePf)
+  {
+    ProfileScope prof(kClsDense, 32.0 * (double)amps(c), c->stream, nt);
+    if (c->k >= k + 4) {
+      DenseMfma2Args d;
+      d.amp = c->amp;
+      d.mat = reinterpret_cast<const double2*>(c->scratch);
+      d.col_blocks = amps(c) >> (k + 4);
+      d.consec_log2 = 0;
+      d.skew = 0;
+      for (int i = 0; i < 6; ++i) {
+        d.pos[i] = i < k ? sorted[i] : 0;
+        d.to_caller[i] = 0;
+        for (int q = 0; q < k; ++q) if (i < k && qubits[q] == sorted[i]) d.to_caller[i] = q;
+      }
+      // k <= 4: a wave takes four CONSECUTIVE column groups (the matrix image costs a few loads per wave; 64 columns = 1 KiB
+      // contiguous per pattern over its four steps: -3 / -5 % against groups strided through the region, the worst
+      // placements -8 / -13 %); k = 5, 6: resident workgroups that walk the column groups (the image is built once per
+      // workgroup in LDS: 32 / 128 KiB) -- for k = 5 TWO per CU, not the four that fit: fewer bytes in flight suit the
+      // memory system better (-9 %; one per CU is as good, three and four are not).  profiles/r05q_dense_knob_scans.txt
+      int cus = 256;
+      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+      int pf = -1, groups = 4, wgs_per_cu = 2, consec_log2 = k <= 4 ? 2 : 0;       // (pf: the product's choice per k, kDensePf)
 #ifdef QSIM_PROBES
-    if (tuning().dense_pf >= 0) pf = tuning().dense_pf;
-    if (tuning().dense_groups > 0) groups = tuning().dense_groups;
-    if (tuning().dense_wgs > 0) wgs_per_cu = tuning().dense_wgs;
-    if (tuning().dense_consec > 0) { consec_log2 = 0; while ((2 << consec_log2) <= tuning().dense_consec) ++consec_log2; }
-    d.skew = (u64)tuning().dense_skew;
+      if (tuning().dense_pf >= 0) pf = tuning().dense_pf;
+      if (tuning().dense_groups > 0) groups = tuning().dense_groups;
+      if (tuning().dense_wgs > 0) wgs_per_cu = tuning().dense_wgs;
+      if (tuning().dense_consec > 0) { consec_log2 = 0; while ((2 << consec_log2) <= tuning().dense_consec) ++consec_log2; }
+      d.skew = (u64)tuning().dense_skew;
 #endif
-    d.consec_log2 = consec_log2;
-    if (k <= 4) {
-      const u64 waves = (d.col_blocks + groups - 1) / groups;
-      const unsigned grid = (unsigned)std::min<u64>(((std::max<u64>((waves + 3) / 4, 1) + 7) & ~7ull), 1u << 20);   // (whole octets: one region per XCD)
-      if (k == 3) QSIM_WITH_NT(launch_dense_mfma2<3, NT, 256>(d, grid, c->stream, pf));
-      else QSIM_WITH_NT(launch_dense_mfma2<4, NT, 256>(d, grid, c->stream, pf));
-    } else if (k == 5) {
-      const unsigned grid = (unsigned)std::min<u64>((std::max<u64>((d.col_blocks + 3) / 4, 1) + 7) & ~7ull, (u64)cus * wgs_per_cu);
-      QSIM_WITH_NT(launch_dense_mfma2<5, NT, 256>(d, grid, c->stream, pf));
+      d.consec_log2 = consec_log2;
+      if (k <= 4) {
+        const u64 waves = (d.col_blocks + groups - 1) / groups;
+        const unsigned grid = (unsigned)std::min<u64>(((std::max<u64>((waves + 3) / 4, 1) + 7) & ~7ull), 1u << 20);   // (whole octets: one region per XCD)
+        if (k == 3) QSIM_WITH_NT(launch_dense_mfma2<3, NT, 256>(d, grid, c->stream, pf));
+        else QSIM_WITH_NT(launch_dense_mfma2<4, NT, 256>(d, grid, c->stream, pf));
+      } else if (k == 5) {
+        const unsigned grid = (unsigned)std::min<u64>((std::max<u64>((d.col_blocks + 3) / 4, 1) + 7) & ~7ull, (u64)cus * wgs_per_cu);
+        QSIM_WITH_NT(launch_dense_mfma2<5, NT, 256>(d, grid, c->stream, pf));
+      } else {
+        const unsigned grid = (unsigned)std::min<u64>((std::max<u64>((d.col_blocks + 7) / 8, 1) + 7) & ~7ull, (u64)cus);
+        QSIM_WITH_NT(launch_dense_mfma2<6, NT, 512>(d, grid, c->stream, pf));
+      }
     } else {
-      const unsigned grid = (unsigned)std::min<u64>((std::max<u64>((d.col_blocks + 7) / 8, 1) + 7) & ~7ull, (u64)cus);
-      QSIM_WITH_NT(launch_dense_mfma2<6, NT, 512>(d, grid, c->stream, pf));
+      DenseSmallArgs a;
+      a.amp = c->amp;
+      a.mat = reinterpret_cast<const double2*>(c->scratch);
+      a.k = k;
+      for (int i = 0; i < 6; ++i) { a.bit[i] = i < k ? qubits[i] : 0; a.pos[i] = i < k ? sorted[i] : 0; }
+      hipLaunchKernelGGL(k_dense_small, dim3((unsigned)(amps(c) >> k)), dim3(64), 0, c->stream, a);
     }
-  } else {
-    DenseSmallArgs a;
-    a.amp = c->amp;
-    a.mat = reinterpret_cast<const double2*>(c->scratch);
-    a.k = k;
-    for (int i = 0; i < 6; ++i) { a.bit[i] = i < k ? qubits[i] : 0; a.pos[i] = i < k ? sorted[i] : 0; }
-    hipLaunchKernelGGL(k_dense_small, dim3((unsigned)(amps(c) >> k)), dim3(64), 0, c->stream, a);
   }
-  prof.done(c->stream);
   HIP_TRY(hipGetLastError());
   return QSIM_OK;
 }

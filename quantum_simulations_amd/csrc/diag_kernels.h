@@ -8,7 +8,8 @@
 // 2^tb CONTIGUOUS amplitudes on the lowest tb = min(k, kExpTileBits) index bits (no TileWalk), base = o << tb.  With the
 // outer bits fixed,   E(base | j) = sum_m W[m] (-1)^popcount(j & m),   W[m] = sum_{t: zi_t = m} c_t (-1)^popcount(base & zo_t):
 // E over the tile is the Walsh-Hadamard transform of the sparse spectrum W (tables and summation order: diag_plan.h).
-// Per tile (k_diag_tile, one workgroup per tile in a grid-stride loop):
+// Per tile (diag_tiles below, the loop of k_diag_tile, k_diag_apply and k_diag_overlap: one workgroup per tile in a
+// grid-stride loop):
 //   1. the thread's kExpLoads amplitudes j = tid + it * kBlock are loaded into REGISTERS and stay there (tile_load's
 //      slots): the LDS of a workgroup is W (16 KiB) and the piece slots (8 KiB), 24 KiB against the 32 KiB tile of the
 //      other Pauli passes, so four workgroups per CU fit with room to spare, and the loads are in flight during 2. and 3.;
@@ -19,10 +20,12 @@
 //      above 2^tb and E(j) repeats -- in four rounds of register butterflies: bits 0-2, 3-5, 6-7 through LDS with a
 //      __syncthreads() between rounds, bits 8-10 on the thread's own slots tid + r * kBlock, which leaves E(j) in
 //      registers next to amplitude j.  The last round zeroes what it reads: W is clear for the next tile;
-//   4. phase:   psi_j *= cos(gamma E_j) - i sin(gamma E_j) (diag_sincos), stored back in place (tiles partition the
+//   4. the kernel's own lines, body(base, x, e):
+//      phase:   psi_j *= cos(gamma E_j) - i sin(gamma E_j) (diag_sincos), stored back in place (tiles partition the
 //      index space);
 //      moments: p = |psi_j|^2 into the thread's running sums of p, p E, p E^2 over its slots and tiles; at the end lane
-//      tree -> waves in wave order -> the workgroup's row of partials; k_hist_sum adds the rows in workgroup order;
+//      tree -> waves in wave order -> the workgroup's row of partials (block_sum_row); k_hist_sum adds the rows in
+//      workgroup order;
 //      sum (k_diag_apply):       dst_j = E_j src_j, or dst_j += E_j src_j: E is a multiplier, not an angle;
 //      overlap (k_diag_overlap): q = conj(bra_j) ket_j into running sums of q and q E_j (re, im), reduced like the moments.
 //      The second operand of these two (dst when accumulating, bra) is loaded AFTER the transform: its 8 double2 are
@@ -144,51 +147,73 @@ __device__ __forceinline__ void diag_load(const double2* amp, u64 base, int S, d
     x[it] = (int)threadIdx.x + it * kBlock < S ? ld_amp<NT>(amp + (base | (u64)((int)threadIdx.x + it * kBlock))) : make_double2(0.0, 0.0);
 }
 
-template <bool NT, int MODE>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_tile(const DiagArgs a) {
+// Steps 1 to 3 for the workgroup's tiles o = blockIdx.x, blockIdx.x + gridDim.x, ..., then body(base, x, e) with the
+// thread's amplitudes x[it] of a.amp and E in e[it], slot j = tid + it * kBlock (x is zero above S = 2^tb); body is a
+// lambda marked always_inline.  The one place that owns W and the slots, and so the rule that W is zero on entry of
+// diag_energies and on its return.
+template <bool NT, class Body>
+__device__ __forceinline__ void diag_tiles(const DiagArgs& a, Body body) {
   __shared__ double W[kExpTile];
   __shared__ double slots[kDiagMaxSlots];
-  const int S = 1 << a.tb;
-  const int tid = threadIdx.x;
 #pragma unroll
-  for (int it = 0; it < kExpLoads; ++it) W[tid + it * kBlock] = 0.0;
-  double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+  for (int it = 0; it < kExpLoads; ++it) W[(int)threadIdx.x + it * kBlock] = 0.0;
   for (u64 o = blockIdx.x; o < a.n_tiles; o += gridDim.x) {
     const u64 base = o << a.tb;
     double2 x[kExpLoads];
-    diag_load<NT>(a.amp, base, S, x);
+    diag_load<NT>(a.amp, base, 1 << a.tb, x);
     double e[kExpLoads];
     diag_energies(a, base, W, slots, e);
+    body(base, x, e);
+  }
+}
+
+// N running sums of the workgroup's threads into row[0 .. N-1]: lane tree, lane 0 of each wave into red[wave][i], then
+// thread i adds red[0][i], red[1][i], ... in wave order, starting from red[0][i].  Every thread of the workgroup calls it.
+template <int N>
+__device__ __forceinline__ void block_sum_row(const double (&s)[N], double* row) {
+  __shared__ double red[kBlock / 64][N];
+  const int tid = threadIdx.x;
 #pragma unroll
-    for (int it = 0; it < kExpLoads; ++it) {
-      if (MODE == kDiagPhase) {
+  for (int i = 0; i < N; ++i) {
+    const double v = wave_sum(s[i]);
+    if ((tid & 63) == 0) red[tid >> 6][i] = v;
+  }
+  __syncthreads();
+  if (tid < N) {
+    double v = red[0][tid];
+    for (int w = 1; w < kBlock / 64; ++w) v += red[w][tid];
+    row[tid] = v;
+  }
+}
+
+template <bool NT, int MODE>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_tile(const DiagArgs a) {
+  const int S = 1 << a.tb;
+  const int tid = threadIdx.x;
+  if (MODE == kDiagPhase) {
+    diag_tiles<NT>(a, [&](u64 base, const double2* x, const double* e) __attribute__((always_inline)) {
+#pragma unroll
+      for (int it = 0; it < kExpLoads; ++it) {
         double s, c;
         diag_sincos(a.gamma * e[it], &s, &c);
         if (tid + it * kBlock < S)
           st_amp<NT>(a.amp + (base | (u64)(tid + it * kBlock)),
                      make_double2(fma(x[it].x, c, x[it].y * s), fma(x[it].y, c, -(x[it].x * s))));
         __builtin_amdgcn_sched_barrier(0);          // one slot at a time: interleaved they need more than 128 VGPRs
-      } else {
-        const double p = fma(x[it].x, x[it].x, x[it].y * x[it].y), pe = p * e[it];
-        m0 += p;
-        m1 += pe;
-        m2 = fma(pe, e[it], m2);
       }
-    }
-  }
-  if (MODE == kDiagMoments) {
-    __shared__ double red[kBlock / 64][3];
-    const int lane = tid & 63, wave = tid >> 6;
-    m0 = wave_sum(m0);
-    m1 = wave_sum(m1);
-    m2 = wave_sum(m2);
-    if (lane == 0) { red[wave][0] = m0; red[wave][1] = m1; red[wave][2] = m2; }
-    __syncthreads();
-    if (tid < 3) {
-      double s = red[0][tid];
-      for (int w = 1; w < kBlock / 64; ++w) s += red[w][tid];
-      a.partial[(u64)blockIdx.x * 3 + tid] = s;
-    }
+    });
+  } else {
+    double m[3] = {0.0, 0.0, 0.0};
+    diag_tiles<NT>(a, [&](u64 base, const double2* x, const double* e) __attribute__((always_inline)) {
+#pragma unroll
+      for (int it = 0; it < kExpLoads; ++it) {
+        const double p = fma(x[it].x, x[it].x, x[it].y * x[it].y), pe = p * e[it];
+        m[0] += p;
+        m[1] += pe;
+        m[2] = fma(pe, e[it], m[2]);
+      }
+    });
+    block_sum_row(m, a.partial + (u64)blockIdx.x * 3);
   }
 }
 
@@ -273,18 +298,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
 // forms alike): writing 98 VGPRs, accumulating 128, overlap 112; no spill, no scratch, four workgroups per CU each.
 template <bool NT, bool ACC>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_apply(const DiagArgs a) {
-  __shared__ double W[kExpTile];
-  __shared__ double slots[kDiagMaxSlots];
   const int S = 1 << a.tb;
   const int tid = threadIdx.x;
-#pragma unroll
-  for (int it = 0; it < kExpLoads; ++it) W[tid + it * kBlock] = 0.0;
-  for (u64 o = blockIdx.x; o < a.n_tiles; o += gridDim.x) {
-    const u64 base = o << a.tb;
-    double2 x[kExpLoads];
-    diag_load<NT>(a.amp, base, S, x);
-    double e[kExpLoads];
-    diag_energies(a, base, W, slots, e);
+  diag_tiles<NT>(a, [&](u64 base, const double2* x, const double* e) __attribute__((always_inline)) {
     double2 y[kExpLoads];
     if (ACC) diag_load<NT>(a.other, base, S, y);
 #pragma unroll
@@ -294,29 +310,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
                             : make_double2(e[it] * x[it].x, e[it] * x[it].y);
       st_amp<NT>(a.other + (base | (u64)(tid + it * kBlock)), v);
     }
-  }
+  });
 }
 
 // sum_j conj(bra_j) ket_j and sum_j conj(bra_j) E_j ket_j, (re, im) each: a.amp = ket, a.other = bra (it may be ket);
 // the workgroup's row of 4 partials into a.partial, by the reduction of the moments.
 template <bool NT>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_diag_overlap(const DiagArgs a) {
-  __shared__ double W[kExpTile];
-  __shared__ double slots[kDiagMaxSlots];
-  __shared__ double red[kBlock / 64][4];
-  const int S = 1 << a.tb;
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int it = 0; it < kExpLoads; ++it) W[tid + it * kBlock] = 0.0;
   double s[4] = {0.0, 0.0, 0.0, 0.0};
-  for (u64 o = blockIdx.x; o < a.n_tiles; o += gridDim.x) {
-    const u64 base = o << a.tb;
-    double2 x[kExpLoads];
-    diag_load<NT>(a.amp, base, S, x);
-    double e[kExpLoads];
-    diag_energies(a, base, W, slots, e);
+  diag_tiles<NT>(a, [&](u64 base, const double2* x, const double* e) __attribute__((always_inline)) {
     double2 b[kExpLoads];
-    diag_load<NT>(a.other, base, S, b);
+    diag_load<NT>(a.other, base, 1 << a.tb, b);
 #pragma unroll
     for (int it = 0; it < kExpLoads; ++it) {        // (slots above S hold zeros in x and b)
       const double re = fma(b[it].x, x[it].x, b[it].y * x[it].y), im = fma(b[it].x, x[it].y, -(b[it].y * x[it].x));
@@ -325,17 +329,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
       s[2] = fma(re, e[it], s[2]);
       s[3] = fma(im, e[it], s[3]);
     }
-  }
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    s[i] = wave_sum(s[i]);
-    if (lane == 0) red[wave][i] = s[i];
-  }
-  __syncthreads();
-  if (tid < 4) {
-    double v = red[0][tid];
-    for (int w = 1; w < kBlock / 64; ++w) v += red[w][tid];
-    a.partial[(u64)blockIdx.x * 4 + tid] = v;
-  }
+  });
+  block_sum_row(s, a.partial + (u64)blockIdx.x * 4);
 }

@@ -41,19 +41,21 @@ struct DiagTable {
   int n_slots = 0;
 };
 
-// The checks of the two diagonal calls after the chunk's own, in this order: n_terms, null arguments, gamma (phase
-// only: null for moments), then term by term locality and a finite coefficient.
-static int check_diag_args(int k, int n_terms, const uint64_t* z_masks, const double* coeffs, const double* gamma, const char* what) {
+// The checks of the five diagonal calls after the chunk's own, in this order: n_terms, null arguments, gamma (phase
+// only: null otherwise), then term by term locality and a finite coefficient.  `per_term` is the caller's array of one
+// double per term: the coefficients (`coeffs` true), or what qsim_expectation_z_terms writes to, which is never read.
+static int check_diag_args(int k, int n_terms, const uint64_t* z_masks, const double* per_term, bool coeffs, const double* gamma,
+                           const char* what) {
   if (n_terms < 0) return fail(QSIM_ERR_INVALID, "%s: n_terms = %d", what, n_terms);
   if (n_terms > kDiagMaxTerms) return fail(QSIM_ERR_INVALID, "%s: %d terms in one call, at most %d", what, n_terms, kDiagMaxTerms);
-  if (n_terms > 0 && (!z_masks || !coeffs)) return fail(QSIM_ERR_INVALID, "%s: null argument", what);
+  if (n_terms > 0 && (!z_masks || !per_term)) return fail(QSIM_ERR_INVALID, "%s: null argument", what);
   if (gamma && !std::isfinite(*gamma)) return fail(QSIM_ERR_INVALID, "%s: gamma is not finite", what);
   const u64 all = k >= 64 ? ~0ull : (1ull << k) - 1;
   for (int t = 0; t < n_terms; ++t) {
     if (z_masks[t] & ~all)
       return fail(QSIM_ERR_NONLOCAL, "%s: term %d acts on index bit %d >= log2(chunk_size)=%d", what, t,
                   63 - __builtin_clzll(z_masks[t] & ~all), k);
-    if (!std::isfinite(coeffs[t])) return fail(QSIM_ERR_INVALID, "%s: coefficient of term %d is not finite", what, t);
+    if (coeffs && !std::isfinite(per_term[t])) return fail(QSIM_ERR_INVALID, "%s: coefficient of term %d is not finite", what, t);
   }
   return QSIM_OK;
 }
@@ -110,20 +112,6 @@ struct DiagValueTable {
   std::vector<DiagValueTerm> terms;
   std::vector<DiagValuePass> passes;
 };
-
-// The checks of qsim_expectation_z_terms after the chunk's own, in the order of check_diag_args: n_terms, null
-// arguments, then term by term locality.
-static int check_diag_value_args(int k, int n_terms, const uint64_t* z_masks, const double* out, const char* what) {
-  if (n_terms < 0) return fail(QSIM_ERR_INVALID, "%s: n_terms = %d", what, n_terms);
-  if (n_terms > kDiagMaxTerms) return fail(QSIM_ERR_INVALID, "%s: %d terms in one call, at most %d", what, n_terms, kDiagMaxTerms);
-  if (n_terms > 0 && (!z_masks || !out)) return fail(QSIM_ERR_INVALID, "%s: null argument", what);
-  const u64 all = k >= 64 ? ~0ull : (1ull << k) - 1;
-  for (int t = 0; t < n_terms; ++t)
-    if (z_masks[t] & ~all)
-      return fail(QSIM_ERR_NONLOCAL, "%s: term %d acts on index bit %d >= log2(chunk_size)=%d", what, t,
-                  63 - __builtin_clzll(z_masks[t] & ~all), k);
-  return QSIM_OK;
-}
 
 // the records and the passes of a checked call on tiles of tb bits
 static void diag_value_table(int tb, int n, const uint64_t* z_masks, DiagValueTable* d) {

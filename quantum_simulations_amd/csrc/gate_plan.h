@@ -140,6 +140,12 @@ static std::mutex g_prof_mu;
 static std::map<hipStream_t, ProfileState> g_profs;       // open profiles, by stream
 static std::vector<hipEvent_t> g_prof_pool;               // recycled events (guarded by g_prof_mu)
 static std::atomic<int> g_prof_open{0};
+// kernel classes of the launch profile: the enum and the names in the same order
+enum KernelClass {
+  kClsGate1, kClsGate2, kClsGate4, kClsShuffle11, kClsShuffle12, kClsShuffle21, kClsTile, kClsDense, kClsHist,
+  kClsSampleSums, kClsSampleResolve, kClsRdm, kClsRot, kClsPsum, kClsOvl, kClsLincomb, kClsDiag, kClsDiagApply,
+  kClsDiagOverlap, kClsDiagTermValues, kNumClasses
+};
 static const char* const kClassNames[] = {
     "k_gate<1> scale (diagonal subset)", "k_gate<2> 2x2 butterfly", "k_gate<4> 4x4 butterfly",
     "k_gate_shuffle<1,1> lane 1q", "k_gate_shuffle<1,2> lane 2q", "k_gate_shuffle<2,1> lane+reg 2q",
@@ -149,7 +155,7 @@ static const char* const kClassNames[] = {
     "k_ovl two-state overlaps", "k_lincomb linear combination", "k_diag diagonal Pauli sum",
     "k_diag_apply diagonal Pauli sum applied", "k_diag_overlap diagonal matrix element",
     "k_diag_term_values per-term Z expectations"};
-constexpr int kNumClasses = 20;
+static_assert(sizeof kClassNames / sizeof kClassNames[0] == kNumClasses, "one name per kernel class, in the enum's order");
 
 static hipEvent_t prof_event_locked() {
   if (!g_prof_pool.empty()) {
@@ -162,10 +168,11 @@ static hipEvent_t prof_event_locked() {
   return e;
 }
 
-struct ProfileScope {  // RAII around one launch
+struct ProfileScope {  // RAII around the launches of its block: e0 at the opening, e1 and the record at the closing brace
   bool on = false;
+  hipStream_t stream;
   LaunchRecord rec;
-  ProfileScope(int cls, double bytes, hipStream_t stream, bool streaming, double hbm_bytes = -1.0) {
+  ProfileScope(KernelClass cls, double bytes, hipStream_t stream_, bool streaming, double hbm_bytes = -1.0) : stream(stream_) {
     if (g_prof_open.load(std::memory_order_relaxed) == 0) return;
     std::lock_guard<std::mutex> lock(g_prof_mu);
     if (g_profs.find(stream) == g_profs.end()) return;
@@ -183,7 +190,9 @@ struct ProfileScope {  // RAII around one launch
     on = true;
     (void)hipEventRecord(rec.e0, stream);
   }
-  void done(hipStream_t stream) {
+  ProfileScope(const ProfileScope&) = delete;
+  ProfileScope& operator=(const ProfileScope&) = delete;
+  ~ProfileScope() {
     if (!on) return;
     (void)hipEventRecord(rec.e1, stream);
     std::lock_guard<std::mutex> lock(g_prof_mu);
@@ -282,9 +291,10 @@ static int launch_reg(const Plan& p, hipStream_t stream) {
   for (int i = 0; i < NM * NM; ++i) a.u[i] = p.u[i];
   const u64 per_block = (u64)kBlock * ITEMS;
   const u64 blocks = (p.count + per_block - 1) / per_block;
-  ProfileScope prof(NM == 1 ? 0 : (NM == 2 ? 1 : 2), 32.0 * NM * (double)p.count, stream, NT);
-  hipLaunchKernelGGL((k_gate<NM, ITEMS, NT, SWZ>), grid_for(blocks), dim3(kBlock), 0, stream, a);
-  prof.done(stream);
+  {
+    ProfileScope prof(NM == 1 ? kClsGate1 : (NM == 2 ? kClsGate2 : kClsGate4), 32.0 * NM * (double)p.count, stream, NT);
+    hipLaunchKernelGGL((k_gate<NM, ITEMS, NT, SWZ>), grid_for(blocks), dim3(kBlock), 0, stream, a);
+  }
   HIP_TRY(hipGetLastError());
   return QSIM_OK;
 }
@@ -302,9 +312,10 @@ static int launch_shuffle(const Plan& p, hipStream_t stream) {
   for (int i = 0; i < DIM * DIM; ++i) a.u[i] = p.u[i];
   const u64 per_block = (u64)kBlock * ITEMS;
   const u64 blocks = (p.count + per_block - 1) / per_block;
-  ProfileScope prof(NMR == 2 ? 5 : (NSH == 1 ? 3 : 4), 32.0 * NMR * (double)p.count, stream, NT);
-  hipLaunchKernelGGL((k_gate_shuffle<NMR, NSH, ITEMS, NT>), grid_for(blocks), dim3(kBlock), 0, stream, a);
-  prof.done(stream);
+  {
+    ProfileScope prof(NMR == 2 ? kClsShuffle21 : (NSH == 1 ? kClsShuffle11 : kClsShuffle12), 32.0 * NMR * (double)p.count, stream, NT);
+    hipLaunchKernelGGL((k_gate_shuffle<NMR, NSH, ITEMS, NT>), grid_for(blocks), dim3(kBlock), 0, stream, a);
+  }
   HIP_TRY(hipGetLastError());
   return QSIM_OK;
 }

@@ -117,19 +117,19 @@ static int launch_tile(const TileArgs& a, const qsim_chunk* c, hipStream_t strea
   for (int i = 0; i < kTileThreadBits - kTileLow && i < T - kTileLow; ++i) wide = wide || args.lay_in[i] >= 28 || args.lay_out[i] >= 28;
   bool nt = c->span_bytes > tuning().mall_bytes;       // cache policy by state size (gate_plan.h)
   if (tuning().force_nt >= 0) nt = tuning().force_nt != 0;
-  ProfileScope prof(6, alg_bytes, stream, nt, 32.0 * (double)(ntiles << T));
   constexpr int TPW = QSIM_TILES_PER_WG;
   const bool two = per_wg > 1;                             // (tiles_per_workgroup: the rule)
   const unsigned grid = (unsigned)(two ? ntiles / TPW : ntiles);
-  bool part = false;                                       // one destination slab: the PART instantiations (full tiles only)
-  if constexpr (T == kTileBitsMax) {
-    part = args.nfix != 0;
-    if (part && two) launch_k_tile<T, TPW, true>(nt, wide, grid, stream, args);
-    else if (part) launch_k_tile<T, 1, true>(nt, wide, grid, stream, args);
+  const bool part = T == kTileBitsMax && args.nfix != 0;   // one destination slab: the PART instantiations (full tiles only)
+  {
+    ProfileScope prof(kClsTile, alg_bytes, stream, nt, 32.0 * (double)(ntiles << T));
+    if constexpr (T == kTileBitsMax) {
+      if (part && two) launch_k_tile<T, TPW, true>(nt, wide, grid, stream, args);
+      else if (part) launch_k_tile<T, 1, true>(nt, wide, grid, stream, args);
+    }
+    if (!part && two) launch_k_tile<T, TPW, false>(nt, wide, grid, stream, args);
+    else if (!part) launch_k_tile<T, 1, false>(nt, wide, grid, stream, args);
   }
-  if (!part && two) launch_k_tile<T, TPW, false>(nt, wide, grid, stream, args);
-  else if (!part) launch_k_tile<T, 1, false>(nt, wide, grid, stream, args);
-  prof.done(stream);
   HIP_TRY(hipGetLastError());
   if (!part) probe_stamps_dump(args, a.nrec, ntiles, stream);
   return QSIM_OK;

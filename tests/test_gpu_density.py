@@ -113,7 +113,7 @@ def loop_state():
 
 @pytest.mark.parametrize("r", [1, 3, 6])
 def test_a_workgroup_walks_four_tiles(loop_state, r):
-    """The grid-stride loop of k_rdm_small (r = 1, 3) and k_rdm_block (r = 6).  A tile has kRdmTileBits = 11 bits
+    """The grid-stride loop of k_rdm_small (r = 1, 3) and k_rdm_mfma (r = 6).  A tile has kRdmTileBits = 11 bits
     whatever r is, and a launch has at most kRdmMaxWg = 1024 workgroups for every r (csrc/rdm_kernels.h), so a chunk of
     n qubits has 2^(n - 11) tiles and a workgroup walks 2^(n - 11 - 10) of them: n = 23 is the smallest size with at least
     three (four) tiles per workgroup -- n = 22 gives two.  Whoever changes either constant moves n with it.  The qubit

@@ -196,7 +196,7 @@ static void check_values(std::mt19937_64& rng, double* worst, int* cases) {
     }
     const int n = (int)z.size();
     double out_stub = 0.0;
-    CHECK(check_diag_value_args(cs.k, n, z.data(), &out_stub, "check") == QSIM_OK);
+    CHECK(check_diag_args(cs.k, n, z.data(), &out_stub, false, nullptr, "check") == QSIM_OK);
     DiagValueTable d;
     diag_value_table(tb, n, z.data(), &d);
     check_value_table(tb, n, z, d);
@@ -247,7 +247,7 @@ int main() {
       c[(size_t)t] = t % 11 == 3 ? 0.0 : coef(rng);
     }
     double gamma = 0.5;
-    CHECK(check_diag_args(cs.k, cs.n, z.data(), c.data(), &gamma, "check") == QSIM_OK);
+    CHECK(check_diag_args(cs.k, cs.n, z.data(), c.data(), true, &gamma, "check") == QSIM_OK);
     DiagTable d;
     diag_table(tb, cs.n, z.data(), c.data(), &d);
     check_tables(tb, cs.n, z, c, d);
@@ -263,26 +263,26 @@ int main() {
   const double c2[2] = {0.1, 0.2};
   const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
   double g = 0.3;
-  CHECK(check_diag_args(14, 2, z2, c2, &g, "f") == QSIM_OK);
-  CHECK(check_diag_args(14, 2, z2, c2, nullptr, "f") == QSIM_OK);
-  CHECK(check_diag_args(14, 0, nullptr, nullptr, &g, "f") == QSIM_OK);
-  CHECK(check_diag_args(14, -1, z2, c2, &g, "f") == QSIM_ERR_INVALID);
-  CHECK(check_diag_args(14, kDiagMaxTerms + 1, z2, c2, &g, "f") == QSIM_ERR_INVALID);   // (refused before anything is read)
-  CHECK(check_diag_args(14, 2, nullptr, c2, &g, "f") == QSIM_ERR_INVALID);
-  CHECK(check_diag_args(14, 2, z2, nullptr, &g, "f") == QSIM_ERR_INVALID);
+  CHECK(check_diag_args(14, 2, z2, c2, true, &g, "f") == QSIM_OK);
+  CHECK(check_diag_args(14, 2, z2, c2, true, nullptr, "f") == QSIM_OK);
+  CHECK(check_diag_args(14, 0, nullptr, nullptr, true, &g, "f") == QSIM_OK);
+  CHECK(check_diag_args(14, -1, z2, c2, true, &g, "f") == QSIM_ERR_INVALID);
+  CHECK(check_diag_args(14, kDiagMaxTerms + 1, z2, c2, true, &g, "f") == QSIM_ERR_INVALID);   // (refused before anything is read)
+  CHECK(check_diag_args(14, 2, nullptr, c2, true, &g, "f") == QSIM_ERR_INVALID);
+  CHECK(check_diag_args(14, 2, z2, nullptr, true, &g, "f") == QSIM_ERR_INVALID);
   for (double bad : {inf, -inf, nan}) {
     double gb = bad;
     const double cb[2] = {0.1, bad};
-    CHECK(check_diag_args(14, 2, z2, c2, &gb, "f") == QSIM_ERR_INVALID);
-    CHECK(check_diag_args(14, 2, z2, cb, &g, "f") == QSIM_ERR_INVALID);
+    CHECK(check_diag_args(14, 2, z2, c2, true, &gb, "f") == QSIM_ERR_INVALID);
+    CHECK(check_diag_args(14, 2, z2, cb, true, &g, "f") == QSIM_ERR_INVALID);
   }
   for (u64 bad : {1ull << 14, 1ull << 15, 1ull << 63}) {
     const uint64_t zb[2] = {1, bad};
-    CHECK(check_diag_args(14, 2, zb, c2, &g, "f") == QSIM_ERR_NONLOCAL);
+    CHECK(check_diag_args(14, 2, zb, c2, true, &g, "f") == QSIM_ERR_NONLOCAL);
     CHECK(g_err.find("term 1 acts on index bit") != std::string::npos && g_err.find("log2(chunk_size)=14") != std::string::npos);
   }
   const uint64_t top[1] = {1ull << 63};
-  CHECK(check_diag_args(64, 1, top, c2, &g, "f") == QSIM_OK);
+  CHECK(check_diag_args(64, 1, top, c2, true, &g, "f") == QSIM_OK);
 
   // the per-term values: tables, the host model of the pass against the direct sum, the argument checks
   double worst_value = 0.0;
@@ -292,20 +292,20 @@ int main() {
               value_cases, worst_value);
   CHECK(worst_value < 1e-12);                       // the bound of the device tests, on weights of total 1
   double o2[2] = {0.0, 0.0};
-  CHECK(check_diag_value_args(14, 2, z2, o2, "f") == QSIM_OK);
-  CHECK(check_diag_value_args(14, 0, nullptr, nullptr, "f") == QSIM_OK);
-  CHECK(check_diag_value_args(14, -1, z2, o2, "f") == QSIM_ERR_INVALID && g_err == "f: n_terms = -1");
-  CHECK(check_diag_value_args(14, kDiagMaxTerms + 1, z2, o2, "f") == QSIM_ERR_INVALID);   // (refused before anything is read)
+  CHECK(check_diag_args(14, 2, z2, o2, false, nullptr, "f") == QSIM_OK);
+  CHECK(check_diag_args(14, 0, nullptr, nullptr, false, nullptr, "f") == QSIM_OK);
+  CHECK(check_diag_args(14, -1, z2, o2, false, nullptr, "f") == QSIM_ERR_INVALID && g_err == "f: n_terms = -1");
+  CHECK(check_diag_args(14, kDiagMaxTerms + 1, z2, o2, false, nullptr, "f") == QSIM_ERR_INVALID);   // (refused before anything is read)
   CHECK(g_err.find("16385 terms in one call, at most 16384") != std::string::npos);
-  CHECK(check_diag_value_args(14, 2, nullptr, o2, "f") == QSIM_ERR_INVALID && g_err == "f: null argument");
-  CHECK(check_diag_value_args(14, 2, z2, nullptr, "f") == QSIM_ERR_INVALID && g_err == "f: null argument");
-  CHECK(check_diag_value_args(14, -1, nullptr, nullptr, "f") == QSIM_ERR_INVALID && g_err == "f: n_terms = -1");   // n_terms before null
+  CHECK(check_diag_args(14, 2, nullptr, o2, false, nullptr, "f") == QSIM_ERR_INVALID && g_err == "f: null argument");
+  CHECK(check_diag_args(14, 2, z2, nullptr, false, nullptr, "f") == QSIM_ERR_INVALID && g_err == "f: null argument");
+  CHECK(check_diag_args(14, -1, nullptr, nullptr, false, nullptr, "f") == QSIM_ERR_INVALID && g_err == "f: n_terms = -1");   // n_terms before null
   for (u64 bad : {1ull << 14, 1ull << 15, 1ull << 63}) {
     const uint64_t zb[2] = {1, bad};
-    CHECK(check_diag_value_args(14, 2, zb, o2, "f") == QSIM_ERR_NONLOCAL);
+    CHECK(check_diag_args(14, 2, zb, o2, false, nullptr, "f") == QSIM_ERR_NONLOCAL);
     CHECK(g_err.find("term 1 acts on index bit") != std::string::npos && g_err.find("log2(chunk_size)=14") != std::string::npos);
   }
-  CHECK(check_diag_value_args(64, 1, top, o2, "f") == QSIM_OK);
+  CHECK(check_diag_args(64, 1, top, o2, false, nullptr, "f") == QSIM_OK);
   if (g_failed) { std::printf("diag_plan_check: %d checks FAILED\n", g_failed); return 1; }
   std::printf("diag_plan_check: ok\n");
   return 0;
