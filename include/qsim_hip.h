@@ -423,6 +423,15 @@ int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out)
  * Hermitian and its diagonal exactly real.  Only the 2 * 4^r doubles cross to the host; blocks until out is written.
  * A repeated qubit fails with QSIM_ERR_INVALID, a qubit >= log2(chunk) with QSIM_ERR_NONLOCAL. */
 int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, double* out);
+/* The same matrix for 7 <= r <= 12 qubits: out holds 2 * 4^r doubles (row-major, (re, im) interleaved, bit j of an
+ * index <-> qubits[j], unnormalised), 256 KiB at r = 7 and 256 MiB at r = 12.  rho is computed in 64 x 64 blocks on the
+ * fp64 matrix cores: one read-only pass in which every amplitude is read 2^(r - 6) times (mostly from the caches), one
+ * partial block per workgroup, the partial blocks added in a fixed order on the device, no atomics: two calls give the
+ * same bits.  Blocks below the diagonal are computed and mirrored as conjugate transposes, diagonal blocks as a
+ * triangle: out is exactly Hermitian and its diagonal exactly real.  Device workspace of the chunk: up to 130 MiB.
+ * r outside 7..12 (r <= 6: qsim_reduced_density_matrix), a repeated qubit, a null pointer or pending slab pieces fail
+ * with QSIM_ERR_INVALID, a qubit >= log2(chunk) with QSIM_ERR_NONLOCAL.  Blocks until out is written. */
+int qsim_reduced_density_matrix_wide(qsim_chunk* c, int r, const int32_t* qubits, double* out);
 /* Expectation values of Pauli strings, unnormalised: out[t] = <psi|P_t|psi> for t < n_terms.  P_t is two masks of
  * physical local index bits: x_masks[t] = the bits that carry X or Y, z_masks[t] = the bits that carry Z or Y; with
  * ny = popcount(x & z) (Y = i X Z), P|i> = i^ny (-1)^popcount(i & z) |i ^ x> and

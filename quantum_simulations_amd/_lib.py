@@ -116,6 +116,7 @@ SIGNATURES = {
     "qsim_norm2": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "qsim_probabilities": (C.c_int, [_P, C.c_int, _P, _P]),
     "qsim_reduced_density_matrix": (C.c_int, [_P, C.c_int, _P, _P]),
+    "qsim_reduced_density_matrix_wide": (C.c_int, [_P, C.c_int, _P, _P]),
     "qsim_expectation_pauli": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_plan_expectation": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     "qsim_apply_pauli_rotations": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),

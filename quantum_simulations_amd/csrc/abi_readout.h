@@ -295,6 +295,57 @@ int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, dou
   return QSIM_OK;
 }
 
+// Reduced density matrix of 7 to 12 qubits (k_rdm_wide in rdm_kernels.h, the plan in rdm_wide_plan.h): one read-only
+// pass of pairs * S workgroups, one partial 64 x 64 block of 64 KiB per workgroup, k_hist_sum over the S slices in slice
+// order (S = 1: nothing to add), the blocks put together, permuted and mirrored on the host.  In the workspace
+// (ensure_work), at most (pairs * S + pairs) blocks with pairs * S <= kRdmWideMaxWg = 2048: 1539 blocks = 96 MiB at
+// r = 7, 1290 = 81 MiB at r = 8, 1188 = 74 MiB at r = 9, 1224 = 77 MiB at r = 10, 1584 = 99 MiB at r = 11 and
+// 2080 = 130 MiB at r = 12 (S = 1); less for chunks of fewer outer tiles than slices.  2 * 4^r doubles cross to the
+// host: 256 KiB at r = 7, 256 MiB at r = 12.
+int qsim_reduced_density_matrix_wide(qsim_chunk* c, int r, const int32_t* qubits, double* out) {
+  static const char* const what = "qsim_reduced_density_matrix_wide";
+  int rc = check_chunk(c, what);
+  if (rc || (rc = rdm_wide_check_count(r, qubits, out, what)) || (rc = require_no_parts(c, what)) ||
+      (rc = rdm_wide_check_qubits(c->k, r, qubits, what)))
+    return rc;
+  RdmWidePlan p;
+  rdm_wide_plan(c->k, r, qubits, &p);
+  if ((rc = ensure_work(c, p.work_bytes))) return rc;
+  RdmWideArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.t.amp = c->amp;
+  a.t.tb = p.tb;
+  a.t.outer_mask = p.outer_mask;
+  a.t.n_tiles = p.n_outer;
+  for (int b = 0; b < p.tb; ++b) { a.t.phys_bit[b] = p.phys_bit[b]; a.t.lds_pos[b] = p.lds_pos[b]; }
+  for (int b = 0; b < p.nb_bits; ++b) a.blk_phys[b] = p.blk_phys[b];
+  a.nb_bits = p.nb_bits;
+  a.pairs = p.pairs;
+  a.slices = p.slices;
+  a.partial = static_cast<double*>(c->work);
+  const u64 block_doubles = (u64)p.pairs * kRdmWideBlockDoubles;
+  double* dev_out = p.slices > 1 ? a.partial + (u64)p.slices * block_doubles : a.partial;
+  HIP_TRY(hipSetDevice(c->device));
+  const bool nt = c->span_bytes > tuning().mall_bytes;
+  {
+    ProfileScope prof(kClsRdmWide, 16.0 * (double)p.nb * (double)amps(c), c->stream, nt);
+    QSIM_WITH_NT(hipLaunchKernelGGL((k_rdm_wide<NT>), dim3(p.grid), dim3(kBlock), 0, c->stream, a));
+  }
+  HIP_TRY(hipGetLastError());
+  // k_hist_sum spends a workgroup per output double (4.3 M of them add two rows at r = 11) and also adds the tiles of
+  // diagonal partial blocks that no workgroup writes: never-initialised doubles that rdm_wide_assemble does not read
+  if (p.slices > 1 && (rc = sum_rows(c, a.partial, p.slices, (int)block_doubles, dev_out))) return rc;
+  std::vector<double> blocks;
+  try {
+    blocks.resize((size_t)block_doubles);          // up to 130 MiB of host memory at r = 12
+  } catch (const std::bad_alloc&) {
+    return fail(QSIM_ERR_NOMEM, "%s: no host memory for %llu doubles of blocks", what, (u64)block_doubles);
+  }
+  if ((rc = fetch_doubles(c, dev_out, block_doubles, blocks.data()))) return rc;
+  rdm_wide_assemble(p, blocks.data(), out);
+  return QSIM_OK;
+}
+
 // Shot sampling (sample_kernels.h): pass A (block sums), the block prefix and the shots' blocks on the host, the shots
 // grouped by block, pass B (one workgroup per hit block), the indices back in the order of randnums.
 int qsim_sample_block_bits(void) { return kSampleBlockBits; }

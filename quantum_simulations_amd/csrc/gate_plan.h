@@ -144,7 +144,7 @@ static std::atomic<int> g_prof_open{0};
 enum KernelClass {
   kClsGate1, kClsGate2, kClsGate4, kClsShuffle11, kClsShuffle12, kClsShuffle21, kClsTile, kClsDense, kClsHist,
   kClsSampleSums, kClsSampleResolve, kClsRdm, kClsRot, kClsPsum, kClsOvl, kClsLincomb, kClsDiag, kClsDiagApply,
-  kClsDiagOverlap, kClsDiagTermValues, kNumClasses
+  kClsDiagOverlap, kClsDiagTermValues, kClsRdmWide, kNumClasses
 };
 static const char* const kClassNames[] = {
     "k_gate<1> scale (diagonal subset)", "k_gate<2> 2x2 butterfly", "k_gate<4> 4x4 butterfly",
@@ -154,7 +154,7 @@ static const char* const kClassNames[] = {
     "k_rdm reduced density matrix", "k_rot Pauli rotations", "k_psum Pauli-sum action",
     "k_ovl two-state overlaps", "k_lincomb linear combination", "k_diag diagonal Pauli sum",
     "k_diag_apply diagonal Pauli sum applied", "k_diag_overlap diagonal matrix element",
-    "k_diag_term_values per-term Z expectations"};
+    "k_diag_term_values per-term Z expectations", "k_rdm_wide density matrix of 7 to 12 qubits"};
 static_assert(sizeof kClassNames / sizeof kClassNames[0] == kNumClasses, "one name per kernel class, in the enum's order");
 
 static hipEvent_t prof_event_locked() {

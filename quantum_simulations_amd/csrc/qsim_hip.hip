@@ -31,6 +31,7 @@
 #include <list>
 #include <map>
 #include <mutex>
+#include <new>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -66,6 +67,7 @@ typedef unsigned long long u64;
 #include "psum_kernels.h"
 #include "ovl_kernels.h"
 #include "lincomb_kernels.h"
+#include "rdm_wide_plan.h"
 #include "rdm_kernels.h"
 #include "sample_kernels.h"
 #include "comm_rccl.h"

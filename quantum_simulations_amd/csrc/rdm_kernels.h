@@ -1,4 +1,5 @@
-// rdm_kernels.h -- reduced density matrix of r <= 6 qubits (qsim_reduced_density_matrix).
+// rdm_kernels.h -- reduced density matrix of r <= 6 qubits (qsim_reduced_density_matrix) and, at the end of the file,
+// of 7 to 12 qubits in 64 x 64 blocks (k_rdm_wide, qsim_reduced_density_matrix_wide).
 // Part of the single translation unit qsim_hip.hip (included there after expect_kernels.h; not a standalone header).
 //
 //   rho[a][b] = sum over e of psi(e, a) conj(psi(e, b)),   a, b < D = 2^r,  bit j of a <-> index bit qubits[j].
@@ -234,13 +235,7 @@ __global__ __launch_bounds__(kBlock) void k_rdm_block(const RdmArgs a) {
 }
 #endif  // QSIM_PROBES
 
-constexpr int rdm_tile_row(int t) {                  // tile t = I (I + 1) / 2 + J of the lower triangle -> I
-  int i = 0;
-  while ((i + 1) * (i + 2) / 2 <= t) ++i;
-  return i;
-}
-constexpr int rdm_tile_col(int t) { return t - rdm_tile_row(t) * (rdm_tile_row(t) + 1) / 2; }
-
+// (rdm_tile_row / rdm_tile_col, tile t = I (I + 1) / 2 + J of the lower triangle -> I, J: rdm_wide_plan.h)
 // r = 6: wave W owns the units W, W + 4, .. (five of the twenty) over every k-step
 template <int W, int NB>
 __device__ __forceinline__ void rdm_mfma_own_units(const double (&p)[NB], const double (&q)[NB], qs_double4_t* acc) {
@@ -364,6 +359,128 @@ __global__ __launch_bounds__(kBlock) void k_rdm_mfma(const RdmArgs a) {
         const int xr = 16 * I + 4 * wave + g, yc = 16 * J + j;
         if (u & 1) { if (xr > yc) mine[yc * D + xr] = sum; }
         else if (xr >= yc) mine[xr * D + yc] = sum;
+      }
+  }
+}
+
+// ---- r = 7..12 (k_rdm_wide, qsim_reduced_density_matrix_wide; the host side is rdm_wide_plan.h)
+// rho is cut into 64 x 64 blocks: six ROW qubits inside a block, r - 6 BLOCK qubits whose pattern I < NB names it.  A
+// tile is staged exactly as k_rdm_mfma stages its r = 6 tile (64 rows of E words, row stride E + 1), with the block
+// pattern deposited on the block qubits' physical bits.  Workgroup w = s * pairs + p takes the block pair p = (I, J),
+// I >= J, and slice s of the outer tiles (s, s + S, ...): per outer tile it stages the tile of pattern I and, off the
+// diagonal, the one of pattern J in a second LDS region, and accumulates Re = X_I X_J^T, Im = X'_I X_J^T.  Off the
+// diagonal that is 16 MFMA tiles x 2 = 32 units: wave W owns row block W of I against the four column blocks of J, 8
+// units, one LDS word of I and four of J per k-step.  On the diagonal it is the 20 units of the lower triangle, five per
+// wave, as r = 6.  The workgroup writes its partial block (Re [a * 64 + b], Im at 4096 + the same; of a diagonal block
+// only the tiles of the lower triangle) and k_hist_sum adds the slices in slice order.  No atomics.
+static_assert(kRdmWideTileBits == kRdmTileBits && kRdmWideRowBits == kRdmMaxQubits, "the r = 6 staging serves the wide kernel");
+constexpr int kRdmWideRegion = 64 * ((kRdmTile >> 6) + 1);   // words of one staged tile: 64 rows of E + 1
+
+struct RdmWideArgs {
+  RdmArgs t;                       // what rdm_thread_slots and rdm_fetch read: amp, the tile (tb, phys_bit, lds_pos), n_tiles = outer
+                                   // tiles, outer_mask without the block qubits (its partial and swz stay unused: zero)
+  double* partial;                 // [slice][pair][kRdmWideBlockDoubles]
+  int blk_phys[kRdmWideMaxQubits - kRdmWideRowBits];   // block bit -> physical bit
+  int nb_bits;
+  int pairs;
+  unsigned slices;
+};
+
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void k_rdm_wide(const RdmWideArgs a) {
+  constexpr int kWaves = kBlock / 64;
+  static_assert(kWaves == 4, "a wave per row block of 16");
+  __shared__ double2 tile[2 * kRdmWideRegion];
+  double2* const tile_i = tile;
+  double2* const tile_j = tile + kRdmWideRegion;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, g = lane >> 4;
+  const int eb = a.t.tb - 6, E = 1 << eb, tile_amps = 1 << a.t.tb;
+  const int pair = (int)(blockIdx.x % (unsigned)a.pairs);
+  const u64 slice = blockIdx.x / (unsigned)a.pairs;
+  const int I = rdm_tile_row(pair), J = rdm_tile_col(pair);
+  const bool diag = I == J;
+  RdmArgs ai = a.t, aj = a.t;      // the two patterns' tiles: the deposit is disjoint from every other bit of an offset
+  ai.amp += rdm_wide_deposit(a.blk_phys, a.nb_bits, I);
+  aj.amp += rdm_wide_deposit(a.blk_phys, a.nb_bits, J);
+  u64 off[kRdmLoads];
+  int lidx[kRdmLoads];
+  rdm_thread_slots<6, false, true>(a.t, off, lidx);
+  const int steps = E > 1 ? E >> 1 : 1;             // k-steps of two e' (E = 1: the second e' is a zero operand)
+  const bool real_e = (g >> 1) < E;
+  const bool im = g & 1;
+  const int row_off = j * (E + 1) + (real_e ? g >> 1 : 0);
+  qs_double4_t acc[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) acc[u] = qs_double4_t{0.0, 0.0, 0.0, 0.0};
+  double2 nxt_i[kRdmLoads], nxt_j[kRdmLoads];       // the tiles on their way
+  rdm_fetch<NT>(ai, slice, off, nxt_i);
+  if (!diag) rdm_fetch<NT>(aj, slice, off, nxt_j);
+  for (u64 o = slice; o < a.t.n_tiles; o += a.slices) {
+    __syncthreads();                                // (the previous tiles are consumed)
+#pragma unroll
+    for (int it = 0; it < kRdmLoads; ++it)
+      if (tid + it * kBlock < tile_amps) {
+        tile_i[lidx[it]] = nxt_i[it];
+        if (!diag) tile_j[lidx[it]] = nxt_j[it];
+      }
+    __syncthreads();
+    rdm_fetch<NT>(ai, o + a.slices, off, nxt_i);
+    if (!diag) rdm_fetch<NT>(aj, o + a.slices, off, nxt_j);
+    if (diag) {
+      const double2* row = tile_i + row_off;
+      for (int s = 0; s < steps; ++s) {
+        double p[4], q[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const double2 v = row[(16 * b) * (E + 1) + 2 * s];
+          p[b] = real_e ? (im ? v.y : v.x) : 0.0;
+          q[b] = real_e ? (im ? -v.x : v.y) : 0.0;
+        }
+        switch (wave) {
+          case 0: rdm_mfma_own_units<0, 4>(p, q, acc); break;
+          case 1: rdm_mfma_own_units<1, 4>(p, q, acc); break;
+          case 2: rdm_mfma_own_units<2, 4>(p, q, acc); break;
+          default: rdm_mfma_own_units<3, 4>(p, q, acc); break;
+        }
+      }
+    } else {
+      const double2* row_i = tile_i + row_off + (16 * wave) * (E + 1);
+      const double2* row_j = tile_j + row_off;
+      for (int s = 0; s < steps; ++s) {
+        const double2 u = row_i[2 * s];
+        const double pi = real_e ? (im ? u.y : u.x) : 0.0;
+        const double qi = real_e ? (im ? -u.x : u.y) : 0.0;
+        double pj[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const double2 v = row_j[(16 * b) * (E + 1) + 2 * s];
+          pj[b] = real_e ? (im ? v.y : v.x) : 0.0;
+        }
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          acc[2 * b] = __builtin_amdgcn_mfma_f64_16x16x4f64(pi, pj[b], acc[2 * b], 0, 0, 0);
+          acc[2 * b + 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(qi, pj[b], acc[2 * b + 1], 0, 0, 0);
+        }
+      }
+    }
+  }
+  double* mine = a.partial + (slice * (u64)a.pairs + (u64)pair) * kRdmWideBlockDoubles;
+  if (diag) {
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      const int u = wave + kWaves * c;              // the unit numbering of rdm_mfma_own_units
+      const int ti = rdm_tile_row(u >> 1), tj = rdm_tile_col(u >> 1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) mine[(u & 1) * 4096 + (16 * ti + 4 * i + g) * 64 + 16 * tj + j] = acc[c][i];
+    }
+  } else {
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        mine[(16 * wave + 4 * i + g) * 64 + 16 * b + j] = acc[2 * b][i];
+        mine[4096 + (16 * wave + 4 * i + g) * 64 + 16 * b + j] = acc[2 * b + 1][i];
       }
   }
 }

@@ -440,6 +440,19 @@ class DeviceChunk:
         _lib.check(_lib.load().qsim_reduced_density_matrix(self._h, len(q), _lib.ptr(q), _lib.ptr(out)))
         return out
 
+    def reduced_density_matrix_wide(self, qubits) -> np.ndarray:
+        """`reduced_density_matrix` for 7 to 12 PHYSICAL index bits: complex128 of shape (2^r, 2^r), the same index
+        convention, unnormalised (qsim_reduced_density_matrix_wide: 64 x 64 blocks on the fp64 matrix cores in one
+        read-only pass, a fixed summation order -- two calls give the same bits; exactly Hermitian).  The result has
+        16 * 4^r bytes: 256 MiB at 12 qubits."""
+        q = np.ascontiguousarray(qubits, dtype=np.int32).reshape(-1)
+        if not 7 <= len(q) <= 12:
+            raise ValueError(f"reduced_density_matrix_wide: 7 to 12 qubits expected, got {len(q)} "
+                             "(reduced_density_matrix serves 1 to 6)")
+        out = np.empty((1 << len(q), 1 << len(q)), dtype=np.complex128)
+        _lib.check(_lib.load().qsim_reduced_density_matrix_wide(self._h, len(q), _lib.ptr(q), _lib.ptr(out)))
+        return out
+
     def expectation_pauli(self, x_masks, z_masks) -> np.ndarray:
         """<psi|P_t|psi> of Pauli strings given as masks of PHYSICAL index bits of this chunk (x: X or Y, z: Z or Y),
         unnormalised (qsim_expectation_pauli: read-only passes on the device, a fixed summation order -- two calls give
