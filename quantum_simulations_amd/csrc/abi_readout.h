@@ -3,12 +3,15 @@
 // Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
 
 // The r distinct local qubits of a readout call, as the mask *sel: null arguments, the range of r, pending parts, then
-// qubit by qubit (range, locality, repetition).
-static int check_qubit_list(qsim_chunk* c, int r, const int32_t* qubits, const void* out, int max_r, const char* what, u64* sel) {
+// qubit by qubit (range, locality, repetition).  `hint`: what follows the refusal of r (where another call serves it).
+static int check_qubit_list(qsim_chunk* c, int r, const int32_t* qubits, const void* out, int min_r, int max_r, const char* what,
+                            u64* sel = nullptr, const char* hint = "") {
   if (!qubits || !out) return fail(QSIM_ERR_INVALID, "%s: null argument", what);
-  if (r < 1 || r > max_r) return fail(QSIM_ERR_INVALID, "%s: 1 <= r <= %d qubits expected, got %d", what, max_r, r);
+  if (r < min_r || r > max_r) return fail(QSIM_ERR_INVALID, "%s: %d <= r <= %d qubits expected, got %d%s", what, min_r, max_r, r, hint);
   int rc = require_no_parts(c, what);
   if (rc) return rc;
+  u64 mask = 0;
+  if (!sel) sel = &mask;
   *sel = 0;
   for (int i = 0; i < r; ++i) {
     if ((rc = check_local_qubit(c, qubits[i]))) return rc;
@@ -121,7 +124,7 @@ int qsim_probabilities(qsim_chunk* c, int r, const int32_t* qubits, double* out)
   int rc = check_chunk(c, "qsim_probabilities");
   if (rc) return rc;
   u64 sel;
-  if ((rc = check_qubit_list(c, r, qubits, out, 8, "qsim_probabilities", &sel))) return rc;
+  if ((rc = check_qubit_list(c, r, qubits, out, 1, 8, "qsim_probabilities", &sel))) return rc;
   if ((rc = ensure_work(c, sizeof(double) * kHistDoubles))) return rc;
   double* const partial = static_cast<double*>(c->work);
   HIP_TRY(hipSetDevice(c->device));
@@ -217,51 +220,31 @@ int qsim_expectation_pauli(qsim_chunk* c, int n_terms, const uint64_t* x_masks, 
   return pauli_reduce_call(c, pp, 1, kExpMaxWg, launch, out, n_passes);
 }
 
-// Reduced density matrix (rdm_kernels.h): one read-only pass (k_rdm_small for r <= 3, k_rdm_mfma for r = 4..6), one
-// partial matrix of 4^r doubles per workgroup, k_hist_sum over them in workgroup order; the triangle is mirrored on the
-// host.  In the workspace (ensure_work): at most (kRdmMaxWg + 1) * 4^r doubles, that is 32 MiB +
+// Reduced density matrices (rdm_kernels.h, the plans in rdm_plan.h).  Both calls: check, plan, workspace, arguments
+// from the plan, one profiled launch, the row sum (k_hist_sum), the copy to the host, the assembly there.
+// r <= 6: one read-only pass (k_rdm_small for r <= 3, k_rdm_mfma for r = 4..6), one partial matrix of 4^r doubles per
+// workgroup, k_hist_sum over them in workgroup order; the triangle is mirrored on the host (rdm_mirror).  In the
+// workspace (ensure_work): at most (kRdmMaxWg + 1) * 4^r doubles, that is 32 MiB +
 // 32 KiB at r = 6, 8 MiB at r = 5, 2 MiB at r = 4, 512 KiB at r = 3 (and grid + 1 matrices for chunks of fewer tiles).
 int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, double* out) {
   int rc = check_chunk(c, "qsim_reduced_density_matrix");
   if (rc) return rc;
-  u64 sel;
-  if ((rc = check_qubit_list(c, r, qubits, out, kRdmMaxQubits, "qsim_reduced_density_matrix", &sel))) return rc;
-  const int k = c->k, tb = std::min(k, kRdmTileBits), eb = tb - r;
-  const u64 all = (1ull << k) - 1;
-  u64 T = sel | ((1ull << std::min(k, kExpLineBits)) - 1);
-  for (int b = 0; b < k && __builtin_popcountll(T) < tb; ++b) T |= 1ull << b;
+  if ((rc = check_qubit_list(c, r, qubits, out, 1, kRdmRowBits, "qsim_reduced_density_matrix"))) return rc;
+  RdmPlan p;
+  rdm_plan(c->k, r, qubits, &p);
+  if ((rc = ensure_work(c, p.work_bytes))) return rc;
   RdmArgs a;
   std::memset(&a, 0, sizeof a);
-  a.amp = c->amp;
-  a.tb = tb;
-  a.outer_mask = all & ~T;
-  a.n_tiles = 1ull << (k - tb);
-  int n_env = 0;                                    // tile bits outside the qubits: the e' bits, ascending
-  for (int b = 0, j = 0; b < k; ++b) {
-    if (!((T >> b) & 1)) continue;
-    a.phys_bit[j] = b;
-    if ((sel >> b) & 1) {
-      for (int q = 0; q < r; ++q) if (qubits[q] == b) a.lds_pos[j] = eb + q;
-    } else {
-      a.lds_pos[j] = n_env++;
-    }
-    ++j;
-  }
-  // r <= 3: a qubit on a line bit XORs one of the e' bits 0..2 that the remaining line bits leave free (rdm_kernels.h)
-  int free_bit = 0;
-  for (int b = 0; b < std::min(k, kExpLineBits); ++b) free_bit += !((sel >> b) & 1);
-  for (int q = 0; q < r; ++q)
-    if (qubits[q] < kExpLineBits && free_bit < std::min(eb, kExpLineBits)) a.swz[q] = 1 << free_bit++;
-  const int dd = 1 << (2 * r), dim = 1 << r;
-  const unsigned grid = (unsigned)std::min<u64>(a.n_tiles, kRdmMaxWg);
-  if ((rc = ensure_work(c, sizeof(double) * ((u64)grid + 1) * (u64)dd))) return rc;
+  rdm_tile_args(p.t, c, &a);
+  for (int q = 0; q < r; ++q) a.swz[q] = p.swz[q];
   a.partial = static_cast<double*>(c->work);
-  double* dev_out = a.partial + (u64)grid * dd;
+  const int dd = 1 << (2 * r);
+  double* dev_out = a.partial + (u64)p.grid * dd;
   HIP_TRY(hipSetDevice(c->device));
   const bool nt = c->span_bytes > tuning().mall_bytes;
   {
     ProfileScope prof(kClsRdm, 16.0 * (double)amps(c), c->stream, nt);
-#define QSIM_RDM_LAUNCH(KERNEL, R) QSIM_WITH_NT(hipLaunchKernelGGL((KERNEL<R, NT>), dim3(grid), dim3(kBlock), 0, c->stream, a));
+#define QSIM_RDM_LAUNCH(KERNEL, R) QSIM_WITH_NT(hipLaunchKernelGGL((KERNEL<R, NT>), dim3(p.grid), dim3(kBlock), 0, c->stream, a));
 #ifdef QSIM_PROBES
     if (tuning().rdm_form == 1 && r >= 4) {
       if (r == 4) { QSIM_RDM_LAUNCH(k_rdm_block, 4) } else if (r == 5) { QSIM_RDM_LAUNCH(k_rdm_block, 5) } else { QSIM_RDM_LAUNCH(k_rdm_block, 6) }
@@ -278,25 +261,15 @@ int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, dou
 #undef QSIM_RDM_LAUNCH
   }
   HIP_TRY(hipGetLastError());
-  if ((rc = sum_rows(c, a.partial, grid, dd, dev_out))) return rc;
+  if ((rc = sum_rows(c, a.partial, p.grid, dd, dev_out))) return rc;
   std::vector<double> tri((size_t)dd);
   if ((rc = fetch_doubles(c, dev_out, (u64)dd, tri.data()))) return rc;
-  for (int x = 0; x < dim; ++x) {                   // the triangle and its mirror image: exactly Hermitian
-    out[2 * (x * dim + x)] = tri[(size_t)(x * dim + x)];
-    out[2 * (x * dim + x) + 1] = 0.0;
-    for (int y = 0; y < x; ++y) {
-      const double re = tri[(size_t)(x * dim + y)], im = tri[(size_t)(y * dim + x)];
-      out[2 * (x * dim + y)] = re;
-      out[2 * (x * dim + y) + 1] = im;
-      out[2 * (y * dim + x)] = re;
-      out[2 * (y * dim + x) + 1] = -im;
-    }
-  }
+  rdm_mirror(r, tri.data(), out);
   return QSIM_OK;
 }
 
-// Reduced density matrix of 7 to 12 qubits (k_rdm_wide in rdm_kernels.h, the plan in rdm_wide_plan.h): one read-only
-// pass of pairs * S workgroups, one partial 64 x 64 block of 64 KiB per workgroup, k_hist_sum over the S slices in slice
+// r = 7..12 (k_rdm_wide): one read-only pass of pairs * S workgroups, one partial 64 x 64 block of 64 KiB per
+// workgroup, k_hist_sum over the S slices in slice
 // order (S = 1: nothing to add), the blocks put together, permuted and mirrored on the host.  In the workspace
 // (ensure_work), at most (pairs * S + pairs) blocks with pairs * S <= kRdmWideMaxWg = 2048: 1539 blocks = 96 MiB at
 // r = 7, 1290 = 81 MiB at r = 8, 1188 = 74 MiB at r = 9, 1224 = 77 MiB at r = 10, 1584 = 99 MiB at r = 11 and
@@ -305,19 +278,16 @@ int qsim_reduced_density_matrix(qsim_chunk* c, int r, const int32_t* qubits, dou
 int qsim_reduced_density_matrix_wide(qsim_chunk* c, int r, const int32_t* qubits, double* out) {
   static const char* const what = "qsim_reduced_density_matrix_wide";
   int rc = check_chunk(c, what);
-  if (rc || (rc = rdm_wide_check_count(r, qubits, out, what)) || (rc = require_no_parts(c, what)) ||
-      (rc = rdm_wide_check_qubits(c->k, r, qubits, what)))
+  if (rc) return rc;
+  if ((rc = check_qubit_list(c, r, qubits, out, kRdmWideMinQubits, kRdmWideMaxQubits, what, nullptr,
+                             " (qsim_reduced_density_matrix serves r <= 6)")))
     return rc;
   RdmWidePlan p;
   rdm_wide_plan(c->k, r, qubits, &p);
   if ((rc = ensure_work(c, p.work_bytes))) return rc;
   RdmWideArgs a;
   std::memset(&a, 0, sizeof a);
-  a.t.amp = c->amp;
-  a.t.tb = p.tb;
-  a.t.outer_mask = p.outer_mask;
-  a.t.n_tiles = p.n_outer;
-  for (int b = 0; b < p.tb; ++b) { a.t.phys_bit[b] = p.phys_bit[b]; a.t.lds_pos[b] = p.lds_pos[b]; }
+  rdm_tile_args(p.t, c, &a);
   for (int b = 0; b < p.nb_bits; ++b) a.blk_phys[b] = p.blk_phys[b];
   a.nb_bits = p.nb_bits;
   a.pairs = p.pairs;

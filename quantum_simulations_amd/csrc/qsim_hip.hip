@@ -67,7 +67,7 @@ typedef unsigned long long u64;
 #include "psum_kernels.h"
 #include "ovl_kernels.h"
 #include "lincomb_kernels.h"
-#include "rdm_wide_plan.h"
+#include "rdm_plan.h"
 #include "rdm_kernels.h"
 #include "sample_kernels.h"
 #include "comm_rccl.h"

@@ -433,24 +433,21 @@ class DeviceChunk:
         of a and b on index bit qubits[j]; its trace is sum |amp|^2 (qsim_reduced_density_matrix: one read-only pass on
         the device, a fixed summation order -- two calls give the same bits; exactly Hermitian).  `density` has purity,
         entropy and fidelity of the result."""
-        q = np.ascontiguousarray(qubits, dtype=np.int32).reshape(-1)
-        if not 1 <= len(q) <= 6:
-            raise ValueError(f"reduced_density_matrix: 1 to 6 qubits expected, got {len(q)}")
-        out = np.empty((1 << len(q), 1 << len(q)), dtype=np.complex128)
-        _lib.check(_lib.load().qsim_reduced_density_matrix(self._h, len(q), _lib.ptr(q), _lib.ptr(out)))
-        return out
+        return self._density_call("reduced_density_matrix", 1, 6, "", qubits)
 
     def reduced_density_matrix_wide(self, qubits) -> np.ndarray:
         """`reduced_density_matrix` for 7 to 12 PHYSICAL index bits: complex128 of shape (2^r, 2^r), the same index
         convention, unnormalised (qsim_reduced_density_matrix_wide: 64 x 64 blocks on the fp64 matrix cores in one
         read-only pass, a fixed summation order -- two calls give the same bits; exactly Hermitian).  The result has
         16 * 4^r bytes: 256 MiB at 12 qubits."""
+        return self._density_call("reduced_density_matrix_wide", 7, 12, " (reduced_density_matrix serves 1 to 6)", qubits)
+
+    def _density_call(self, name: str, lo: int, hi: int, hint: str, qubits) -> np.ndarray:
         q = np.ascontiguousarray(qubits, dtype=np.int32).reshape(-1)
-        if not 7 <= len(q) <= 12:
-            raise ValueError(f"reduced_density_matrix_wide: 7 to 12 qubits expected, got {len(q)} "
-                             "(reduced_density_matrix serves 1 to 6)")
+        if not lo <= len(q) <= hi:
+            raise ValueError(f"{name}: {lo} to {hi} qubits expected, got {len(q)}{hint}")
         out = np.empty((1 << len(q), 1 << len(q)), dtype=np.complex128)
-        _lib.check(_lib.load().qsim_reduced_density_matrix_wide(self._h, len(q), _lib.ptr(q), _lib.ptr(out)))
+        _lib.check(getattr(_lib.load(), "qsim_" + name)(self._h, len(q), _lib.ptr(q), _lib.ptr(out)))
         return out
 
     def expectation_pauli(self, x_masks, z_masks) -> np.ndarray:

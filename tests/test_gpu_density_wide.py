@@ -158,8 +158,8 @@ def loop_state():
 @pytest.mark.parametrize("r", [7, 8])
 def test_a_workgroup_walks_four_tiles(loop_state, r):
     """A launch has pairs * S workgroups, S the largest power of two with pairs * S <= kRdmWideMaxWg = 2048
-    (csrc/rdm_wide_plan.h): S = 512 for the 3 pairs of r = 7, 128 for the 10 pairs of r = 8.  The outer index has
-    n - 11 - (r - 6) bits (a tile has kRdmWideTileBits = 11, the block qubits are not walked), so a workgroup walks
+    (csrc/rdm_plan.h): S = 512 for the 3 pairs of r = 7, 128 for the 10 pairs of r = 8.  The outer index has
+    n - 11 - (r - 6) bits (a tile has kRdmTileBits = 11, the block qubits are not walked), so a workgroup walks
     2^(n - 5 - r) / S outer tiles: n = 23 (r = 7) and n = 22 (r = 8) are the smallest sizes with at least three (four);
     one qubit less gives two.  Whoever changes either constant moves n with it.  The first set of each r has line bits
     and the top bit."""
@@ -226,10 +226,12 @@ def test_argument_errors():
         rep = np.array([3, 5, 0, 1, 2, 4, 3], dtype=np.int32)
         assert wide(c._h, 7, _lib.ptr(rep), op) == _lib.QSIM_ERR_INVALID
         assert b"repeated qubit 3" in lib.qsim_last_error()
+        assert b"qsim_reduced_density_matrix_wide: repeated qubit 3" in lib.qsim_last_error()
         far = np.array([0, 1, 2, 3, 4, 5, k], dtype=np.int32)
         assert wide(c._h, 7, _lib.ptr(far), op) == _lib.QSIM_ERR_NONLOCAL
         neg = np.array([0, 1, 2, 3, 4, 5, -1], dtype=np.int32)
         assert wide(c._h, 7, _lib.ptr(neg), op) == _lib.QSIM_ERR_INVALID
+        assert b"is negative" in lib.qsim_last_error()
         assert not out.any()                                         # nothing written by a refused call
         assert wide(c._h, 7, qp, op) == _lib.QSIM_OK
         with pytest.raises(ValueError, match="7 to 12"):
