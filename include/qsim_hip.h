@@ -204,6 +204,25 @@ int qsim_plan_peek_pass(int n_local_qubits, int n_total_qubits, int n_ops, const
 int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats, int beam,
                      uint64_t* out_masks, int out_capacity, int32_t* n_passes);
 
+/* qsim_plan_search of ONE op list under many line-qubit triples.  The three qubits on index bits 0..2 belong to every tile,
+ * so they decide how many passes a plan needs; triples[3 t + b] = the logical qubit that goes to index bit b under triple t
+ * (the qubit that was there takes its place; n_triples = 0: every a < b < c, ascending), and the list is searched on the
+ * index bits each triple gives.  n_threads (1..64) host threads share the fewest passes found so far, which ends every
+ * search that can no longer reach it; a search that can is never touched, so the result -- *best_passes and, for every
+ * triple that reaches them, its position in the list (found_index), its qubits (found_triples, 3 each) and its tiles
+ * (found_masks, *best_passes each), sorted by the qubits -- is what qsim_plan_search gives triple by triple, whatever the
+ * thread count.  found_index / found_triples hold an entry per triple searched, found_masks mask_capacity masks (too few:
+ * an error, after *best_passes and *n_found are written).  histogram: NULL or QSIM_PLAN_HISTOGRAM_BINS counts of triples by
+ * pass count -- the last bin but one with everything above it, the last the searches that were ended (counts above the
+ * fewest are exact only with QSIM_TRIPLES_UNBOUNDED).  Host only. */
+#define QSIM_PLAN_HISTOGRAM_BINS 64
+#define QSIM_TRIPLES_UNBOUNDED 1   /* flags: no search is ended early (measurements, checks) */
+#define QSIM_TRIPLES_NEED_BITS 2   /* flags: the bound also counts the tile bits the remaining ops of a state need */
+int qsim_plan_search_triples(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                             int n_triples, const int32_t* triples, int beam, int n_threads, int flags, int32_t* best_passes,
+                             int32_t* n_found, int32_t* found_index, int32_t* found_triples, uint64_t* found_masks,
+                             uint64_t mask_capacity, int32_t* histogram);
+
 /* The op list a plan for repeated execution is made from: X / Y gates pushed into their neighbours (an X is a bit flip of
  * the index: it passes CNOTs and diagonal gates and is absorbed by the next dense 1q gate), CNOTs with an exact H on the
  * target turned into CZ.  Same packed format in and out, same amplitudes up to the rounding of the 2x2 products; fewer ops

@@ -62,6 +62,8 @@ SIGNATURES = {
     "qsim_plan_ops_tiled": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_uint64, _P]),
     "qsim_lower_pass_images": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
     "qsim_plan_search": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P]),
+    "qsim_plan_search_triples": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,
+                                           C.c_uint64, _P]),
     "qsim_rewrite_ops": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     "qsim_rewrite_ops_priced": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int]),
     "qsim_apply_ops_tiled": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P]),

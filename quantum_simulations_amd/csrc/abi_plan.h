@@ -89,19 +89,83 @@ int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int
     return fail(QSIM_ERR_INVALID, "qsim_plan_search: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
   int rc = check_op_list(n_ops, nq, qubits, mats, n_local_qubits, kQubitOfPlan);
   if (rc) return rc;
-  std::vector<FusedOp> ops;
-  classify_ops(n_ops, nq, qubits, mats, &ops);
 #ifdef QSIM_PROBES
   if (beam <= 0) if (const char* e = getenv("QSIM_PLAN_BEAM")) beam = atoi(e);
 #endif
-  std::vector<u64> masks;
-  int passes = 0;
-  rc = plan_search(n_local_qubits, ops, beam, &masks, &passes);
+  // (the one-triple case of qsim_plan_search_triples: the qubits that are on the line bits stay there, nothing bounds it)
+  TripleSearch ts;
+  ts.beam = beam;
+  ts.bounded = false;
+  rc = plan_search_triples(n_local_qubits, n_ops, nq, qubits, mats, {LineTriple{{0, 1, 2}}}, &ts);
   if (rc) return rc;
-  *n_passes = passes;
+  const std::vector<u64>& masks = ts.masks[0];
+  *n_passes = ts.best;
   if (out_masks) {
     if ((int)masks.size() > out_capacity) return fail(QSIM_ERR_INVALID, "qsim_plan_search: output buffer too small");
     for (size_t p = 0; p < masks.size(); ++p) out_masks[p] = masks[p];
+  }
+  return QSIM_OK;
+}
+
+// qsim_plan_search of ONE op list under many line-qubit triples (tile_search.h plan_search_triples): triples[3 t + b] = the
+// logical qubit that goes to index bit b under triple t, the qubit that was there taking its place -- the layout
+// runner/layout_search.py gives a candidate; n_triples = 0: every a < b < c of the n_local_qubits, ascending.  The searches
+// run on n_threads host threads (1..64) and share the fewest passes found so far, which ends every search that can no longer
+// reach it (flags & QSIM_TRIPLES_UNBOUNDED: none is ended; QSIM_TRIPLES_NEED_BITS: the bound also counts the tile bits a
+// state's remaining ops need).  Out: *best_passes, the fewest passes over the triples, and every triple that reaches them,
+// sorted by its three qubits (then by position in the list): found_index (position in the list), found_triples (3 each),
+// found_masks (*best_passes each, on the triple's index bits: what qsim_plan_search returns for the relabelled list); the
+// first two hold one entry per triple searched, found_masks mask_capacity masks -- too few is an error after *best_passes
+// and *n_found are written.  histogram (optional, QSIM_PLAN_HISTOGRAM_BINS counts): triples by pass count, the last bin but
+// one also holding everything above it, the last bin the searches that were ended (exact counts above the fewest exist
+// only unbounded).  The result does not depend on n_threads or on the bound.  Host only, no device.
+int qsim_plan_search_triples(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                             int n_triples, const int32_t* triples, int beam, int n_threads, int flags, int32_t* best_passes,
+                             int32_t* n_found, int32_t* found_index, int32_t* found_triples, uint64_t* found_masks,
+                             uint64_t mask_capacity, int32_t* histogram) {
+  if (!best_passes || !n_found || !found_index || !found_triples || n_triples < 0 || (n_triples && !triples) || (mask_capacity && !found_masks))
+    return fail(QSIM_ERR_INVALID, "qsim_plan_search_triples: bad arguments");
+  if (n_local_qubits < kTileMinChunk || n_local_qubits > kTileMaxQubits)
+    return fail(QSIM_ERR_INVALID, "qsim_plan_search_triples: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
+  int rc = check_op_list(n_ops, nq, qubits, mats, n_local_qubits, kQubitOfPlan);
+  if (rc) return rc;
+  std::vector<LineTriple> list;
+  for (int t = 0; t < n_triples; ++t) {
+    const int32_t* q = triples + 3 * (size_t)t;
+    for (int b = 0; b < 3; ++b)
+      if (q[b] < 0 || q[b] >= n_local_qubits || (b && q[b] == q[0]) || (b == 2 && q[2] == q[1]))
+        return fail(QSIM_ERR_INVALID, "qsim_plan_search_triples: triple %d is not three qubits of the %d", t, n_local_qubits);
+    list.push_back(LineTriple{{q[0], q[1], q[2]}});
+  }
+  if (!n_triples)
+    for (int a = 0; a < n_local_qubits; ++a)
+      for (int b = a + 1; b < n_local_qubits; ++b)
+        for (int c = b + 1; c < n_local_qubits; ++c) list.push_back(LineTriple{{a, b, c}});
+  TripleSearch ts;
+  ts.beam = beam;
+  ts.n_threads = n_threads;
+  ts.bounded = !(flags & QSIM_TRIPLES_UNBOUNDED);
+  ts.need_bits = (flags & QSIM_TRIPLES_NEED_BITS) != 0;
+  rc = plan_search_triples(n_local_qubits, n_ops, nq, qubits, mats, list, &ts);
+  if (rc) return rc;
+  std::vector<int32_t> found;
+  for (size_t t = 0; t < list.size(); ++t) if (ts.passes[t] == ts.best) found.push_back((int32_t)t);
+  std::stable_sort(found.begin(), found.end(), [&](int32_t x, int32_t y) {
+    return std::lexicographical_compare(list[(size_t)x].q, list[(size_t)x].q + 3, list[(size_t)y].q, list[(size_t)y].q + 3);
+  });
+  *best_passes = ts.best;
+  *n_found = (int32_t)found.size();
+  if (histogram) {
+    for (int b = 0; b < QSIM_PLAN_HISTOGRAM_BINS; ++b) histogram[b] = 0;
+    for (int32_t p : ts.passes) ++histogram[p < 0 ? QSIM_PLAN_HISTOGRAM_BINS - 1 : std::min((int)p, QSIM_PLAN_HISTOGRAM_BINS - 2)];
+  }
+  if ((uint64_t)found.size() * (uint64_t)ts.best > mask_capacity)
+    return fail(QSIM_ERR_INVALID, "qsim_plan_search_triples: output buffer too small (%d triples of %d masks)", (int)found.size(), ts.best);
+  for (size_t f = 0; f < found.size(); ++f) {
+    const size_t t = (size_t)found[f];
+    found_index[f] = found[f];
+    for (int b = 0; b < 3; ++b) found_triples[3 * f + b] = list[t].q[b];
+    for (int p = 0; p < ts.best; ++p) found_masks[f * (size_t)ts.best + p] = ts.masks[t][(size_t)p];
   }
   return QSIM_OK;
 }

@@ -178,8 +178,23 @@ struct PassBuilder {
   static u64 mask_of(const std::vector<int>& bits, size_t n) { u64 m = 0; for (size_t i = 0; i < n && i < bits.size(); ++i) m |= 1ull << bits[i]; return m; }
 
   // look-ahead growth of a tile: add the bit that lets the pass hold the most ops, one at a time, up to a whole tile
+  // (grow_memo, the searching builder only: it grows some sixty tiles from one done-set, which end in about nine -- their
+  // paths meet, and from a mask that an earlier path went through the growth is the same, so its end is taken from there.
+  // Exact while the choice of a bit depends on the mask and the done-set alone, that is without the jitter probe; whoever
+  // switches it on clears it whenever `done`, `first`, the scan window or the placement change.)
+  bool grow_memo_on = false;
+  std::vector<std::pair<u64, u64>> grow_memo;  // a mask a growth went through -> where that growth ended
   u64 grow(u64 mask) {
+    const bool memo = grow_memo_on && tune.plan_jitter <= 0;
+    const size_t known = grow_memo.size();
+    std::vector<u64> path;
     while (__builtin_popcountll(mask) < cap) {
+      if (memo) {
+        size_t at = 0;
+        while (at < known && grow_memo[at].first != mask) ++at;
+        if (at < known) { mask = grow_memo[at].second; break; }
+        path.push_back(mask);
+      }
       int pick = -1, pick_count = -(1 << 20);
       for (int b = low; b < k; ++b) {
         if ((mask >> b) & 1) continue;
@@ -189,9 +204,9 @@ struct PassBuilder {
       if (pick < 0) break;
       mask |= 1ull << pick;
     }
+    for (u64 through : path) grow_memo.push_back({through, mask});
     return mask;
   }
-
 
   // first come: an op that still fits claims the bits it needs (`claimed`: in that order); returns the tile
   u64 first_come(u64 forced, std::vector<int>* claimed) const {

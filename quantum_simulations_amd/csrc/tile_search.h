@@ -25,6 +25,16 @@ constexpr int kSearchBeamDefault = 8;
 constexpr size_t kSearchPairSeeds = 10;
 constexpr int kSearchBeamMax = 4096;
 
+// A search that runs next to others (plan_search_triples): `best` is the fewest passes any of them has reached so far.  A
+// search that can no longer reach it stops and says so (`cut`) -- its result would have been thrown away -- and a search
+// that can is not touched, so what survives does not depend on when `best` fell.  need_bits: the beam is also cut where
+// its states cannot finish in time by the tile bits their remaining ops still need (SearchState lower bound, below).
+struct SearchBound {
+  const std::atomic<int>* best;
+  bool need_bits;
+  bool cut;                    // out: more passes than *best; masks and n_passes are the greedy plan's, not a result
+};
+
 // The tiles of the greedy plan (or of the replay of `hint`): the fall-back and the bar the search has to clear.
 static int planned_tiles(int k, const std::vector<FusedOp>& ops, const TileHint* hint, std::vector<u64>* masks, int* n_passes) {
   masks->clear();
@@ -38,7 +48,9 @@ static int planned_tiles(int k, const std::vector<FusedOp>& ops, const TileHint*
 
 // Tiles (high-bit masks, whole tiles) of a plan of `ops_in` on k index bits with as few passes as the search finds: never
 // more than the greedy builder's, whose tiles are returned when the search does not beat them.
-static int plan_search(int k, const std::vector<FusedOp>& ops_in, int beam, std::vector<u64>* masks, int* n_passes) {
+static int plan_search(int k, const std::vector<FusedOp>& ops_in, int beam, std::vector<u64>* masks, int* n_passes,
+                       SearchBound* bound = nullptr) {
+  if (bound) bound->cut = false;
   beam = std::max(1, std::min(beam > 0 ? beam : kSearchBeamDefault, kSearchBeamMax));
   int rc = planned_tiles(k, ops_in, nullptr, masks, n_passes);
   if (rc) return rc;
@@ -47,6 +59,7 @@ static int plan_search(int k, const std::vector<FusedOp>& ops_in, int beam, std:
   PassBuilder pb(k, ops, k);
   if (greedy_passes <= 1 || k - pb.low <= pb.cap) return QSIM_OK;      // (one tile holds every qubit: nothing to choose)
   const size_t n_ops = pb.n_ops;
+  pb.grow_memo_on = true;
 
   std::vector<std::vector<SearchNode>> nodes;    // per depth: the kept states' tiles
   std::vector<SearchState> states(1), children;
@@ -63,6 +76,22 @@ static int plan_search(int k, const std::vector<FusedOp>& ops_in, int beam, std:
   int finished = -1;                             // node of the last depth that finishes the list
   // (a plan of greedy_passes passes is known: the search only looks for shorter ones)
   for (int depth = 0; depth + 1 < greedy_passes && finished < 0 && !states.empty(); ++depth) {
+    // The bound: every state here has run `depth` passes and needs one more at least -- with need_bits, as many as it
+    // takes to bring every tile bit its remaining ops need into a tile, `cap` per pass.  Once that is past `best`, and the
+    // greedy plan is too, nothing this search can still return reaches `best`.
+    if (bound) {
+      int more = 1;
+      if (bound->need_bits) {
+        more = 1 << 20;
+        for (const SearchState& s : states) {
+          u64 needed = 0;
+          for (size_t i = 0; i < n_ops; ++i) if (!s.done[i]) needed |= pb.need[i];
+          more = std::min(more, std::max(1, (__builtin_popcountll(needed) + pb.cap - 1) / pb.cap));
+        }
+      }
+      const int best = bound->best->load(std::memory_order_relaxed);
+      if (greedy_passes > best && depth + more > best) { bound->cut = true; return QSIM_OK; }
+    }
     children.clear();
     for (size_t si = 0; si < states.size(); ++si) {
       const SearchState& s = states[si];
@@ -70,6 +99,7 @@ static int plan_search(int k, const std::vector<FusedOp>& ops_in, int beam, std:
       pb.remaining = s.remaining;
       pb.first = 0;
       pb.begin_pass();
+      pb.grow_memo.clear();                         // (growths are shared between the candidates of ONE state)
       // Candidates: the greedy builder's first-come tile and its look-ahead tiles, grown from EVERY prefix of the
       // first-come bits; then, for every op at the front of the list (nothing undone in front of it on its qubits), the
       // tile grown around its targets -- the tiles a first-come scan never starts from.
@@ -164,6 +194,83 @@ static int plan_search(int k, const std::vector<FusedOp>& ops_in, int beam, std:
   rc = planned_tiles(k, ops_in, &hint, &replay, &replay_passes);
   if (rc) return rc;
   if (replay_passes == (int)found.size() && replay == found) { *masks = found; *n_passes = replay_passes; }
+  return QSIM_OK;
+}
+
+// ---- many line-qubit triples, one bound ------------------------------------------------------------------------------
+// The three qubits on the line bits belong to every tile, so they decide how many passes a plan needs (13 to 15 for the
+// rewritten 28-qubit bench list, 13 on 3.5 % of its 3 276 triples).  plan_search_triples searches one op list under many
+// triples on host threads: every thread relabels the list for its triple (triple_layout: the rule of
+// runner/layout_search.py), runs plan_search with searcher state of its own, and shares one thing with the others, the
+// atomic fewest-passes-so-far that bounds every search (SearchBound).  What comes back -- the fewest passes and, for every
+// triple that reaches them, its tiles -- is what unbounded searches one by one would give, whatever the thread count.
+struct LineTriple { int32_t q[3]; };             // logical qubits that go to index bits 0, 1, 2
+
+// qubit -> index bit with the triple on the line bits: from the identity, the qubit on bit b trades places with t.q[b]
+static void triple_layout(int k, const LineTriple& t, int32_t* lay) {
+  for (int q = 0; q < k; ++q) lay[q] = q;
+  for (int bit = 0; bit < 3; ++bit) {
+    int j = 0;
+    while (lay[j] != bit) ++j;
+    lay[j] = lay[t.q[bit]];
+    lay[t.q[bit]] = bit;
+  }
+}
+
+struct TripleSearch {
+  int beam = 0, n_threads = 1;
+  bool bounded = true, need_bits = false;
+  int best = 0;                                  // out: the fewest passes over the triples
+  std::vector<int32_t> passes;                   // out, per triple: its passes; bounded: -1 where they are more than `best`
+  std::vector<std::vector<u64>> masks;           // out, per triple: its tiles where it reaches `best`, else empty
+};
+
+static int plan_search_triples(int k, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                               const std::vector<LineTriple>& triples, TripleSearch* ts) {
+  const size_t n = triples.size();
+  ts->passes.assign(n, -1);
+  ts->masks.assign(n, std::vector<u64>());
+  ts->best = 0;
+  if (!n) return QSIM_OK;
+  (void)tuning();                                // (initialised before the threads start)
+  std::atomic<int> best{1 << 30}, bad{0};
+  std::atomic<size_t> next{0};
+  auto work = [&]() {                            // (everything a search writes is local to it or its own slot of `ts`)
+    std::vector<FusedOp> ops;
+    std::vector<int32_t> lay((size_t)k);
+    std::vector<u64> found;
+    for (;;) {
+      const size_t t = next.fetch_add(1);
+      if (t >= n) return;
+      triple_layout(k, triples[t], lay.data());
+      ops.clear();
+      for (int i = 0; i < n_ops; ++i) {
+        const int32_t q[2] = {lay[qubits[2 * i]], nq[i] == 2 ? lay[qubits[2 * i + 1]] : -1};
+        FusedOp o;
+        if (classify_op(nq[i], q, mats + 32 * (size_t)i, &o)) ops.push_back(o);
+      }
+      SearchBound bound = {&best, ts->need_bits, false};
+      int passes = 0;
+      if (plan_search(k, ops, ts->beam, &found, &passes, ts->bounded ? &bound : nullptr)) { bad.store(1); continue; }
+      if (bound.cut) continue;
+      ts->passes[t] = passes;
+      ts->masks[t] = found;
+      for (int seen = best.load(); passes < seen && !best.compare_exchange_weak(seen, passes);) {}
+    }
+  };
+  const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, ts->n_threads), std::min<size_t>(n, 64)));
+  std::vector<std::thread> pool;
+  for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+  work();
+  for (std::thread& t : pool) t.join();
+  if (bad.load()) return fail(QSIM_ERR_INVALID, "internal: a line-qubit triple could not be planned");
+  ts->best = best.load();
+  // a search that ended above the final `best` before `best` fell kept its result: dropped here, like the ones cut
+  for (size_t t = 0; t < n; ++t)
+    if (ts->passes[t] != ts->best) {
+      ts->masks[t].clear();
+      if (ts->bounded) ts->passes[t] = -1;
+    }
   return QSIM_OK;
 }
 

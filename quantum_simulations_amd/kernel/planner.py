@@ -1,5 +1,5 @@
 """The host planner of libqsim_hip.so in Python: what the pass builder would do with an op list, without a device
-(csrc/abi_plan.h: qsim_plan_ops, qsim_lower_pass_images, qsim_plan_ops_tiled, qsim_plan_ops_placed, qsim_plan_balance, qsim_plan_search, qsim_plan_count_layouts, qsim_plan_peek_pass,
+(csrc/abi_plan.h: qsim_plan_ops, qsim_lower_pass_images, qsim_plan_ops_tiled, qsim_plan_ops_placed, qsim_plan_balance, qsim_plan_search, qsim_plan_search_triples, qsim_plan_count_layouts, qsim_plan_peek_pass,
 qsim_rewrite_ops_priced; csrc/tile_launch.h: qsim_tiles_per_workgroup; csrc/abi_rotation.h: qsim_plan_pauli_rotations).
 
 A thin binding.  `ops` is [(qubits, U), ...] or the tuple `pack_ops` returns (`device.as_packed`).  Return codes become
@@ -127,6 +127,40 @@ def search_tiles(n: int, ops, beam: int = 0) -> np.ndarray:
     out = np.zeros(len(nq), dtype=np.uint64)
     _lib.check(_lib.load().qsim_plan_search(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), beam, ptr(out), len(out), C.byref(count)))
     return out[:count.value].copy()
+
+
+HISTOGRAM_BINS = 64                # QSIM_PLAN_HISTOGRAM_BINS (include/qsim_hip.h)
+TRIPLES_UNBOUNDED, TRIPLES_NEED_BITS = 1, 2     # QSIM_TRIPLES_* flags
+_MASK_ROOM = 1 << 22               # most masks `search_triples` makes room for (32 MiB)
+
+
+def search_triples(n: int, ops, triples=None, beam: int = 0, threads: int = 1, flags: int = 0) -> dict:
+    """`search_tiles` of ONE op list under many line-qubit triples in one library call (qsim_plan_search_triples):
+    `triples` is an int array of shape (m, 3), row t = the logical qubits that go to index bits 0, 1, 2 (the qubits that
+    were there take their places: the candidate layouts of runner/layout_search.py); None = every a < b < c.  `threads`
+    host threads share the fewest passes found so far, which ends the searches that cannot reach it -- the result is that
+    of `search_tiles` triple by triple, whatever `threads` (TRIPLES_UNBOUNDED in `flags`: no search is ended).  Returns
+    `passes` (the fewest), `index` / `triples` / `masks` (of every triple that reaches them, sorted by its qubits:
+    position in `triples`, the three qubits, one uint64 mask per pass on the triple's index bits), `searched` (triples)
+    and `histogram` ({passes: triples}; the triples above the fewest under the key None unless unbounded)."""
+    nq, qubits, mats = as_packed(ops)
+    tri = None if triples is None else np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+    if tri is not None and not len(tri):
+        raise ValueError("an empty list of triples (None searches them all)")
+    m = n * (n - 1) * (n - 2) // 6 if tri is None else len(tri)
+    best, count = C.c_int32(), C.c_int32()
+    index, found = np.zeros(m, dtype=np.int32), np.zeros((m, 3), dtype=np.int32)
+    room = min(_MASK_ROOM, m * max(1, len(nq)))
+    masks, hist = np.zeros(room, dtype=np.uint64), np.zeros(HISTOGRAM_BINS, dtype=np.int32)
+    _lib.check(_lib.load().qsim_plan_search_triples(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), 0 if tri is None else m, ptr(tri),
+                                                    beam, threads, flags, C.byref(best), C.byref(count), ptr(index), ptr(found),
+                                                    ptr(masks), room, ptr(hist)))
+    k, p = count.value, best.value
+    histogram = {int(b): int(c) for b, c in enumerate(hist[:-1]) if c}
+    if hist[-1]:
+        histogram[None] = int(hist[-1])
+    return {"passes": p, "index": index[:k].copy(), "triples": found[:k].copy(), "masks": masks[:k * p].reshape(k, p).copy(),
+            "searched": m, "histogram": histogram}
 
 
 def rewrite_ops(n: int, ops, stats: dict = None, engine_costs=None) -> list:

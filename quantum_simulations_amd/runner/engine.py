@@ -62,7 +62,7 @@ class SingleGpuEngine(StateCalls):
     rank = 0
     LAYOUT_MIN_QUBITS = 26
     LAYOUT_MIN_REPEATS = 8         # layout = "auto": plans for fewer executions are not worth a second of search
-    LAYOUT_CANDIDATES = 31         # random line-qubit triples (next to the identity) whose plans are searched
+    LAYOUT_CANDIDATES = 63         # random line-qubit triples (next to the identity) searched in one library call (qsim_plan_search_triples)
     LAYOUT_BEAM = 0                # beam width of the pass search (0: the library's default)
     LAYOUT_FINALISTS = 8           # minimum-pass layouts timed on the device (tune_on_device, |0..0> state only)
     ENGINE_PRICING = True          # plans made for many executions price the gate engine (runner/engine_cost.py): rule (d) of the
@@ -147,6 +147,20 @@ class SingleGpuEngine(StateCalls):
         import time
         t0 = time.perf_counter()
         tune = self.tune_on_device and self._zero            # (timing runs overwrite the state: only |0..0> can be put back)
+        plans = self.finalist_plans(batches, self.LAYOUT_FINALISTS if tune else 4)
+        chosen = plans[0]
+        if tune and len(plans) > 1:
+            timed = self._time_on_device(plans)
+            chosen = plans[int(np.argmin(timed))]
+            chosen.layout_info["tuned_on_device_ms"] = [round(t, 3) for t in timed]
+        chosen.layout_info["seconds"] = round(time.perf_counter() - t0, 3)
+        return chosen
+
+    def finalist_plans(self, batches, n_finalists: int) -> list:
+        """The plans of up to n_finalists minimum-pass layouts of the op lists `batches` (`choose_plan_layout` over the
+        identity and LAYOUT_CANDIDATES random line-qubit triples), lowest modelled time first: what `plan_batches` chooses
+        from -- the first, or the one the device runs fastest (tune_on_device)."""
+        from quantum_simulations_amd.kernel.device import pack_ops
         # What the planner is given: the batches with their X / Y gates pushed into neighbouring gates and their H-framed
         # CNOTs turned into CZ (csrc/op_rewrite.h) -- the same amplitudes from fewer ops that need their target inside a
         # tile, hence fewer passes (16 -> 13 on the 28-qubit bench circuit).  `passes_identity` stays what it was:
@@ -166,7 +180,7 @@ class SingleGpuEngine(StateCalls):
         # model prices lower under them (`priced_variant`).
         priced = None if costs is None else [planner.rewrite_ops(self.n, ops, None, costs) for ops in own_batches]
         own_identity = int(_count_passes(self.n, own_batches, np.arange(self.n, dtype=np.int32)[None, :], 1)[0])
-        finalists = choose_plan_layout(self.n, batches, self.LAYOUT_CANDIDATES, n_finalists=self.LAYOUT_FINALISTS if tune else 4,
+        finalists = choose_plan_layout(self.n, batches, self.LAYOUT_CANDIDATES, n_finalists=n_finalists,
                                        all_finalists=True, beam=self.LAYOUT_BEAM, engine_costs=costs, priced_batches=priced)
 
         def build(l2p, masks, info):
@@ -178,14 +192,7 @@ class SingleGpuEngine(StateCalls):
             plan.model_ms = info["model_ms"]
             plan.layout_info = dict(info, passes_identity=own_identity, rewrite=dict(rewrite))
             return plan
-        plans = [build(*f) for f in finalists]
-        chosen = plans[0]
-        if tune and len(plans) > 1:
-            timed = self._time_on_device(plans)
-            chosen = plans[int(np.argmin(timed))]
-            chosen.layout_info["tuned_on_device_ms"] = [round(t, 3) for t in timed]
-        chosen.layout_info["seconds"] = round(time.perf_counter() - t0, 3)
-        return chosen
+        return [build(*f) for f in finalists]
 
     def _time_on_device(self, plans) -> list:
         """Milliseconds of every plan on the device.  The cost model cannot rank the minimum-pass layouts (measured: 3 %

@@ -33,31 +33,80 @@ def _count_passes(n: int, batches, layouts: np.ndarray, threads: int) -> np.ndar
     return total
 
 
+PLACED_PER_FINALIST = 4            # minimum-pass layouts placed and priced for every finalist `choose_plan_layout` returns
+
+
+def candidate_triples(n: int, n_candidates: int, seed: int) -> np.ndarray:
+    """The line-qubit triples `choose_plan_layout` searches, int32 (n_candidates + 1, 3): the identity (0, 1, 2), then
+    n_candidates random ones from one generator, so a longer list starts with the shorter one."""
+    rng = np.random.default_rng(seed)
+    rows = [[0, 1, 2]] + [[int(x) for x in rng.choice(n, size=3, replace=False)] for _ in range(n_candidates)]
+    return np.array(rows, dtype=np.int32)
+
+
+def triple_layouts(n: int, triples) -> np.ndarray:
+    """Rows qubit -> index bit, one per triple: from the identity, the qubit on line bit b trades places with triple[b]
+    (the rule of the library's triple_layout, csrc/tile_search.h)."""
+    layouts = np.tile(np.arange(n, dtype=np.int32), (len(triples), 1))
+    for row, triple in zip(layouts, triples):
+        for bit, q in enumerate(int(x) for x in triple):
+            j = int(np.flatnonzero(row == bit)[0])          # the qubit on `bit` trades places with q
+            row[j], row[q] = row[q], bit
+    return layouts
+
+
+def _search_triples(n: int, batches, triples, layouts, beam: int, threads: int) -> tuple:
+    """(fewest passes of the batches over the triples, {candidate: tile masks per batch} of the candidates that reach them,
+    {passes: candidates}).  One op list of two ops or more: one library call, whose searches share their bound
+    (`planner.search_triples`; candidates above the fewest are counted under ">fewest").  Several: the sum over the lists
+    decides, which no bound on one of them knows, so every list is searched to the end under every triple."""
+    none = np.zeros(0, dtype=np.uint64)
+    short = sum(len(ops) for ops in batches if len(ops) < 2)                    # (a single op is not searched: one pass)
+    long = [i for i, ops in enumerate(batches) if len(ops) >= 2]
+    if len(long) == 1:
+        res = planner.search_triples(n, batches[long[0]], triples, beam, threads)
+        best = short + res["passes"]
+        found = {int(t): [ms if i == long[0] else none for i in range(len(batches))] for t, ms in zip(res["index"], res["masks"])}
+        by_passes = {best: len(found)}
+        if len(found) < len(triples):
+            by_passes[f">{best}"] = len(triples) - len(found)
+        return best, found, by_passes
+    from concurrent.futures import ThreadPoolExecutor
+
+    def search(lay):                                        # (the library call releases the interpreter lock)
+        return [planner.search_tiles(n, [([int(lay[q]) for q in qs], U) for qs, U in ops], beam) if len(ops) >= 2 else none
+                for ops in batches]
+    with ThreadPoolExecutor(threads) as pool:
+        every = list(pool.map(search, layouts))
+    counts = np.array([short + sum(len(ms) for ms in f) for f in every], dtype=np.int64)
+    best = int(counts.min())
+    return (best, {int(t): every[t] for t in np.flatnonzero(counts == best)},
+            {int(c): int((counts == c).sum()) for c in np.unique(counts)})
+
+
 def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 20260504, n_finalists: int = 4,
                        all_finalists: bool = False, beam: int = 0, engine_costs=None, priced_batches=None):
     """(l2p, tile masks per batch on the chosen index bits, info) for the op lists `batches` (logical qubits).  The three
     qubits on the line bits belong to every tile, so they decide how many passes a plan needs; which index bits the OTHER
     qubits live on does not (a relabelling of the bits >= 3 maps every valid pass sequence to a valid one).  So: for the
-    identity and `n_candidates` random line-qubit triples the library's searching pass builder (qsim_plan_search, beam
-    width `beam`, 0 = its default) plans the batches, in parallel on the host; the triples that need the fewest passes
-    are kept and their other qubits placed by the tile-cost model (runner/tile_layout.py).  Host only.  all_finalists: the
-    list of up to n_finalists minimum-pass layouts, best model cost first (the engine may time them on the device).
+    identity and `n_candidates` random line-qubit triples (`candidate_triples`) the library's searching pass builder
+    plans the batches in one call (qsim_plan_search_triples, beam width `beam`, 0 = its default; `_search_triples`); of
+    the triples that need the fewest passes the first PLACED_PER_FINALIST * n_finalists are kept and their other qubits
+    placed by the tile-cost model (runner/tile_layout.py), on a thread pool.  Host only.  all_finalists: the list of the
+    n_finalists of those that the model prices lowest, best first (the engine may time them on the device).  info:
+    `candidates_by_passes` ({passes: candidates}; one op list: the fewest and ">fewest"), `minimum_pass_triples` (how many
+    candidates reach the fewest passes), `line_qubits` (the layout's triple).
     engine_costs (the table of runner/engine_cost.py; None: pricing off): a pass is priced max(memory model of its tile,
     engine time of its records); `priced_variant` then chooses between `batches` and `priced_batches` (the same lists
     under rule (d) of the rewrite, optional) and places the ops that need no tile: info gains `planned` (the op lists to
     run, on their index bits), `placed` (their placements, per batch) and the modelled split (`model_split_ms`), and the
     finalists rank by that total instead of the memory model alone."""
     import os
-    from concurrent.futures import ThreadPoolExecutor
 
     from quantum_simulations_amd import _lib
     from quantum_simulations_amd.runner import tile_layout
-    rng = np.random.default_rng(seed)
-    layouts = np.tile(np.arange(n, dtype=np.int32), (n_candidates + 1, 1))
-    for row in layouts[1:]:
-        for bit, q in enumerate(int(x) for x in rng.choice(n, size=3, replace=False)):
-            j = int(np.flatnonzero(row == bit)[0])          # the qubit on `bit` trades places with q
-            row[j], row[q] = row[q], bit
+    triples = candidate_triples(n, n_candidates, seed)
+    layouts = triple_layouts(n, triples)
     try:
         threads = len(os.sched_getaffinity(0))
     except AttributeError:
@@ -67,24 +116,27 @@ def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 2026
 
     def relabelled(lay):
         return [[([int(lay[q]) for q in qs], U) for qs, U in ops] for ops in batches]
-
-    def search(lay):                                        # (the library call releases the interpreter lock)
-        none = np.zeros(0, dtype=np.uint64)
-        return [planner.search_tiles(n, ops, beam) if len(ops) >= 2 else none for ops in relabelled(lay)]
-    with ThreadPoolExecutor(threads) as pool:
-        found = list(pool.map(search, layouts))
-    short = sum(len(ops) for ops in batches if len(ops) < 2)                    # (a single op is not searched: one pass)
-    counts = np.array([short + sum(len(ms) for ms in f) for f in found], dtype=np.int64)
-    best = int(counts.min())
-    finalists = [int(i) for i in np.flatnonzero(counts == best)][:max(1, n_finalists)]   # (the identity first when it ties)
+    best, found, by_passes = _search_triples(n, batches, triples, layouts, beam, threads)
+    # The layouts to place and price: minimum-pass candidates in candidate order (the identity first when it ties),
+    # PLACED_PER_FINALIST of them for every finalist asked for.  The finalists are the lowest of those by the model, which
+    # separates good from bad layouts though it does not rank the best.
+    tried = sorted(found)[:PLACED_PER_FINALIST * max(1, n_finalists)]
     greedy_identity = int(_count_passes(n, batches, layouts[:1], 1)[0])
-    out = []
-    for f in finalists:
+    from concurrent.futures import ThreadPoolExecutor
+    tile_layout.model_for(n)                                    # (loaded before the threads ask for it)
+
+    def annealed(job):                                          # (the library call releases the interpreter lock)
+        f, s = job
+        return tile_layout.choose_layout([[b for b in range(tile_layout.LOW, n) if (int(m) >> b) & 1] for ms in found[f] for m in ms], n, seed=s)
+    with ThreadPoolExecutor(threads) as pool:                   # eight annealing runs per layout, all layouts at once
+        runs = list(pool.map(annealed, [(f, s) for f in tried for s in range(1, 9)]))
+
+    def placed(at):
+        f = tried[at]
         first = [int(x) for x in layouts[f]]
         moved = relabelled(first)
         masks = found[f]
-        tiles = [[b for b in range(tile_layout.LOW, n) if (int(m) >> b) & 1] for ms in masks for m in ms]
-        second, cost0, cost1 = min((tile_layout.choose_layout(tiles, n, seed=s) for s in range(1, 9)), key=lambda r: r[2])
+        second, cost0, cost1 = min(runs[8 * at:8 * at + 8], key=lambda r: r[2])
         final_masks = [np.array([sum(1 << second[b] for b in range(n) if (int(m) >> b) & 1) for m in ms], dtype=np.uint64) for ms in masks]
         # The pass count does not depend on the placement, but the records of a pass are written in the order of its tile
         # bits, and a pass at the edge of its record budget may hold one op fewer in another order: a placement that would
@@ -95,8 +147,8 @@ def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 2026
             second, final_masks, cost1 = list(range(n)), [np.array(ms, dtype=np.uint64) for ms in masks], cost0
         l2p = [second[first[q]] for q in range(n)]
         info = {"passes_identity": greedy_identity, "passes_chosen": best, "candidates": n_candidates + 1,
-                "candidates_by_passes": {int(c): int((counts == c).sum()) for c in np.unique(counts)},
-                "passes_identity_searched": int(counts[0]), "beam": int(beam) if beam > 0 else "default",
+                "candidates_by_passes": dict(by_passes), "minimum_pass_triples": len(found), "line_qubits": [int(q) for q in triples[f]],
+                "beam": int(beam) if beam > 0 else "default",
                 "model_ms": (round(cost0, 3), round(cost1, 3))}
         if engine_costs is not None:
             def on_bits(lists):
@@ -105,9 +157,11 @@ def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 2026
             info["planned"], info["placed"], info["model_split_ms"] = priced_variant(
                 n, on_bits(batches), None if priced_batches is None else on_bits(priced_batches), final_masks, engine_costs)
             info["passes_chosen"] = info["model_split_ms"]["pass_count"]       # (a list under rule (d) may finish a pass early)
-        out.append((l2p, final_masks, info))
+        return l2p, final_masks, info
+    with ThreadPoolExecutor(threads) as pool:
+        out = list(pool.map(placed, range(len(tried))))
     out.sort(key=lambda r: r[2]["model_split_ms"]["passes"] if "model_split_ms" in r[2] else r[2]["model_ms"][1])
-    return out if all_finalists else out[0]
+    return out[:max(1, n_finalists)] if all_finalists else out[0]
 
 
 def pass_memory_us(n: int, masks) -> np.ndarray:
