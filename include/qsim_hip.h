@@ -112,6 +112,29 @@ int qsim_apply_ops_tiled(qsim_chunk* c, int n_ops, const int32_t* nq, const int3
 int qsim_apply_ops_placed(qsim_chunk* c, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
                           int n_tiles, const uint64_t* tile_masks, const int32_t* earliest_pass);
 
+/* ---- cyclic plans: an op list L executed again and again, planned across the boundary of two executions ----------------
+ * With L = A.B as a product (a head A, a tail B: qsim_plan_search_cycle finds them) R executions are A (B.A)^(R-1) B, and
+ * B.A may need a fused pass fewer than L.  A cycle holds the prepared passes of the three lists (each with its named tiles
+ * and optional placement, as for qsim_apply_ops_placed; chunks of n_local_qubits qubits).  qsim_apply_cycle is one
+ * execution of L: the chunk runs A when nothing of this cycle is deferred on it (whatever else is deferred is run first)
+ * and B.A when this cycle's tail is, and either way is left with B DEFERRED.  Nobody sees a state with the tail missing:
+ * every call that takes a chunk runs a deferred tail before it touches or hands out the amplitudes (qsim_sync included:
+ * a timed region that ends in it has paid for its tail; not qsim_time_begin / qsim_time_end, which touch none); calls that overwrite the whole state (qsim_init_zero,
+ * qsim_init_random, an upload of every amplitude, qsim_destroy) drop it.  A view shares its parent's tail.  Chunks that
+ * own their memory only (qsim_create).  A cycle may be destroyed while its tail is deferred somewhere. */
+typedef struct qsim_cycle qsim_cycle;
+typedef struct {
+  int32_t n_ops; const int32_t* nq; const int32_t* qubits; const double* mats;
+  int32_t n_tiles; const uint64_t* tile_masks;   /* the high tile bits of its passes (n_tiles = 0: the pass builder's own) */
+  const int32_t* earliest_pass;                  /* NULL, or n_ops entries (qsim_apply_ops_placed) */
+} qsim_cycle_list;
+/* n_passes: NULL, or three counts (head, steady, tail) */
+int qsim_cycle_create(int n_local_qubits, const qsim_cycle_list* head, const qsim_cycle_list* steady, const qsim_cycle_list* tail,
+                      int32_t* n_passes, qsim_cycle** out);
+int qsim_cycle_destroy(qsim_cycle* cycle);
+/* qsim_last_pass_count then reports the passes this call launched for the cycle (head or steady) */
+int qsim_apply_cycle(qsim_chunk* c, const qsim_cycle* cycle);
+
 /* ---- op list with a re-layout fused into its ends ------------------------------------------------
  * Multi-GPU re-layouts (the staging SWAP lists of wenbo_engine/circuit/staging.py:136-152, merged into one
  * all-to-all) move the shard through exchange buffers in SLAB layout (qsim_pack_all below).  Instead of one extra
@@ -222,6 +245,17 @@ int qsim_plan_search_triples(int n_local_qubits, int n_ops, const int32_t* nq, c
                              int n_triples, const int32_t* triples, int beam, int n_threads, int flags, int32_t* best_passes,
                              int32_t* n_found, int32_t* found_index, int32_t* found_triples, uint64_t* found_masks,
                              uint64_t mask_capacity, int32_t* histogram);
+/* Cyclic plans of ONE op list L under the line-qubit triples given (n_triples >= 1): L.L is searched under every triple, cut
+ * at the first pass that holds an op of its second copy into a head A and a tail B, and A, B.A and B are searched under the
+ * same triple (qsim_cycle_create runs them).  plain_passes: NULL, or the passes of L under every triple where the caller
+ * knows them.  Out, for the triples with the fewest steady passes among those with fewer steady passes than plain ones:
+ * found_index, found_triples (3 each), found_passes (4 each: plain, head, steady, tail), found_tail (n_ops bytes each: 1 =
+ * the op belongs to B; A and B keep the order of L), found_masks (head, steady, tail tiles one after the other, on the
+ * triple's index bits; mask_capacity masks fit).  *n_found = 0: no cycle, a result and no error.  Independent of n_threads. */
+int qsim_plan_search_cycle(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                           int n_triples, const int32_t* triples, const int32_t* plain_passes, int beam, int n_threads,
+                           int32_t* n_found, int32_t* found_index, int32_t* found_triples, int32_t* found_passes,
+                           uint8_t* found_tail, uint64_t* found_masks, uint64_t mask_capacity);
 
 /* The op list a plan for repeated execution is made from: X / Y gates pushed into their neighbours (an X is a bit flip of
  * the index: it passes CNOTs and diagonal gates and is absorbed by the next dense 1q gate), CNOTs with an exact H on the
@@ -632,6 +666,7 @@ int qsim_max_abs_err_closed_form_perm(qsim_chunk* c, int kind, int n_total_qubit
  * selected with sel_mask / sel_value -- an amplitude-level check of states too large to gather (n = 33: 128 GiB). */
 int qsim_fingerprint(qsim_chunk* c, int n_total_qubits, uint64_t base_index, const int32_t* log_to_phys, uint64_t seed,
                      uint64_t sel_mask, uint64_t sel_value, double out[2]);
+/* (neither call touches an amplitude: the deferred tail of a cyclic plan is NOT run by them -- qsim_sync does that) */
 int qsim_time_begin(qsim_chunk* c);                        /* hipEventRecord on stream  */
 int qsim_time_end(qsim_chunk* c, float* elapsed_ms);       /* record + synchronize      */
 

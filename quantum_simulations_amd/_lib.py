@@ -64,6 +64,11 @@ SIGNATURES = {
     "qsim_plan_search": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P]),
     "qsim_plan_search_triples": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,
                                            C.c_uint64, _P]),
+    "qsim_plan_search_cycle": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P,
+                                         C.c_uint64]),
+    "qsim_cycle_create": (C.c_int, [C.c_int, _P, _P, _P, _P, C.POINTER(_P)]),
+    "qsim_cycle_destroy": (C.c_int, [_P]),
+    "qsim_apply_cycle": (C.c_int, [_P, _P]),
     "qsim_rewrite_ops": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     "qsim_rewrite_ops_priced": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int]),
     "qsim_apply_ops_tiled": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P]),
@@ -162,6 +167,12 @@ class OpsIo(C.Structure):
 class OpList(C.Structure):
     """qsim_op_list (include/qsim_hip.h)"""
     _fields_ = [("n_ops", C.c_int32), ("nq", C.c_void_p), ("qubits", C.c_void_p), ("mats", C.c_void_p)]
+
+
+class CycleList(C.Structure):
+    """qsim_cycle_list (include/qsim_hip.h): one op list of a cyclic plan with its named tiles and optional placement"""
+    _fields_ = [("n_ops", C.c_int32), ("nq", C.c_void_p), ("qubits", C.c_void_p), ("mats", C.c_void_p),
+                ("n_tiles", C.c_int32), ("tile_masks", C.c_void_p), ("earliest_pass", C.c_void_p)]
 
 
 class ProfileEntry(C.Structure):

@@ -65,6 +65,7 @@ int qsim_destroy(qsim_chunk* c) {
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->work) (void)hipFree(c->work);
   delete c->split;
+  delete c->deferred;                // (a deferred tail is dropped: nobody can look at the state again)
   if (c->owns_memory && c->amp) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(c->amp);
@@ -74,10 +75,11 @@ int qsim_destroy(qsim_chunk* c) {
 }
 
 int qsim_n_local_qubits(const qsim_chunk* c) { return c ? c->k : -1; }
-void* qsim_device_ptr(const qsim_chunk* c) { return c ? (void*)c->amp : nullptr; }
+// (whoever holds the pointer reads the amplitudes behind the library's back: a deferred tail runs first)
+void* qsim_device_ptr(const qsim_chunk* c) { return c && settle(const_cast<qsim_chunk*>(c)) == QSIM_OK ? (void*)c->amp : nullptr; }
 
 int qsim_init_zero(qsim_chunk* c, int set_amp0) {
-  int rc = check_chunk(c, "qsim_init_zero");
+  int rc = check_chunk_overwritten(c, "qsim_init_zero");
   if (rc) return rc;
   drop_pending(c);
   HIP_TRY(hipSetDevice(c->device));
@@ -87,7 +89,7 @@ int qsim_init_zero(qsim_chunk* c, int set_amp0) {
 }
 
 int qsim_init_random(qsim_chunk* c, uint64_t seed) {
-  int rc = check_chunk(c, "qsim_init_random");
+  int rc = check_chunk_overwritten(c, "qsim_init_random");
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
   hipLaunchKernelGGL(k_fill_random, dim3(stream_grid(amps(c))), dim3(kBlock), 0, c->stream, c->amp, amps(c), (u64)seed);
@@ -101,7 +103,9 @@ int qsim_init_random(qsim_chunk* c, uint64_t seed) {
 }
 
 static int transfer(qsim_chunk* c, double* re_im, uint64_t offset_amps, uint64_t count, bool download) {
-  int rc = check_chunk(c, download ? "qsim_download" : "qsim_upload");
+  // (an upload of every amplitude overwrites the state: a deferred tail is dropped, not run)
+  const bool whole = !download && c && re_im && offset_amps == 0 && count == amps(c);
+  int rc = whole ? check_chunk_overwritten(c, "qsim_upload") : check_chunk(c, download ? "qsim_download" : "qsim_upload");
   if (rc) return rc;
   if (!re_im && count) return fail(QSIM_ERR_INVALID, "host buffer is null");
   if (offset_amps > amps(c) || count > amps(c) - offset_amps)
@@ -122,7 +126,8 @@ int qsim_download(qsim_chunk* c, double* re_im, uint64_t offset_amps, uint64_t c
 
 // complex64 transfers (the reference's chunk-file dtype): converted on the device through a staging buffer
 static int c64_transfer(qsim_chunk* c, float* host, uint64_t offset_amps, uint64_t count, bool download, const char* what) {
-  int rc = check_chunk(c, what);
+  const bool whole = !download && c && host && offset_amps == 0 && count == amps(c);
+  int rc = whole ? check_chunk_overwritten(c, what) : check_chunk(c, what);
   if (rc) return rc;
   if (!host && count) return fail(QSIM_ERR_INVALID, "%s: host buffer is null", what);
   if (offset_amps > amps(c) || count > amps(c) - offset_amps)
@@ -194,6 +199,7 @@ int qsim_copy_variant(qsim_chunk* dst, const qsim_chunk* src, int variant) {
   return QSIM_OK;
 }
 
+// (check_chunk runs a deferred tail first: after the call the chunk holds the finished state)
 int qsim_sync(qsim_chunk* c) {
   int rc = check_chunk(c, "qsim_sync");
   if (rc) return rc;
@@ -212,15 +218,17 @@ static int ensure_events(qsim_chunk* c) {
   return QSIM_OK;
 }
 
+// (the two timing calls touch no amplitude and run no deferred tail: events around executions of a cyclic plan time its
+// steady passes; a region that is to pay for the tail ends in qsim_sync)
 int qsim_time_begin(qsim_chunk* c) {
-  int rc = check_chunk(c, "qsim_time_begin");
+  int rc = check_chunk_unsettled(c, "qsim_time_begin");
   if (rc || (rc = ensure_events(c))) return rc;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   return QSIM_OK;
 }
 
 int qsim_time_end(qsim_chunk* c, float* elapsed_ms) {
-  int rc = check_chunk(c, "qsim_time_end");
+  int rc = check_chunk_unsettled(c, "qsim_time_end");
   if (rc || (rc = ensure_events(c))) return rc;
   if (!elapsed_ms) return fail(QSIM_ERR_INVALID, "elapsed_ms is null");
   HIP_TRY(hipEventRecord(c->ev1, c->stream));

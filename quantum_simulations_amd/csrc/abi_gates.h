@@ -114,6 +114,84 @@ int qsim_apply_ops_placed(qsim_chunk* c, int n_ops, const int32_t* nq, const int
   return apply_ops_fused(c, n_ops, nq, qubits, mats, n_tiles, tile_masks, "qsim_apply_ops_placed", earliest_pass);
 }
 
+}  // extern "C"
+
+// ---- cyclic plans (include/qsim_hip.h; the search: tile_search.h plan_search_cycle; the deferred tail: abi_pending.h) ------
+struct qsim_cycle {
+  int k;
+  u64 id;                            // what a chunk's deferred tail names its cycle by
+  PassList head, steady, tail;
+};
+static std::atomic<u64> g_cycle_ids{0};
+
+// the passes of one list of a cycle, prepared like the cached passes of qsim_apply_ops_placed (no buffers yet)
+static int cycle_passes(int k, const qsim_cycle_list* l, const char* part, PassList* out) {
+  if (!l || l->n_ops < 1 || l->n_tiles < 0 || (l->n_tiles && !l->tile_masks))
+    return fail(QSIM_ERR_INVALID, "qsim_cycle_create: bad %s list", part);
+  int rc = check_op_list(l->n_ops, l->nq, l->qubits, l->mats, k, kQubitOfPlan);
+  if (rc) return rc;
+  std::vector<FusedOp> ops;
+  std::vector<int32_t> origin, placed;
+  classify_ops(l->n_ops, l->nq, l->qubits, l->mats, &ops, &origin);
+  if (ops.empty()) return fail(QSIM_ERR_INVALID, "qsim_cycle_create: the %s list holds identities only", part);
+  TileHint hint = {l->tile_masks, l->n_tiles};
+  if (l->earliest_pass && l->n_tiles) {
+    for (int32_t i : origin) placed.push_back(l->earliest_pass[i]);
+    hint.earliest = placed.data();
+  }
+  auto made = std::make_shared<std::vector<CachedPass>>();
+  int passes = 0;
+  rc = plan_fused(k, ops, &passes, [&](TileArgs& a, int T, double alg_bytes, bool, bool) {
+    lower_unit_real(&a);
+    made->push_back(CachedPass{a, T, alg_bytes});
+    return (int)QSIM_OK;
+  }, l->n_tiles ? &hint : nullptr);
+  *out = made;
+  return rc;
+}
+
+extern "C" {
+int qsim_cycle_create(int n_local_qubits, const qsim_cycle_list* head, const qsim_cycle_list* steady, const qsim_cycle_list* tail,
+                      int32_t* n_passes, qsim_cycle** out) {
+  if (!out) return fail(QSIM_ERR_INVALID, "qsim_cycle_create: out is null");
+  if (n_local_qubits < kTileMinChunk || n_local_qubits > kTileMaxQubits)
+    return fail(QSIM_ERR_INVALID, "qsim_cycle_create: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
+  std::unique_ptr<qsim_cycle> cy(new qsim_cycle());
+  cy->k = n_local_qubits;
+  cy->id = ++g_cycle_ids;
+  int rc = cycle_passes(n_local_qubits, head, "head", &cy->head);
+  if (rc || (rc = cycle_passes(n_local_qubits, steady, "steady", &cy->steady)) || (rc = cycle_passes(n_local_qubits, tail, "tail", &cy->tail)))
+    return rc;
+  if (n_passes) { n_passes[0] = (int32_t)cy->head->size(); n_passes[1] = (int32_t)cy->steady->size(); n_passes[2] = (int32_t)cy->tail->size(); }
+  *out = cy.release();
+  return QSIM_OK;
+}
+
+int qsim_cycle_destroy(qsim_cycle* cycle) {
+  delete cycle;                      // (a tail deferred on a chunk keeps its passes alive)
+  return QSIM_OK;
+}
+
+int qsim_apply_cycle(qsim_chunk* c, const qsim_cycle* cycle) {
+  int rc = check_chunk_unsettled(c, "qsim_apply_cycle");
+  if (rc) return rc;
+  if (!cycle) return fail(QSIM_ERR_INVALID, "qsim_apply_cycle: null cycle");
+  if (cycle->k != c->k) return fail(QSIM_ERR_INVALID, "qsim_apply_cycle: a cycle for %d qubits on a chunk of %d", cycle->k, c->k);
+  if (!c->owns_memory || c->parent)
+    return fail(QSIM_ERR_INVALID, "qsim_apply_cycle: the chunk must own its memory (views and wrapped pointers cannot defer a tail)");
+  if ((rc = require_no_parts(c, "qsim_apply_cycle"))) return rc;
+  const bool steady = c->deferred && c->deferred->passes && c->deferred->id == cycle->id;
+  if (!steady && (rc = settle(c))) return rc;
+  if (!c->deferred) c->deferred = new DeferredTail();
+  c->deferred->passes.reset();       // (steady: the tail runs now, as the front of B.A)
+  const std::vector<CachedPass>& run = steady ? *cycle->steady : *cycle->head;
+  if ((rc = launch_passes(c, run))) return rc;
+  c->deferred->id = cycle->id;
+  c->deferred->passes = cycle->tail;
+  c->last_passes = (int)run.size();
+  return QSIM_OK;
+}
+
 // Dense k-qubit block: new[idx with the block's bits = out] = sum_in M[out][in] old[idx with the block's bits = in], pattern
 // bit i <-> qubits[i] -- v3's `_apply_combined_matrix` (parallel_gate_applicator.py:315-385) for a genuinely dense 2^k x 2^k
 // matrix (its tensor-product blocks are cheaper as butterflies inside a fused pass: qsim_apply_ops).  1 <= k <= 6.

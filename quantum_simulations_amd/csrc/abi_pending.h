@@ -1,5 +1,6 @@
-// abi_pending.h -- what a split qsim_apply_ops_io call (abi_relayout.h) leaves pending on a chunk: the piece cut and the one
-// record behind qsim_chunk::split; every topic of the C ABI asks whether pieces are pending.
+// abi_pending.h -- what calls leave pending on a chunk.  A split qsim_apply_ops_io call (abi_relayout.h): the piece cut and the
+// one record behind qsim_chunk::split; every topic of the C ABI asks whether pieces are pending.  A cyclic plan
+// (abi_gates.h qsim_apply_cycle): the deferred tail behind qsim_chunk::deferred, and settle(), which runs it.
 // Part of the single translation unit qsim_hip.hip (included there, in order; not a standalone header).
 
 // The top nb index bits of a k-bit index that are none of the m slab bits, ascending (the piece bits of the split form).
@@ -90,6 +91,48 @@ static int require_no_parts(const qsim_chunk* c, const char* what) {
   if (parts_pending(c)) return fail(QSIM_ERR_INVALID, "%s: slab pieces of a split qsim_apply_ops_io call are pending on this chunk", what);
   return QSIM_OK;
 }
+// ---- the deferred tail of a cyclic plan (abi_gates.h qsim_apply_cycle) -------------------------------------------------------
+// One execution of a cyclic plan leaves the passes of its tail B unlaunched on the chunk, so that the next execution can run
+// them together with its head (B.A, a pass fewer than A and B apart).  The record shares the prepared passes with the cycle
+// object (which may be destroyed first) and names it by `id`, never by address.  settle() launches what is deferred and
+// clears the record: check_chunk calls it for every exported call (qsim_core.h), for a view also on the chunks it is a
+// window of.  Only chunks that own their memory carry a tail, so no two chunks with one hide the same amplitudes.
+typedef std::shared_ptr<const std::vector<CachedPass>> PassList;
+struct DeferredTail {
+  u64 id = 0;                        // the cycle whose tail it is
+  PassList passes;                   // null: nothing deferred
+};
+static int launch_passes(qsim_chunk* c, const std::vector<CachedPass>& passes) {
+  HIP_TRY(hipSetDevice(c->device));
+  for (size_t p = 0; p < passes.size(); ++p) {
+    CachedPass pass = passes[p];     // (buffers and launch geometry go into a copy: the images are shared)
+    prepare_planned(c, pass.a, pass.T, p == 0, p + 1 == passes.size(), nullptr);
+    const int rc = dispatch_planned(c, pass.a, pass.T, pass.alg_bytes);
+    if (rc) return rc;
+  }
+  return QSIM_OK;
+}
+static void drop_deferred(qsim_chunk* c) {
+  if (c->deferred) c->deferred->passes.reset();
+}
+static int settle(qsim_chunk* c) {
+  for (; c; c = c->parent) {
+    if (!c->deferred || !c->deferred->passes) continue;
+    const PassList tail = std::move(c->deferred->passes);
+    c->deferred->passes.reset();
+    const int rc = launch_passes(c, *tail);
+    if (rc) return rc;
+  }
+  return QSIM_OK;
+}
+// check_chunk of a call that overwrites every amplitude of the chunk: its own tail is dropped, not run
+static int check_chunk_overwritten(qsim_chunk* c, const char* what) {
+  const int rc = check_chunk_unsettled(c, what);
+  if (rc) return rc;
+  drop_deferred(c);
+  return settle(c->parent);
+}
+
 // An error between arming and disarming leaves nothing pending on the chunk.
 struct PendingGuard {
   qsim_chunk* c;

@@ -93,7 +93,7 @@ int qsim_plan_search(int n_local_qubits, int n_ops, const int32_t* nq, const int
   if (beam <= 0) if (const char* e = getenv("QSIM_PLAN_BEAM")) beam = atoi(e);
 #endif
   // (the one-triple case of qsim_plan_search_triples: the qubits that are on the line bits stay there, nothing bounds it)
-  TripleSearch ts;
+  ListSearch ts;
   ts.beam = beam;
   ts.bounded = false;
   rc = plan_search_triples(n_local_qubits, n_ops, nq, qubits, mats, {LineTriple{{0, 1, 2}}}, &ts);
@@ -141,7 +141,7 @@ int qsim_plan_search_triples(int n_local_qubits, int n_ops, const int32_t* nq, c
     for (int a = 0; a < n_local_qubits; ++a)
       for (int b = a + 1; b < n_local_qubits; ++b)
         for (int c = b + 1; c < n_local_qubits; ++c) list.push_back(LineTriple{{a, b, c}});
-  TripleSearch ts;
+  ListSearch ts;
   ts.beam = beam;
   ts.n_threads = n_threads;
   ts.bounded = !(flags & QSIM_TRIPLES_UNBOUNDED);
@@ -166,6 +166,61 @@ int qsim_plan_search_triples(int n_local_qubits, int n_ops, const int32_t* nq, c
     found_index[f] = found[f];
     for (int b = 0; b < 3; ++b) found_triples[3 * f + b] = list[t].q[b];
     for (int p = 0; p < ts.best; ++p) found_masks[f * (size_t)ts.best + p] = ts.masks[t][(size_t)p];
+  }
+  return QSIM_OK;
+}
+
+// Cyclic plans of ONE op list L that is executed again and again (tile_search.h plan_search_cycle), under the line-qubit
+// triples given (as in qsim_plan_search_triples; at least one): L.L is searched under every triple, its tiles replayed for
+// the pass of every op, L cut at the first pass that holds an op of the second copy into a head A and a tail B, and A, B.A
+// and B searched under the same triple.  R executions are then A (B.A)^(R-1) B.  plain_passes (optional, one per triple):
+// the passes of L under the triple where the caller has searched it already; NULL: searched here.  Out, for the triples with
+// the fewest steady passes among those whose steady passes are fewer than the plain ones, in list order: found_index,
+// found_triples (3 each), found_passes (4 each: plain, head, steady, tail), found_tail (n_ops bytes each: 1 = the op belongs to
+// B; inside A and B the ops keep the order of L), found_masks (head, steady and tail tiles one after the other, on the
+// triple's index bits) -- one entry per triple given has room for everything but the masks, mask_capacity says how many of
+// those fit; too few is an error after *n_found is written.  *n_found = 0, no cycle, is a result and not an error.  The result does
+// not depend on n_threads.  Host only, no device.
+int qsim_plan_search_cycle(int n_local_qubits, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                           int n_triples, const int32_t* triples, const int32_t* plain_passes, int beam, int n_threads,
+                           int32_t* n_found, int32_t* found_index, int32_t* found_triples, int32_t* found_passes,
+                           uint8_t* found_tail, uint64_t* found_masks, uint64_t mask_capacity) {
+  if (!n_found || !found_index || !found_triples || !found_passes || !found_tail || n_triples < 1 || !triples || (mask_capacity && !found_masks))
+    return fail(QSIM_ERR_INVALID, "qsim_plan_search_cycle: bad arguments");
+  if (n_local_qubits < kTileMinChunk || n_local_qubits > kTileMaxQubits)
+    return fail(QSIM_ERR_INVALID, "qsim_plan_search_cycle: fused passes need %d..%d local qubits", kTileMinChunk, kTileMaxQubits);
+  int rc = check_op_list(n_ops, nq, qubits, mats, n_local_qubits, kQubitOfPlan);
+  if (rc) return rc;
+  std::vector<LineTriple> list;
+  for (int t = 0; t < n_triples; ++t) {
+    const int32_t* q = triples + 3 * (size_t)t;
+    for (int b = 0; b < 3; ++b)
+      if (q[b] < 0 || q[b] >= n_local_qubits || (b && q[b] == q[0]) || (b == 2 && q[2] == q[1]))
+        return fail(QSIM_ERR_INVALID, "qsim_plan_search_cycle: triple %d is not three qubits of the %d", t, n_local_qubits);
+    list.push_back(LineTriple{{q[0], q[1], q[2]}});
+  }
+  std::vector<CyclePlan> cycles;
+  if ((rc = plan_search_cycle(n_local_qubits, n_ops, nq, qubits, mats, list, plain_passes, beam, n_threads, &cycles))) return rc;
+  int fewest = 1 << 30;
+  for (const CyclePlan& c : cycles) if (c.found) fewest = std::min(fewest, (int)c.passes[1]);
+  int found = 0;
+  uint64_t used = 0;
+  for (const CyclePlan& c : cycles) if (c.found && c.passes[1] == fewest) { ++found; used += c.masks[0].size() + c.masks[1].size() + c.masks[2].size(); }
+  *n_found = found;
+  if (used > mask_capacity) return fail(QSIM_ERR_INVALID, "qsim_plan_search_cycle: output buffer too small (%llu masks)", (u64)used);
+  size_t f = 0;
+  for (size_t t = 0; t < cycles.size(); ++t) {
+    const CyclePlan& c = cycles[t];
+    if (!c.found || c.passes[1] != fewest) continue;
+    found_index[f] = (int32_t)t;
+    for (int b = 0; b < 3; ++b) found_triples[3 * f + b] = list[t].q[b];
+    found_passes[4 * f] = c.plain;
+    for (int w = 0; w < 3; ++w) {
+      found_passes[4 * f + 1 + w] = c.passes[w];
+      for (u64 m : c.masks[w]) *found_masks++ = m;
+    }
+    std::memcpy(found_tail + f * (size_t)n_ops, c.tail.data(), (size_t)n_ops);
+    ++f;
   }
   return QSIM_OK;
 }

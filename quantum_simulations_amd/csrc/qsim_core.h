@@ -38,6 +38,7 @@ struct qsim_chunk {
   u64 span_bytes;        // size of the allocation the chunk lives in (cache-policy choice)
   struct SplitIo* split;         // split form of qsim_apply_ops_io: what is planned but not yet launched (abi_pending.h; owned)
   bool own_in_chunk;     // the last qsim_apply_ops_io stored its own slab into THIS chunk (dst_own == src, one pass): qsim_apply_ops_io_own_slab
+  struct DeferredTail* deferred;  // the tail of a cyclic plan that has not run yet (abi_pending.h settle; owned)
 };
 
 static const int kMaxDevices = 16;
@@ -67,9 +68,17 @@ static inline u64 amps(const qsim_chunk* c) { return 1ull << c->k; }
   } while (0)
 
 // ------------------------------------------------------------------ argument checks
-static int check_chunk(const qsim_chunk* c, const char* what) {
+// Every exported call that takes a chunk comes through check_chunk before it touches or hands out the amplitudes, so this
+// is where the deferred tail of a cyclic plan runs (abi_pending.h settle): nobody sees a state with the tail missing.
+// Calls that overwrite the whole state drop the tail instead (check_chunk_overwritten), qsim_apply_cycle looks at it itself.
+static int settle(qsim_chunk* c);
+static int check_chunk_unsettled(const qsim_chunk* c, const char* what) {
   if (!c || !c->amp) return fail(QSIM_ERR_INVALID, "%s: null chunk", what);
   return QSIM_OK;
+}
+static int check_chunk(const qsim_chunk* c, const char* what) {
+  const int rc = check_chunk_unsettled(c, what);
+  return rc ? rc : settle(const_cast<qsim_chunk*>(c));
 }
 
 static int check_local_qubit(const qsim_chunk* c, int q) {

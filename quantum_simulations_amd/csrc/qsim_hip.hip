@@ -30,6 +30,7 @@
 #include <atomic>
 #include <list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>

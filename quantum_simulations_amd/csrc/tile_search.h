@@ -217,17 +217,17 @@ static void triple_layout(int k, const LineTriple& t, int32_t* lay) {
   }
 }
 
-struct TripleSearch {
+struct ListSearch {
   int beam = 0, n_threads = 1;
   bool bounded = true, need_bits = false;
-  int best = 0;                                  // out: the fewest passes over the triples
-  std::vector<int32_t> passes;                   // out, per triple: its passes; bounded: -1 where they are more than `best`
-  std::vector<std::vector<u64>> masks;           // out, per triple: its tiles where it reaches `best`, else empty
+  int best = 0;                                  // out: the fewest passes over the lists
+  std::vector<int32_t> passes;                   // out, per list: its passes; bounded: -1 where they are more than `best`
+  std::vector<std::vector<u64>> masks;           // out, per list: its tiles where it reaches `best` (unbounded: always), else empty
 };
 
-static int plan_search_triples(int k, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
-                               const std::vector<LineTriple>& triples, TripleSearch* ts) {
-  const size_t n = triples.size();
+// plan_search of n op lists on host threads under one bound: make(t, &ops) writes list t (called on the thread that searches it)
+template <class Make>
+static int plan_search_lists(int k, size_t n, Make&& make, ListSearch* ts) {
   ts->passes.assign(n, -1);
   ts->masks.assign(n, std::vector<u64>());
   ts->best = 0;
@@ -237,18 +237,12 @@ static int plan_search_triples(int k, int n_ops, const int32_t* nq, const int32_
   std::atomic<size_t> next{0};
   auto work = [&]() {                            // (everything a search writes is local to it or its own slot of `ts`)
     std::vector<FusedOp> ops;
-    std::vector<int32_t> lay((size_t)k);
     std::vector<u64> found;
     for (;;) {
       const size_t t = next.fetch_add(1);
       if (t >= n) return;
-      triple_layout(k, triples[t], lay.data());
       ops.clear();
-      for (int i = 0; i < n_ops; ++i) {
-        const int32_t q[2] = {lay[qubits[2 * i]], nq[i] == 2 ? lay[qubits[2 * i + 1]] : -1};
-        FusedOp o;
-        if (classify_op(nq[i], q, mats + 32 * (size_t)i, &o)) ops.push_back(o);
-      }
+      make(t, &ops);
       SearchBound bound = {&best, ts->need_bits, false};
       int passes = 0;
       if (plan_search(k, ops, ts->beam, &found, &passes, ts->bounded ? &bound : nullptr)) { bad.store(1); continue; }
@@ -263,14 +257,168 @@ static int plan_search_triples(int k, int n_ops, const int32_t* nq, const int32_
   for (int t = 1; t < nt; ++t) pool.emplace_back(work);
   work();
   for (std::thread& t : pool) t.join();
-  if (bad.load()) return fail(QSIM_ERR_INVALID, "internal: a line-qubit triple could not be planned");
+  if (bad.load()) return fail(QSIM_ERR_INVALID, "internal: an op list of a pass search could not be planned");
   ts->best = best.load();
   // a search that ended above the final `best` before `best` fell kept its result: dropped here, like the ones cut
-  for (size_t t = 0; t < n; ++t)
+  for (size_t t = 0; t < n && ts->bounded; ++t)
     if (ts->passes[t] != ts->best) {
       ts->masks[t].clear();
-      if (ts->bounded) ts->passes[t] = -1;
+      ts->passes[t] = -1;
     }
+  return QSIM_OK;
+}
+
+// the caller's op list on the index bits of a triple; origin (optional): classified op -> index in the caller's list
+static void triple_ops(int k, const LineTriple& t, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                       std::vector<FusedOp>* ops, std::vector<int32_t>* origin = nullptr) {
+  std::vector<int32_t> lay((size_t)k);
+  triple_layout(k, t, lay.data());
+  for (int i = 0; i < n_ops; ++i) {
+    const int32_t q[2] = {lay[qubits[2 * i]], nq[i] == 2 ? lay[qubits[2 * i + 1]] : -1};
+    FusedOp o;
+    if (!classify_op(nq[i], q, mats + 32 * (size_t)i, &o)) continue;
+    ops->push_back(o);
+    if (origin) origin->push_back(i);
+  }
+}
+
+static int plan_search_triples(int k, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                               const std::vector<LineTriple>& triples, ListSearch* ts) {
+  const bool bounded = ts->bounded;
+  const int rc = plan_search_lists(k, triples.size(), [&](size_t t, std::vector<FusedOp>* ops) {
+    triple_ops(k, triples[t], n_ops, nq, qubits, mats, ops);
+  }, ts);
+  // (unbounded: the passes of every triple stay, the tiles only of those that reach the fewest)
+  for (size_t t = 0; t < triples.size() && !rc && !bounded; ++t) if (ts->passes[t] != ts->best) ts->masks[t].clear();
+  return rc;
+}
+
+// ---- cyclic plans: the tail of one execution runs with the head of the next ---------------------------------------------
+// A list L that is executed again and again is planned as if every execution stood alone, and the last passes of a plan
+// carry little (10 and 36 records against 50-60 on the bench list).  Planned across the boundary the ops are the same:
+// with L = A.B as a product (A: a head, B: a tail, each in list order) R executions are A (B.A)^(R-1) B, and B.A may need a
+// pass fewer than L (12 instead of 13 for the 28-qubit bench list).  Where to cut comes from a plan, not from the list (no
+// list suffix of 6 to 320 ops got below 13): L.L is searched, its tiles are replayed through holds / emit / account for the
+// pass of every op -- what emit really wrote, not what holds promised -- and the cut is the first pass that holds an op of
+// the second copy: A = the first-copy ops of the passes before it, B = the rest.  That is a product of L: the passes are an
+// order of L.L in which no op overtakes one it does not commute with, so nothing of B comes before something of A it does
+// not commute with.  A, B.A and B are then searched under the same triple; plan_search checks the replay of each.
+struct CyclePlan {
+  bool found = false;
+  int32_t plain = 0;                             // passes of L under the triple
+  int32_t passes[3] = {0, 0, 0};                 // head A, steady B.A, tail B
+  std::vector<uint8_t> tail;                     // per op of the CALLER's list: 1 = in B (identities: 0)
+  std::vector<u64> masks[3];
+};
+
+// the pass of every op of `ops` under the named tiles (first come, no placement); false: they do not finish the list
+static bool replay_pass_of(int k, const std::vector<FusedOp>& ops, const std::vector<u64>& masks, std::vector<int32_t>* pass_of) {
+  pass_of->assign(ops.size(), -1);
+  PassBuilder pb(k, ops, k);
+  std::vector<size_t> members;
+  std::vector<char> emitted;
+  std::vector<TileGroup> groups;
+  for (size_t p = 0; p < masks.size() && pb.remaining; ++p) {
+    pb.begin_pass();
+    pb.pass_no = (int)p;
+    members.clear();
+    pb.holds(masks[p], &members);
+    if (members.empty()) return false;
+    pb.emit(members, pb.filled(pb.bits_of(masks[p])), &groups, &emitted);
+    for (size_t mi = 0; mi < members.size(); ++mi) if (emitted[mi]) (*pass_of)[members[mi]] = (int32_t)p;
+    size_t n_emitted = 0;
+    pb.account(members, emitted, &n_emitted);
+    if (!n_emitted) return false;
+  }
+  return pb.remaining == 0;
+}
+
+// plain_passes (optional, per triple): the passes of L under the triple where the caller knows them; else L is searched too
+static int plan_search_cycle(int k, int n_ops, const int32_t* nq, const int32_t* qubits, const double* mats,
+                             const std::vector<LineTriple>& triples, const int32_t* plain_passes, int beam, int n_threads,
+                             std::vector<CyclePlan>* out) {
+  const size_t n = triples.size();
+  out->assign(n, CyclePlan());
+  std::vector<std::vector<FusedOp>> L(n);
+  std::vector<std::vector<int32_t>> origin(n);
+  for (size_t t = 0; t < n; ++t) triple_ops(k, triples[t], n_ops, nq, qubits, mats, &L[t], &origin[t]);
+  ListSearch ls;
+  ls.beam = beam;
+  ls.n_threads = n_threads;
+  // 1. L.L under every triple, one bound
+  int rc = plan_search_lists(k, n, [&](size_t t, std::vector<FusedOp>* ops) {
+    *ops = L[t];
+    ops->insert(ops->end(), L[t].begin(), L[t].end());
+  }, &ls);
+  if (rc) return rc;
+  // 2. the cut, and B.A under the triples that have one (one bound again: the fewest steady passes)
+  std::vector<size_t> cyc;                       // triples with a cut
+  std::vector<std::vector<FusedOp>> part[3];     // A, B.A, B per entry of cyc
+  std::vector<int32_t> pass_of;
+  for (size_t t = 0; t < n; ++t) {
+    if (ls.passes[t] < 0) continue;
+    std::vector<FusedOp> twice = L[t];
+    twice.insert(twice.end(), L[t].begin(), L[t].end());
+    const std::vector<FusedOp> planned = planned_ops(twice);
+    const size_t m = L[t].size();
+    if (planned.size() != twice.size() || !replay_pass_of(k, planned, ls.masks[t], &pass_of)) continue;   // (the probe build's commuting fusion renumbers the ops)
+    int32_t cut = 1 << 30;
+    for (size_t i = m; i < 2 * m; ++i) cut = std::min(cut, pass_of[i]);
+    std::vector<FusedOp> A, B;
+    CyclePlan& c = (*out)[t];
+    c.tail.assign((size_t)n_ops, 0);
+    for (size_t i = 0; i < m; ++i) {
+      (pass_of[i] < cut ? A : B).push_back(L[t][i]);
+      c.tail[(size_t)origin[t][i]] = pass_of[i] >= cut;
+    }
+    if (A.empty() || B.empty()) continue;          // no cycle under this triple
+    std::vector<FusedOp> BA = B;
+    BA.insert(BA.end(), A.begin(), A.end());
+    cyc.push_back(t);
+    part[0].push_back(A); part[1].push_back(BA); part[2].push_back(B);
+  }
+  if (cyc.empty()) return QSIM_OK;
+  ListSearch steady;
+  steady.beam = beam;
+  steady.n_threads = n_threads;
+  rc = plan_search_lists(k, cyc.size(), [&](size_t j, std::vector<FusedOp>* ops) { *ops = part[1][j]; }, &steady);
+  if (rc) return rc;
+  std::vector<size_t> kept;                      // entries of cyc at the fewest steady passes
+  for (size_t j = 0; j < cyc.size(); ++j) if (steady.passes[j] == steady.best) kept.push_back(j);
+  // 3. A and B of those (and L where the caller does not know its passes), each to the end
+  ListSearch ends;
+  ends.beam = beam;
+  ends.n_threads = n_threads;
+  ends.bounded = false;
+  const size_t per = plain_passes ? 2 : 3;
+  rc = plan_search_lists(k, per * kept.size(), [&](size_t j, std::vector<FusedOp>* ops) {
+    const size_t which = j % per, at = kept[j / per];
+    *ops = which == 0 ? part[0][at] : which == 1 ? part[2][at] : L[cyc[at]];
+  }, &ends);
+  if (rc) return rc;
+  for (size_t i = 0; i < kept.size(); ++i) {
+    const size_t t = cyc[kept[i]];
+    CyclePlan& c = (*out)[t];
+    c.plain = plain_passes ? plain_passes[t] : ends.passes[per * i + 2];
+    c.passes[0] = ends.passes[per * i];
+    c.passes[1] = steady.passes[kept[i]];
+    c.passes[2] = ends.passes[per * i + 1];
+    c.masks[0] = ends.masks[per * i];
+    c.masks[1] = steady.masks[kept[i]];
+    c.masks[2] = ends.masks[per * i + 1];
+    // a cycle counts when its steady passes are fewer than the plain plan's and the three tile lists replay through the
+    // hint path into exactly the passes counted
+    bool ok = c.passes[1] < c.plain;
+    for (int w = 0; w < 3 && ok; ++w) {
+      std::vector<u64> replay;
+      int replay_passes = 0;
+      const std::vector<uint64_t> named(c.masks[w].begin(), c.masks[w].end());
+      const TileHint hint = {named.data(), (int)named.size()};
+      if ((rc = planned_tiles(k, part[w][kept[i]], &hint, &replay, &replay_passes))) return rc;
+      ok = replay_passes == c.passes[w] && (int)named.size() == c.passes[w];
+    }
+    c.found = ok;
+  }
   return QSIM_OK;
 }
 

@@ -196,8 +196,16 @@ class DeviceChunk:
                                              _lib.ptr(place)))
         return lib.qsim_last_pass_count(self._h)
 
+    def apply_cycle(self, cycle: "Cycle") -> int:
+        """One execution of the op list a cyclic plan was made from (qsim_apply_cycle): the head passes, or the steady
+        ones when this cycle's tail is deferred on the chunk; the tail stays deferred until anything looks at the state
+        (every other call on the chunk runs it first, `sync` included).  Returns the passes launched."""
+        lib = _lib.load()
+        _lib.check(lib.qsim_apply_cycle(self._h, cycle._h))
+        return lib.qsim_last_pass_count(self._h)
+
     def apply_ops(self, ops, fused: bool = True) -> int:
-        """One pass: every (qubits, U) of `ops` in one C call.  `fused` groups them into LDS-tile
+        """One pass: every (qubits, U) of `ops` in one C call. `fused` groups them into LDS-tile
         launches (order kept for ops sharing a qubit); returns the number of HBM round trips.
         `ops` may also be the tuple returned by `pack_ops` (plans that run repeatedly pack once)."""
         if not len(ops):
@@ -551,6 +559,41 @@ class DeviceChunk:
         b = np.asarray(bits, dtype=np.int32)
         _lib.check(_lib.load().qsim_unpack_all(self._h, len(b), _lib.ptr(b), buf._h, int(skip_pattern),
                                                int(piece), int(n_pieces)))
+
+
+class Cycle:
+    """The prepared passes of a cyclic plan on chunks of k qubits (qsim_cycle_create): `head`, `steady` and `tail` are
+    (ops, tile masks, earliest or None) each -- with the op list L = head . tail as a product, R executions are
+    head (tail . head)^(R-1) tail, and `steady` = tail . head may need a pass fewer than L.  `passes`: the three counts."""
+
+    def __init__(self, k: int, head, steady, tail):
+        keep, lists = [], []
+        for ops, masks, earliest in (head, steady, tail):
+            nq, qs, mats = as_packed(ops)
+            tm = np.ascontiguousarray(masks if masks is not None else [], dtype=np.uint64)
+            place = None if earliest is None else np.ascontiguousarray(earliest, dtype=np.int32)
+            if place is not None and len(place) != len(nq):
+                raise ValueError("one earliest pass per op expected")
+            keep.append((nq, qs, mats, tm, place))
+            lists.append(_lib.CycleList(len(nq), _lib.ptr(nq).value, _lib.ptr(qs).value, _lib.ptr(mats).value, len(tm),
+                                        _lib.ptr(tm).value if len(tm) else None, None if place is None else _lib.ptr(place).value))
+        counts = np.zeros(3, dtype=np.int32)
+        self._h = C.c_void_p()
+        _lib.check(_lib.load().qsim_cycle_create(int(k), C.byref(lists[0]), C.byref(lists[1]), C.byref(lists[2]), _lib.ptr(counts),
+                                                 C.byref(self._h)))
+        self.k = k
+        self.passes = tuple(int(x) for x in counts)
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            _lib.load().qsim_cycle_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # best effort
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def split_piece_count(k: int, m: int, parts: int) -> int:

@@ -1,5 +1,5 @@
 """The host planner of libqsim_hip.so in Python: what the pass builder would do with an op list, without a device
-(csrc/abi_plan.h: qsim_plan_ops, qsim_lower_pass_images, qsim_plan_ops_tiled, qsim_plan_ops_placed, qsim_plan_balance, qsim_plan_search, qsim_plan_search_triples, qsim_plan_count_layouts, qsim_plan_peek_pass,
+(csrc/abi_plan.h: qsim_plan_ops, qsim_lower_pass_images, qsim_plan_ops_tiled, qsim_plan_ops_placed, qsim_plan_balance, qsim_plan_search, qsim_plan_search_triples, qsim_plan_search_cycle, qsim_plan_count_layouts, qsim_plan_peek_pass,
 qsim_rewrite_ops_priced; csrc/tile_launch.h: qsim_tiles_per_workgroup; csrc/abi_rotation.h: qsim_plan_pauli_rotations).
 
 A thin binding.  `ops` is [(qubits, U), ...] or the tuple `pack_ops` returns (`device.as_packed`).  Return codes become
@@ -161,6 +161,40 @@ def search_triples(n: int, ops, triples=None, beam: int = 0, threads: int = 1, f
         histogram[None] = int(hist[-1])
     return {"passes": p, "index": index[:k].copy(), "triples": found[:k].copy(), "masks": masks[:k * p].reshape(k, p).copy(),
             "searched": m, "histogram": histogram}
+
+
+def search_cycle(n: int, ops, triples, plain_passes=None, beam: int = 0, threads: int = 1) -> list:
+    """Cyclic plans of ONE op list L that runs again and again, under the line-qubit triples given (qsim_plan_search_cycle):
+    L.L is searched under every triple, L is cut at the first pass of that plan which holds an op of the second copy into a
+    head A and a tail B, and A, B.A and B are searched under the same triple -- R executions are A (B.A)^(R-1) B
+    (`device.Cycle`).  `plain_passes`: the passes of L under every triple, where known (else searched here).  Returns one
+    dict per triple with the fewest steady passes, if those are fewer than its plain passes (an empty list: no cycle):
+    `index` (position in `triples`), `triple`, `plain` / `head` / `steady` / `tail` (pass counts), `is_tail` (bool per op
+    of L: it belongs to B; inside A and B the ops keep the order of L) and `masks` (three uint64 arrays: the tiles of A,
+    B.A and B on the triple's index bits)."""
+    nq, qubits, mats = as_packed(ops)
+    tri = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+    m = len(tri)
+    if not m:
+        raise ValueError("an empty list of triples")
+    plain = None if plain_passes is None else np.ascontiguousarray(plain_passes, dtype=np.int32)
+    if plain is not None and len(plain) != m:
+        raise ValueError("one plain pass count per triple expected")
+    count = C.c_int32()
+    index, found, passes = np.zeros(m, dtype=np.int32), np.zeros((m, 3), dtype=np.int32), np.zeros((m, 4), dtype=np.int32)
+    tail = np.zeros((m, max(1, len(nq))), dtype=np.uint8)
+    room = min(_MASK_ROOM, 3 * m * max(1, len(nq)))
+    masks = np.zeros(room, dtype=np.uint64)
+    _lib.check(_lib.load().qsim_plan_search_cycle(n, len(nq), ptr(nq), ptr(qubits), ptr(mats), m, ptr(tri), ptr(plain), beam, threads,
+                                                  C.byref(count), ptr(index), ptr(found), ptr(passes), ptr(tail), ptr(masks), room))
+    out, at = [], 0
+    for f in range(count.value):
+        cuts = at + np.concatenate([[0], np.cumsum(passes[f, 1:])])
+        out.append({"index": int(index[f]), "triple": [int(q) for q in found[f]], "plain": int(passes[f, 0]), "head": int(passes[f, 1]),
+                    "steady": int(passes[f, 2]), "tail": int(passes[f, 3]), "is_tail": tail[f, :len(nq)].astype(bool),
+                    "masks": [masks[cuts[w]:cuts[w + 1]].copy() for w in range(3)]})
+        at = int(cuts[3])
+    return out
 
 
 def rewrite_ops(n: int, ops, stats: dict = None, engine_costs=None) -> list:

@@ -40,6 +40,8 @@ class GpuPlan(list):
     placed: list | None = None           # per batch the placement of its ops over the named passes (int32 per op: `planner.balance`), or None
     l2p: list | None = None
     model_ms: tuple | None = None        # (identity, chosen) totals of the tile-cost model over the passes, when a layout was chosen
+    cycle = None                         # a cyclic plan (`device.Cycle`): `execute` defers the tail of every execution to the next; the
+                                         # list itself then holds the steady op list, for callers that look at it
 
 
 class SingleGpuEngine(StateCalls):
@@ -65,6 +67,8 @@ class SingleGpuEngine(StateCalls):
     LAYOUT_CANDIDATES = 63         # random line-qubit triples (next to the identity) searched in one library call (qsim_plan_search_triples)
     LAYOUT_BEAM = 0                # beam width of the pass search (0: the library's default)
     LAYOUT_FINALISTS = 8           # minimum-pass layouts timed on the device (tune_on_device, |0..0> state only)
+    CYCLES = True                  # plans of one op list made for LAYOUT_MIN_REPEATS executions or more may be cyclic (`planner.search_cycle`);
+                                   # False: every execution is planned as if it stood alone (A/B runs)
     ENGINE_PRICING = True          # plans made for many executions price the gate engine (runner/engine_cost.py): rule (d) of the
                                    # op rewrite, and ops that need no tile leave the passes whose records cost more than their memory time
 
@@ -147,7 +151,7 @@ class SingleGpuEngine(StateCalls):
         import time
         t0 = time.perf_counter()
         tune = self.tune_on_device and self._zero            # (timing runs overwrite the state: only |0..0> can be put back)
-        plans = self.finalist_plans(batches, self.LAYOUT_FINALISTS if tune else 4)
+        plans = self.finalist_plans(batches, self.LAYOUT_FINALISTS if tune else 4, repeats)
         chosen = plans[0]
         if tune and len(plans) > 1:
             timed = self._time_on_device(plans)
@@ -156,11 +160,13 @@ class SingleGpuEngine(StateCalls):
         chosen.layout_info["seconds"] = round(time.perf_counter() - t0, 3)
         return chosen
 
-    def finalist_plans(self, batches, n_finalists: int) -> list:
+    def finalist_plans(self, batches, n_finalists: int, repeats: int = 1) -> list:
         """The plans of up to n_finalists minimum-pass layouts of the op lists `batches` (`choose_plan_layout` over the
         identity and LAYOUT_CANDIDATES random line-qubit triples), lowest modelled time first: what `plan_batches` chooses
-        from -- the first, or the one the device runs fastest (tune_on_device)."""
-        from quantum_simulations_amd.kernel.device import pack_ops
+        from -- the first, or the one the device runs fastest (tune_on_device).  One op list planned for `repeats` >=
+        LAYOUT_MIN_REPEATS executions (and CYCLES): the cyclic plans found for it are finalists too, next to the plain ones."""
+        from quantum_simulations_amd.kernel.device import Cycle, pack_ops
+        cycle_repeats = repeats if self.CYCLES and len(batches) == 1 and repeats >= self.LAYOUT_MIN_REPEATS else 0
         # What the planner is given: the batches with their X / Y gates pushed into neighbouring gates and their H-framed
         # CNOTs turned into CZ (csrc/op_rewrite.h) -- the same amplitudes from fewer ops that need their target inside a
         # tile, hence fewer passes (16 -> 13 on the 28-qubit bench circuit).  `passes_identity` stays what it was:
@@ -181,9 +187,22 @@ class SingleGpuEngine(StateCalls):
         priced = None if costs is None else [planner.rewrite_ops(self.n, ops, None, costs) for ops in own_batches]
         own_identity = int(_count_passes(self.n, own_batches, np.arange(self.n, dtype=np.int32)[None, :], 1)[0])
         finalists = choose_plan_layout(self.n, batches, self.LAYOUT_CANDIDATES, n_finalists=n_finalists,
-                                       all_finalists=True, beam=self.LAYOUT_BEAM, engine_costs=costs, priced_batches=priced)
+                                       all_finalists=True, beam=self.LAYOUT_BEAM, engine_costs=costs, priced_batches=priced,
+                                       cycle_repeats=cycle_repeats)
 
         def build(l2p, masks, info):
+            cyc = info.pop("cycle", None)
+            if cyc is not None:                                 # (head, steady, tail: `planned` is the steady list)
+                info.pop("planned", None)
+                info.pop("placed", None)
+                plan = GpuPlan([pack_ops(cyc["planned"][1])])
+                plan.cycle = Cycle(self.n, *zip(cyc["planned"], cyc["tiles"], cyc["placed"]))
+                plan.tiles, plan.placed = masks, [cyc["placed"][1]]
+                plan.l2p = None if l2p == list(range(self.n)) else l2p
+                plan.model_ms = info["model_ms"]
+                plan.layout_info = dict(info, passes_identity=own_identity, rewrite=dict(rewrite), cycle_passes=dict(
+                    zip(("head", "steady", "tail"), plan.cycle.passes), plain=cyc["plain_passes"]))
+                return plan
             planned = info.pop("planned", None) or [[([l2p[q] for q in qs], U) for qs, U in ops] for ops in batches]
             plan = GpuPlan([pack_ops(ops) for ops in planned])
             plan.tiles = masks
@@ -197,7 +216,9 @@ class SingleGpuEngine(StateCalls):
     def _time_on_device(self, plans) -> list:
         """Milliseconds of every plan on the device.  The cost model cannot rank the minimum-pass layouts (measured: 3 %
         apart, uncorrelated with the model): the device can -- the better of two timed executions of each on the (zero)
-        state, which is |0..0> again afterwards."""
+        state, which is |0..0> again afterwards.  A cyclic plan is timed alike: after its first execution (the head) the
+        timed ones run its steady passes -- `time_begin` / `time_end` do not run a deferred tail -- and `init_zero_state`
+        drops the tail that is left."""
         timed = []
         for p in plans:
             self.init_zero_state()
@@ -229,6 +250,9 @@ class SingleGpuEngine(StateCalls):
         self._adopt_layout(getattr(plan, "l2p", None))
         self._zero = False
         self.last_passes = 0
+        if getattr(plan, "cycle", None) is not None and self.mode != "per-gate":
+            self.last_passes = self.state.apply_cycle(plan.cycle)
+            return
         tiles = getattr(plan, "tiles", None) or [None] * len(plan)
         placed = getattr(plan, "placed", None) or [None] * len(plan)
         for ops, masks, place in zip(plan, tiles, placed):

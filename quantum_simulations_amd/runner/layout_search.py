@@ -34,6 +34,8 @@ def _count_passes(n: int, batches, layouts: np.ndarray, threads: int) -> np.ndar
 
 
 PLACED_PER_FINALIST = 4            # minimum-pass layouts placed and priced for every finalist `choose_plan_layout` returns
+CYCLE_FINALISTS = 4                # cyclic plans (`planner.search_cycle`) placed and priced next to the plain finalists, at most
+CYCLE_STEADY_WEIGHT = 8            # most copies of the steady tiles the placement of a cyclic plan sets against one of its head and tail tiles
 
 
 def candidate_triples(n: int, n_candidates: int, seed: int) -> np.ndarray:
@@ -85,7 +87,7 @@ def _search_triples(n: int, batches, triples, layouts, beam: int, threads: int) 
 
 
 def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 20260504, n_finalists: int = 4,
-                       all_finalists: bool = False, beam: int = 0, engine_costs=None, priced_batches=None):
+                       all_finalists: bool = False, beam: int = 0, engine_costs=None, priced_batches=None, cycle_repeats: int = 0):
     """(l2p, tile masks per batch on the chosen index bits, info) for the op lists `batches` (logical qubits).  The three
     qubits on the line bits belong to every tile, so they decide how many passes a plan needs; which index bits the OTHER
     qubits live on does not (a relabelling of the bits >= 3 maps every valid pass sequence to a valid one).  So: for the
@@ -100,7 +102,14 @@ def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 2026
     engine time of its records); `priced_variant` then chooses between `batches` and `priced_batches` (the same lists
     under rule (d) of the rewrite, optional) and places the ops that need no tile: info gains `planned` (the op lists to
     run, on their index bits), `placed` (their placements, per batch) and the modelled split (`model_split_ms`), and the
-    finalists rank by that total instead of the memory model alone."""
+    finalists rank by that total instead of the memory model alone.
+    cycle_repeats > 0 (one op list, all_finalists): the plan is made for that many executions one after the other, and the
+    cyclic plans of the list under its minimum-pass triples (`planner.search_cycle`: the tail of one execution runs with
+    the head of the next, a pass fewer per execution where one is found) join the finalists, after n_finalists plain ones.
+    One layout serves the three lists of a cycle: its other qubits are placed over the steady tiles, min(cycle_repeats,
+    CYCLE_STEADY_WEIGHT) times each, and the head and tail tiles once; pricing applies to each list as to one list; the
+    model total is that of the steady passes.  info["cycle"]: `planned`, `tiles`, `placed` (three each: head, steady,
+    tail), `passes` (the three counts) and `plain_passes`."""
     import os
 
     from quantum_simulations_amd import _lib
@@ -158,10 +167,62 @@ def choose_plan_layout(n: int, batches, n_candidates: int = 31, seed: int = 2026
                 n, on_bits(batches), None if priced_batches is None else on_bits(priced_batches), final_masks, engine_costs)
             info["passes_chosen"] = info["model_split_ms"]["pass_count"]       # (a list under rule (d) may finish a pass early)
         return l2p, final_masks, info
+    def modelled(r):
+        return r[2]["model_split_ms"]["passes"] if "model_split_ms" in r[2] else r[2]["model_ms"][1]
+
+    def cycle_tiles(c):                                         # (the steady tiles weigh `cycle_repeats` to one, up to the cap)
+        weights = [1, max(1, min(int(cycle_repeats), CYCLE_STEADY_WEIGHT)), 1]
+        return [[b for b in range(tile_layout.LOW, n) if (int(m) >> b) & 1] for ms, w in zip(c["masks"], weights) for m in list(ms) * w]
+
+    def cyclic(job):
+        c, annealings = job
+        f = sorted(found)[c["index"]]
+        first = [int(x) for x in layouts[f]]
+        ops = batches[0]
+        head = [op for op, late in zip(ops, c["is_tail"]) if not late]
+        tail = [op for op, late in zip(ops, c["is_tail"]) if late]
+        parts, counts = [head, tail + head, tail], [c["head"], c["steady"], c["tail"]]
+        second = min(annealings, key=lambda r: r[2])[0]
+
+        def moved(lists, lay):
+            return [[([lay[first[q]] for q in qs], U) for qs, U in part] for part in lists]
+
+        def on_bits(lay):
+            return [np.array([sum(1 << lay[b] for b in range(n) if (int(m) >> b) & 1) for m in ms], dtype=np.uint64) for ms in c["masks"]]
+        masks = on_bits(second)
+        # (as for a plain plan: a placement under which a list would replay into other passes is dropped for the searched one)
+        if [planner.pass_count(n, part, ms) for part, ms in zip(moved(parts, second), masks)] != counts:
+            second = list(range(n))
+            masks = on_bits(second)
+        l2p = [second[first[q]] for q in range(n)]
+        info = {"passes_identity": greedy_identity, "passes_chosen": c["steady"], "candidates": n_candidates + 1,
+                "candidates_by_passes": dict(by_passes), "minimum_pass_triples": len(found), "line_qubits": [int(q) for q in triples[f]],
+                "beam": int(beam) if beam > 0 else "default",
+                # (of the steady passes alone: what the annealing priced holds their copies and the head and tail tiles too)
+                "model_ms": tuple(round(float(pass_memory_us(n, ms).sum()) / 1e3, 3) for ms in (on_bits(list(range(n)))[1], masks[1]))}
+        planned, places = moved(parts, second), [None, None, None]
+        if engine_costs is not None:
+            for w in range(3):
+                priced = planner.rewrite_ops(n, planned[w], None, engine_costs)
+                (planned[w],), (places[w],), split = priced_variant(n, [planned[w]], [priced], [masks[w]], engine_costs)
+                counts[w] = split["pass_count"]
+                if w == 1:
+                    info["model_split_ms"] = split
+            info["passes_chosen"] = counts[1]
+        info["cycle"] = {"planned": planned, "tiles": masks, "placed": places, "passes": [int(x) for x in counts], "plain_passes": int(c["plain"])}
+        return l2p, [masks[1]], info
     with ThreadPoolExecutor(threads) as pool:
         out = list(pool.map(placed, range(len(tried))))
-    out.sort(key=lambda r: r[2]["model_split_ms"]["passes"] if "model_split_ms" in r[2] else r[2]["model_ms"][1])
-    return out[:max(1, n_finalists)] if all_finalists else out[0]
+        out.sort(key=modelled)
+        out = out[:max(1, n_finalists)]
+        if cycle_repeats > 0 and all_finalists and len(batches) == 1 and len(batches[0]) >= 2:
+            plain = [best] * len(found)
+            cycles = planner.search_cycle(n, batches[0], triples[sorted(found)], plain, beam, threads)[:CYCLE_FINALISTS]
+            anneal = list(pool.map(lambda job: tile_layout.choose_layout(cycle_tiles(job[0]), n, seed=job[1]),
+                                   [(c, s) for c in cycles for s in range(1, 9)]))
+            out += list(pool.map(cyclic, [(c, anneal[8 * i:8 * i + 8]) for i, c in enumerate(cycles)]))
+            out.sort(key=modelled)
+    return out if all_finalists else out[0]
 
 
 def pass_memory_us(n: int, masks) -> np.ndarray:
